@@ -10,6 +10,11 @@ images (weak scaling, no data-path collective); value = images all ranks produce
     python bench.py --gpus 1 --steps 3 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \
         bench.py --gpus 8 --steps 3 --warmup 1
+
+A plain run sets up, warms up, times `--steps` passes and prints the line.  Everything else the line can carry (the
+roofline / FLOP census pass, host-input, shared-sample and f16x3 parity passes, the fp16 / training / SDXL legs, the CPU
+baseline, the training all-reduce time) runs only with --full.  --dump-outputs DIR writes what the last timed pass
+returned as DIR/<name>.npy (float32; rank 0), from inputs that are the same on every run with the same arguments.
 """
 import argparse
 import json
@@ -30,6 +35,26 @@ PEAK_FP8_TFLOPS = 5000.0                              # dense e4m3 (block-scaled
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor as out_dir/<name>.npy in float32.  A tensor larger than its share of DUMP_BYTES is
+    replaced by a fixed sample of its flattened elements (seeded indices, ascending), the same on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        sampled = t.numel() > cap
+        if sampled:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        arr = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+        log(f"[bench] wrote {name}.npy {list(arr.shape)}{' (sampled)' if sampled else ''} to {out_dir}")
 
 
 def build_pipeline(precision, device, keep_cpu_sd=False, model="sd15"):
@@ -139,6 +164,8 @@ def stub_main(a, D):
     rank, world, _ = D.init_process_group("gloo")
     if world != a.gpus:
         raise SystemExit(f"bench.py: WORLD_SIZE={world} but --gpus {a.gpus}")
+    if a.dump_outputs:
+        raise SystemExit("bench.py: --stub computes nothing to dump")
     for _ in range(a.warmup):
         time.sleep(0.001)
     D.barrier()
@@ -224,9 +251,14 @@ def train_main(a, D):
     reduce_device = "cpu" if backend == "gloo" else device
     elapsed = D.max_over_ranks(time.perf_counter() - t0, device=reduce_device)
     assert torch.isfinite(loss).all() and torch.isfinite(norm).all()
+    if a.dump_outputs and rank == 0:
+        # what train_step hands back, and a fixed sample of each trainable network's fp32 master weights after the step
+        dump_outputs(a.dump_outputs, {"loss": loss, "grad_norm": norm,
+                                      **{f"{type(m).__name__.lower()}_weights": m.flat_w[:m.num_arena_floats()]
+                                         for m in model.get_trainable_modules()}})
     # configs[3] asks for the all-reduce time beside samples/s: one un-overlapped pass over every gradient bucket, after
     # the timed steps (inside a step the buckets are reduced on a side stream under the backward pass)
-    ar_ms = sync.time_all_reduce() if sync is not None else None
+    ar_ms = sync.time_all_reduce() if sync is not None and a.full else None
     ar_bytes = sum(m.num_arena_floats() for m in model.get_trainable_modules()) * 4
     if rank == 0:
         gflop = 3 * 441.3 + 2 * 803.3            # per sample: BrushNet fwd + dgrad + wgrad, frozen UNet fwd + dgrad (no CFG)
@@ -285,6 +317,12 @@ def main():
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true",
                     help="skip the secondary legs of the default line: fp16 mode, the training step (configs[3]) and SDXL fp8 (configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary measurement of the line (roofline, host inputs, shared "
+                         "sample, f16x3 parity, fp16 / train / SDXL legs, CPU baseline, training all-reduce); the --no-* options "
+                         "switch single ones off again.  Without it only the headline passes run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB; rank 0)")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(sys.argv[1:], a.gpus))          # before anything touches the GPU
@@ -323,7 +361,7 @@ def main():
     # 100+-core host (cpu_baseline sets its own thread count later)
     torch.set_num_threads(max(1, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 8)))
 
-    want_cpu = rank == 0 and world == 1 and not a.no_cpu_baseline and not xl
+    want_cpu = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not xl
     pipe, sds = build_pipeline(a.precision, device, keep_cpu_sd=want_cpu, model=a.model)
     # every rank works on its own images: rank-dependent seed, same shapes (weak scaling)
     inp = synth.pipeline_inputs(a.batch, a.size, a.size, seed=1234 + rank, cross_dim=2048 if xl else 768)
@@ -371,6 +409,8 @@ def main():
     torch.cuda.synchronize()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, device=reduce_device)
     assert torch.isfinite(img).all(), "non-finite output image"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"images": img})
 
     images = a.batch * a.steps * world
     value = images / elapsed
@@ -380,7 +420,7 @@ def main():
     step_tflops = a.batch * gflop * 1e9 / step_s / 1e12 if gflop else None
 
     roofline = None
-    if rank == 0 and not a.no_profile:
+    if a.full and rank == 0 and not a.no_profile:
         # live per-launch timing of the dominant kernel family (mf_gemm_conv: every conv / linear, ~90 % of the
         # algorithmic FLOPs) over ONE denoise step, HIP events on the launch stream
         x2 = torch.cat([inp["latents"].to(device)] * 2)
@@ -442,7 +482,7 @@ def main():
                                               "frac = time at each launch's own dense MFMA peak (fp8 Linears 5 PF, the rest 2.5 PF) / step time"})}
 
     host_inputs = None
-    if rank == 0 and world == 1 and a.inputs == "device" and not a.no_profile and not xl:
+    if a.full and rank == 0 and world == 1 and a.inputs == "device" and not a.no_profile and not xl:
         # the same passes with the inputs handed over as HOST tensors (what a caller of the reference's pipeline does):
         # CPU preprocessing + pinned-staging upload inside the pass.  Reported beside `value`, never as `value`.
         inp = inp_host
@@ -457,7 +497,7 @@ def main():
                        "note": "inputs as host tensors: CPU preprocessing and the PCIe upload (pinned staging) inside the pass"}
 
     shared = None
-    if rank == 0 and world == 1 and not a.no_parity_mode and not a.no_profile and not xl:
+    if a.full and rank == 0 and world == 1 and not a.no_parity_mode and not a.no_profile and not xl:
         # Secondary line, never `value`: the same workload with ONE VAE-posterior sample of the conditioning latents used
         # for both classifier-free-guidance halves (the reference draws one per half, pipeline_brushnet.py:1188 on the
         # image doubled at :771-772).  BrushNet is attention-free, so with identical conditioning its two halves are the
@@ -483,7 +523,7 @@ def main():
         inp = inp_timed
 
     parity = None
-    if rank == 0 and world == 1 and not a.no_parity_mode and not a.no_profile and not xl and a.precision == "bf16":
+    if a.full and rank == 0 and world == 1 and not a.no_parity_mode and not a.no_profile and not xl and a.precision == "bf16":
         # The SAME workload in the precision mode that meets BASELINE.json's 1e-3 latent bound against the reference
         # (f16x3: fp32 storage, three fp16 MFMAs per product; asserted in tests/ and smoke()): one warm-up, then timed.
         del pipe
@@ -517,7 +557,7 @@ def main():
 
     # ---- secondary legs of the driver's line: never `value` ---------------------------------------------
     fp16_mode = train_leg = sdxl_leg = None
-    extra = (rank == 0 and world == 1 and not a.no_extra_legs and not a.no_parity_mode and not a.no_profile and not xl
+    extra = (a.full and rank == 0 and world == 1 and not a.no_extra_legs and not a.no_parity_mode and not a.no_profile and not xl
              and a.precision == "bf16" and a.batch == 4 and a.size == 512)
     if extra:
         # (1) the SAME workload in the reference scripts' default precision, torch_dtype=torch.float16 (test_brushnet.py:122-126):
@@ -558,7 +598,7 @@ def main():
         def child(args, keys, profile=False):
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), *args, "--no-cpu-baseline", "--no-parity-mode",
-                                    *([] if profile else ["--no-profile"]), "--no-extra-legs"], capture_output=True, text=True, timeout=900)
+                                    *(["--full"] if profile else ["--no-profile"]), "--no-extra-legs"], capture_output=True, text=True, timeout=900)
                 line = next((l for l in reversed(r.stdout.splitlines()) if l.startswith("{") and '"metric"' in l), None)
                 if line is None:
                     return {"error": (r.stderr or r.stdout)[-300:]}

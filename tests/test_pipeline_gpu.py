@@ -457,6 +457,33 @@ def test_bench_two_ranks_on_one_device():
     assert abs(rec["value"] - 2 / (rec["ms_per_step"] * 1e-3)) < 0.02 * rec["value"]
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_images(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps passes, runs none of the secondary legs, and --dump-outputs DIR
+    writes the images the last timed pass returned as DIR/images.npy (float32, [batch, 3, size, size], in [0, 1])."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out_dir = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--batch", "1", "--size", "256", "--denoise-steps", "3", "--dump-outputs", str(out_dir)],
+                         capture_output=True, text=True, timeout=1500, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["unit"] == "images/sec" and rec["higher_is_better"] is True and rec["dtype"] == "bf16"
+    assert out.stderr.count("[bench] pass ") == 2
+    assert abs(rec["value"] - 1 / (rec["ms_per_step"] * 1e-3)) < 0.02 * rec["value"]
+    for leg in ("roofline", "parity_mode", "shared_conditioning_sample", "cpu_baseline", "host_inputs", "fp16_mode", "train_step", "sdxl"):
+        assert rec[leg] is None, leg
+    img = np.load(out_dir / "images.npy")
+    assert img.dtype == np.float32 and img.shape == (1, 3, 256, 256)
+    assert np.isfinite(img).all() and img.min() >= 0.0 and img.max() <= 1.0 and img.std() > 0
+
+
 @pytest.mark.parametrize("prec,tol", [("f16x3", 1e-3), ("bf16", None), ("fp16", None)])
 def test_baseline_config1_batch4_512_against_reference(prec, tol):
     """BASELINE.json configs[1] sizes — batch 4 x 512 x 512, the tile choices the autotuner makes at M = 32768 — through

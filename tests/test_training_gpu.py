@@ -915,7 +915,7 @@ def test_baseline_config3_full_size_step_determinism_and_forced_rccl_sync(train_
 def test_bench_train_under_torchrun_with_rccl_reports_all_reduce():
     """bench.py --mode train launched the way the driver launches N > 1 (python -m torch.distributed.run ... bench.py --gpus N)
     with the default backend (RCCL) and MF_FORCE_GRAD_SYNC=1 on this one GPU: the rendezvous, the bucketed exchange under
-    the backward pass and time_all_reduce() all run over RCCL, and the JSON line carries all_reduce.ms."""
+    the backward pass and time_all_reduce() (a --full measurement) all run over RCCL, and the JSON line carries all_reduce.ms."""
     import json
     import subprocess
     import sys
@@ -925,7 +925,7 @@ def test_bench_train_under_torchrun_with_rccl_reports_all_reduce():
     env["MF_FORCE_GRAD_SYNC"] = "1"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     out = subprocess.run(torchrun_argv(1) + [os.path.join(root, "bench.py"), "--gpus", "1", "--mode", "train", "--steps", "1",
-                                             "--warmup", "1", "--batch", "2", "--size", "256"], capture_output=True, text=True, timeout=1500, env=env)
+                                             "--warmup", "1", "--batch", "2", "--size", "256", "--full"], capture_output=True, text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

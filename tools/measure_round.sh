@@ -3,9 +3,10 @@
 : "${GRAFT_REPO_ROOT:?run through gpurun}"; : "${MF_SESSION_OUT:?run through tools/gpu_session.sh}"
 cd "$GRAFT_REPO_ROOT" || exit 1
 out="$MF_SESSION_OUT"
+repo="$(pwd)"
 timeout 3000 python -m pytest tests -x -q -m gpu > "$out/pytest_gpu.txt" 2>&1; echo "pytest -m gpu rc $?"; tail -n 4 "$out/pytest_gpu.txt"
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$out/smoke.txt" 2>&1; echo "smoke rc $?"; tail -n 3 "$out/smoke.txt"
-timeout 1800 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc $?"
+timeout 1800 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "bench rc $?"
 python - "$out/bench_default.json" <<'PY'
 import json, sys
 r = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
@@ -15,7 +16,7 @@ for k in ("parity_mode", "fp16_mode", "train_step", "sdxl"):
     v = r.get(k) or {}
     print(k, {a: v.get(a) for a in ("value", "unit", "denoise_step_ms", "ms_per_step", "error")})
 PY
-(cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o b -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-extra-legs --no-parity-mode --no-cpu-baseline > "$out/prof_bench.json" 2> "$out/prof_bench.err")
+(cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o b -- python3 "$repo/bench.py" --full --no-extra-legs --no-parity-mode --no-cpu-baseline > "$out/prof_bench.json" 2> "$out/prof_bench.err")
 find "$out" -name "*kernel_trace.csv" -delete; find "$out" -name "*.db" -delete
 head -n 12 "$out"/prof/*/b_kernel_stats.csv 2>/dev/null | cut -c1-200 || find "$out/prof" -name "*stats*" | head
 bash tools/pmc_step.sh > "$out/pmc_step.txt" 2>&1; cp gpurun_out/pmc_gemm_family.json "$out/" 2>/dev/null; cat "$out/pmc_gemm_family.json"

@@ -29,7 +29,7 @@ for n in 1 2 4 8; do
   run "$n" "infer_n$n" --steps 5 --warmup 2 --no-cpu-baseline --no-parity-mode --no-extra-legs
 done
 for n in 1 8; do
-  run "$n" "train_n$n" --mode train --precision bf16 --steps 10 --warmup 3
+  run "$n" "train_n$n" --mode train --precision bf16 --steps 10 --warmup 3 --full
 done
 # the overlap fraction of the gradient exchange: the same 8-rank step with the exchange forced AFTER the backward pass
 MF_GRAD_SYNC_SERIAL=1 run 8 train_n8_serial --mode train --precision bf16 --steps 10 --warmup 3

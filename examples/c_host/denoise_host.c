@@ -1,9 +1,11 @@
 /* A denoise loop with no Python in the process: loads a step program exported by
  *   pipe.export_denoise_step("step.mfprog", ...)        (reflecting_reality_amd/pipeline.py, program.py)
  * gives every buffer device memory, and calls mf_denoise_step_fused (include/mfhip.h) once per timestep — the loop body of the
- * reference's pipelines/brushnet/pipeline_brushnet.py:1250-1332 behind one C entry.  Between steps the host copies the step's rows
- * of the schedule's tables (DDIM coefficients, the two time-embedding tables: named constants of the file) into the io buffers,
- * which is all the reference's loop does on the host besides launching.
+ * reference's pipelines/brushnet/pipeline_brushnet.py:1250-1332 behind one C entry.  Between steps the host copies row i of every
+ * table of the schedule ("table.X", a named constant of the file) into the io buffer "X" — the DDIM coefficients ("coef4") or the
+ * PNDM / UniPC row ("sched_row", a program exported with scheduler="device"), and the two time-embedding tables — which is all the
+ * reference's loop does on the host besides launching.  A PNDM / UniPC step keeps the scheduler's history in the io buffer
+ * "sched_state" between runs.
  *
  *   gcc -O2 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude examples/c_host/denoise_host.c \
  *       -Lreflecting-reality_amd/lib -lmfhip -L/opt/rocm/lib -lamdhip64 -o denoise_host
@@ -99,19 +101,44 @@ int main(int argc, char** argv) {
     fclose(f);
     printf("program: %d calls, %d buffers (%.1f MB constants, %.1f MB workspace, %.3f MB io)\nmeta: %s\n", mf_program_num_calls(prog), nbuf,
            total[MF_PROGRAM_CONST] / 1e6, total[MF_PROGRAM_WORKSPACE] / 1e6, total[MF_PROGRAM_IO] / 1e6, mf_program_meta(prog));
-    int64_t lat_bytes = 0, coef_bytes = 0, tu_bytes = 0, tb_bytes = 0, tab_c = 0, tab_u = 0, tab_b = 0;
+    int64_t lat_bytes = 0;
     void* lat = device_buffer(prog, "latents", &lat_bytes, dev);
-    void* coef = device_buffer(prog, "coef4", &coef_bytes, dev);
-    void* tu = device_buffer(prog, "temb_unet", &tu_bytes, dev);
-    void* tb = device_buffer(prog, "temb_brushnet", &tb_bytes, dev);
-    char* table_c = (char*)device_buffer(prog, "table.coef4", &tab_c, dev);
-    char* table_u = (char*)device_buffer(prog, "table.temb_unet", &tab_u, dev);
-    char* table_b = (char*)device_buffer(prog, "table.temb_brushnet", &tab_b, dev);
-    if (!lat || !coef || !tu || !tb || !table_c || !table_u || !table_b) {
-        fprintf(stderr, "not a denoise-step program (io buffers latents / coef4 / temb_* and their tables)\n");
+    if (!lat || !device_buffer(prog, "temb_unet", NULL, dev) || !device_buffer(prog, "temb_brushnet", NULL, dev)) {
+        fprintf(stderr, "not a denoise-step program (io buffers latents / temb_unet / temb_brushnet)\n");
         return 1;
     }
-    const int steps = (int)(tab_c / coef_bytes);
+    if (!device_buffer(prog, "coef4", NULL, dev) && !device_buffer(prog, "sched_row", NULL, dev)) {
+        fprintf(stderr, device_buffer(prog, "eps", NULL, dev)
+                            ? "this step program ends with the guided noise prediction (\"eps\"): its scheduler steps on the host. Export it "
+                              "with export_denoise_step(..., scheduler=\"device\") to run PNDM / UniPC here\n"
+                            : "not a denoise-step program (no scheduler update: io buffer coef4 or sched_row)\n");
+        return 1;
+    }
+    /* every "table.X" with an io buffer "X": row i goes into X before step i */
+    int ntab = 0, steps = -1;
+    void** tab_dst = (void**)calloc((size_t)nbuf, sizeof(void*));
+    const char** tab_src = (const char**)calloc((size_t)nbuf, sizeof(char*));
+    int64_t* tab_row = (int64_t*)calloc((size_t)nbuf, sizeof(int64_t));
+    for (int32_t i = 0; i < nbuf; ++i) {
+        int32_t kind; int64_t bytes, off, row_bytes = 0; const char* name;
+        MF_OKAY(mf_program_buffer_info(prog, i, &kind, &bytes, &off, &name));
+        if (strncmp(name, "table.", 6) != 0) continue;
+        void* dst = device_buffer(prog, name + 6, &row_bytes, dev);
+        const int32_t j = mf_program_find_buffer(prog, name + 6);
+        int32_t dst_kind = -1;
+        if (j >= 0) mf_program_buffer_info(prog, j, &dst_kind, NULL, NULL, NULL);
+        if (!dst || dst_kind != MF_PROGRAM_IO || row_bytes <= 0 || bytes % row_bytes) {
+            fprintf(stderr, "table %s: no io buffer %s whose size divides it\n", name, name + 6);
+            return 1;
+        }
+        if (steps >= 0 && bytes / row_bytes != steps) {
+            fprintf(stderr, "table %s has %lld rows, another table %d\n", name, (long long)(bytes / row_bytes), steps);
+            return 1;
+        }
+        steps = (int)(bytes / row_bytes);
+        tab_dst[ntab] = dst; tab_src[ntab] = (const char*)dev[i]; tab_row[ntab] = row_bytes; ++ntab;
+    }
+    if (steps < 1) { fprintf(stderr, "the program carries no schedule tables\n"); return 1; }
     if (in_path) {
         FILE* g = fopen(in_path, "rb");
         void* host = malloc((size_t)lat_bytes);
@@ -168,19 +195,32 @@ int main(int argc, char** argv) {
     }
     hipGraphExec_t exec = NULL;
     if (use_graph) {
-        /* a first eager run (nothing lazy is left to initialise, but it keeps the capture free of first-use work), on a copy of the latents */
-        void* keep;
-        HIP_OK(hipMalloc(&keep, (size_t)lat_bytes));
-        HIP_OK(hipMemcpyAsync(keep, lat, (size_t)lat_bytes, hipMemcpyDeviceToDevice, stream));
+        /* a first eager run (nothing lazy is left to initialise, but it keeps the capture free of first-use work); every io buffer it
+         * writes (the latents, a PNDM / UniPC history) is restored afterwards */
+        void** keep = (void**)calloc((size_t)nbuf, sizeof(void*));
+        for (int32_t i = 0; i < nbuf; ++i) {
+            int32_t kind; int64_t bytes;
+            MF_OKAY(mf_program_buffer_info(prog, i, &kind, &bytes, NULL, NULL));
+            if (kind != MF_PROGRAM_IO || bytes <= 0) continue;
+            HIP_OK(hipMalloc(&keep[i], (size_t)bytes));
+            HIP_OK(hipMemcpyAsync(keep[i], dev[i], (size_t)bytes, hipMemcpyDeviceToDevice, stream));
+        }
         MF_OKAY(mf_program_run(prog, stream));
-        HIP_OK(hipMemcpyAsync(lat, keep, (size_t)lat_bytes, hipMemcpyDeviceToDevice, stream));
+        for (int32_t i = 0; i < nbuf; ++i) {
+            int64_t bytes;
+            if (!keep[i]) continue;
+            MF_OKAY(mf_program_buffer_info(prog, i, NULL, &bytes, NULL, NULL));
+            HIP_OK(hipMemcpyAsync(dev[i], keep[i], (size_t)bytes, hipMemcpyDeviceToDevice, stream));
+        }
         HIP_OK(hipStreamSynchronize(stream));
         hipGraph_t graph;
         HIP_OK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
         MF_OKAY(mf_program_run(prog, stream));
         HIP_OK(hipStreamEndCapture(stream, &graph));
         HIP_OK(hipGraphInstantiateWithFlags(&exec, graph, hipGraphInstantiateFlagAutoFreeOnLaunch));
-        HIP_OK(hipFree(keep));
+        for (int32_t i = 0; i < nbuf; ++i)
+            if (keep[i]) HIP_OK(hipFree(keep[i]));
+        free(keep);
     }
     hipEvent_t e0, e1;
     HIP_OK(hipEventCreate(&e0));
@@ -189,9 +229,8 @@ int main(int argc, char** argv) {
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     for (int i = in_path ? 0 : 1; i < steps; ++i) {
-        HIP_OK(hipMemcpyAsync(coef, table_c + (size_t)i * coef_bytes, (size_t)coef_bytes, hipMemcpyDeviceToDevice, stream));
-        HIP_OK(hipMemcpyAsync(tu, table_u + (size_t)i * tu_bytes, (size_t)tu_bytes, hipMemcpyDeviceToDevice, stream));
-        HIP_OK(hipMemcpyAsync(tb, table_b + (size_t)i * tb_bytes, (size_t)tb_bytes, hipMemcpyDeviceToDevice, stream));
+        for (int k = 0; k < ntab; ++k)
+            HIP_OK(hipMemcpyAsync(tab_dst[k], tab_src[k] + (size_t)i * tab_row[k], (size_t)tab_row[k], hipMemcpyDeviceToDevice, stream));
         if (exec) HIP_OK(hipGraphLaunch(exec, stream));
         else MF_OKAY(mf_denoise_step_fused(prog, NULL, NULL, NULL, NULL, stream));      /* NULL: the bindings made above stay */
     }
@@ -214,6 +253,7 @@ int main(int argc, char** argv) {
         fclose(g);
     }
     free(host);
+    free(tab_dst); free(tab_src); free(tab_row);
     mf_program_destroy(prog);
     for (int32_t i = 0; i < nbuf; ++i) hipFree(dev[i]);
     free(dev);

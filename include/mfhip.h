@@ -59,7 +59,7 @@ extern "C" {
 #define MF_ACT_GEGLU4 2
 
 /* ABI version, bumped on any struct change; checked by the Python host at load time. */
-#define MF_ABI_VERSION 20
+#define MF_ABI_VERSION 21
 int mf_abi_version(void);
 const char* mf_last_error(void);
 /* sizeof() of the descriptor structs, so a foreign-language binding can verify its layout */
@@ -373,6 +373,38 @@ int mf_cfg_combine(const float* eps_u, const float* eps_c, float g, float* eps, 
 /* generic y = sum_i c[i]*x[i] (i < nin <= 6) — PNDM/PLMS linear multistep and _get_prev_sample
  * (scheduling_pndm.py:370-382,436-446) */
 int mf_axpby_n(const float* const* xs, const float* coefs, int32_t nin, float* y, int64_t n, void* stream);
+/* Device-side update of a multistep scheduler (PNDM, UniPC): ONE launch per denoise step does what mf_cfg_combine followed by the
+ * scheduler's mf_axpby_n calls does, bit for bit (same roundings, same order of terms, same FMA contraction).  The step's work is a
+ * row in DEVICE memory (so a captured hipGraph or a step program serves every step; the host copies the next row in, as it does
+ * for coef4).  The row's ops act on a per-element register file:
+ *   register 0               e = eu + g*(ec - eu), the guided noise prediction
+ *   register 1               the latents: the value on entry; the last value written is stored back (the new latents)
+ *   registers 2 .. 2+nslots-1  state[s][0..n) for s = register - 2: history kept by the caller between steps
+ *   registers above          temporaries of the step
+ * op: dst = sum_k coef[k] * reg[src[k]] (k < nterms <= MF_SCHED_MAX_TERMS: coef[0]*x0, then fmaf(coef[k], x_k, acc)), or
+ * nterms == 0: dst = reg[src[0]] (a move).  `load` / `store`: bit r = register r is read from / written back to memory (bits 1 and
+ * 2 .. 2+nslots-1 only).  Every element reads what it loads before it stores anything, so the update is in place.  The row comes from
+ * reflecting_reality_amd/schedulers.py (device_plan: a trace of the scheduler's own step()), which reads no slot it has not written.
+ * state: nslots * n floats; n % 4 == 0; latents, state, eps_u, eps_c 16-byte aligned. */
+#define MF_SCHED_MAX_OPS 8
+#define MF_SCHED_MAX_TERMS 6
+#define MF_SCHED_MAX_REGS 16
+typedef struct mf_sched_op {
+    int32_t dst;
+    int32_t nterms;
+    int32_t src[MF_SCHED_MAX_TERMS];
+    float coef[MF_SCHED_MAX_TERMS];
+} mf_sched_op;
+typedef struct mf_sched_row {
+    int32_t nops;
+    int32_t nslots;
+    uint32_t load;
+    uint32_t store;
+    mf_sched_op ops[MF_SCHED_MAX_OPS];
+} mf_sched_row;
+int mf_sizeof_sched_row(void);
+int mf_sched_step_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row, int64_t n,
+                      void* stream);
 /* training loss (examples/brushnet/train_brushnet_mirror.py:1433-1449): per_sample[r] = mean_i (pred[r][i] -
  * target[r][i])^2 * (weights ? weights[r] : 1) and loss[0] = mean_r per_sample[r]; fp32 in, double accumulation */
 int mf_mse_loss(const float* pred, const float* target, const float* weights, float* per_sample, float* loss,
@@ -608,8 +640,13 @@ int mf_program_run(mf_program* p, void* stream);
  * guidance, DDIM update — as one call: binds the io buffers "latents" (NCHW fp32, updated IN PLACE), "coef4" (the step's
  * {sqrt_at, sqrt_1m_at, sqrt_ap, dir_coef}, mf_cfg_ddim_step_dev), "temb_unet" / "temb_brushnet" (the step's rows of the two
  * time-embedding tables) and runs the program.  A NULL argument keeps the buffer's current binding.  A step exported under a
- * multistep scheduler (PNDM, UniPC: host-side state between steps, scheduling_pndm.py:321-390) has no "coef4": it ends with the guided
- * noise prediction e = eu + g (ec - eu) in the io buffer "eps" (pipeline_brushnet.py:1310-1312) and the host's scheduler steps from it. */
+ * multistep scheduler (PNDM, UniPC) has no "coef4"; it comes in one of two forms (export_denoise_step(..., scheduler=)):
+ *   "device": the update is inside (mf_sched_step_dev): io buffers "sched_row" (the step's row of the named constant
+ *             "table.sched_row", copied in like coef4) and "sched_state" (the scheduler's history, nslots * latents; it persists
+ *             between runs, so bind it once and leave it alone).  mf_denoise_step_fused(step, NULL, NULL, NULL, NULL, stream) then
+ *             runs a whole PNDM / UniPC step.
+ *   "host":   it ends with the guided noise prediction e = eu + g (ec - eu) in the io buffer "eps" (pipeline_brushnet.py:1310-1312)
+ *             and the host's scheduler steps from it. */
 int mf_denoise_step_fused(mf_program* step, void* latents, const void* coef4, const void* temb_unet, const void* temb_brushnet, void* stream);
 /* UNet2DConditionModel.forward (unet_2d_condition.py:1037-1311) with BrushNet's residuals injected (:1172-1177, 1218, 1262-1284):
  * io buffers "sample", "temb", "residual.<i>" (i < n_residuals, the order of brushnet.py:896-936: down, mid, up), "eps" (the noise

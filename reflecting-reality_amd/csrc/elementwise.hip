@@ -3,6 +3,9 @@
 // error-string plumbing.
 #include <stdarg.h>
 #include <string.h>
+
+#include <utility>
+
 #include "mf_common.h"
 
 static thread_local char g_err[512] = "";
@@ -16,6 +19,7 @@ extern "C" const char* mf_last_error(void) { return g_err; }
 extern "C" int mf_abi_version(void) { return MF_ABI_VERSION; }
 extern "C" int mf_sizeof_gemm_desc(void) { return (int)sizeof(mf_gemm_desc); }
 extern "C" int mf_sizeof_groupnorm_desc(void) { return (int)sizeof(mf_groupnorm_desc); }
+extern "C" int mf_sizeof_sched_row(void) { return (int)sizeof(mf_sched_row); }
 
 extern "C" int mf_split_overflow(int32_t reset, int32_t* raised, void* stream) {
     MF_CHECK_ARG(raised != nullptr, "mf_split_overflow: null pointer");
@@ -199,6 +203,66 @@ __global__ void axpby_kernel(AxpbyArgs a, float* y, int64_t n) {
         for (int k = 1; k < a.nin; ++k) v += a.c[k] * a.x[k][i];
         y[i] = v;
     }
+}
+
+// mf_sched_step_dev: CFG combine + the step's ops of a multistep scheduler on a per-element register file (include/mfhip.h).
+// Four elements per thread (16-byte loads / stores).  The row is read through scalar loads and readfirstlane'd, so every branch on
+// it is wave-uniform; registers are selected by unrolled compares against compile-time indices (no private array is indexed at run
+// time: 0 scratch).  The arithmetic is that of cfg_combine_kernel (fmaf(g, ec - eu, eu)) and axpby_kernel (c0 * x0, then
+// fmaf(c_k, x_k, acc)), written out so that the contraction cannot differ.
+constexpr int kSchedRegs = MF_SCHED_MAX_REGS;
+
+__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+// The register file is a local array of this one function and every index into it is a literal (fold expressions over Rs): SROA
+// keeps it in VGPRs.  (A helper taking the array by reference, or a loop over it, lets the optimizer turn the compare chain into a
+// load at a run-time offset first, and the array then lives in scratch.)
+template <int... Rs>
+__device__ __forceinline__ void sched_step_body(const f32x4_t* __restrict__ eu, const f32x4_t* __restrict__ ec, float g,
+                                                f32x4_t* __restrict__ lat, f32x4_t* __restrict__ state,
+                                                const mf_sched_row* __restrict__ row, int64_t n4, std::integer_sequence<int, Rs...>) {
+    static_assert(sizeof...(Rs) == kSchedRegs, "one index per register");
+    // (counts clamped to the struct: a malformed row never reads past it)
+    const int nops = min(uniform_i(row->nops), MF_SCHED_MAX_OPS), nslots = uniform_i(row->nslots);
+    const unsigned ldm = (unsigned)uniform_i((int)row->load), stm = (unsigned)uniform_i((int)row->store);
+    const f32x4_t zero = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        f32x4_t R[kSchedRegs];
+        const f32x4_t u = eu[i], c = ec[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) R[0][j] = __builtin_fmaf(g, c[j] - u[j], u[j]);
+        R[1] = (ldm & 2u) ? lat[i] : zero;
+        ((Rs >= 2 ? (R[Rs] = (Rs - 2 < nslots && ((ldm >> Rs) & 1u)) ? state[(int64_t)(Rs - 2) * n4 + i] : zero) : R[0]), ...);
+        for (int o = 0; o < nops; ++o) {
+            const mf_sched_op& op = row->ops[o];
+            const int nt = min(uniform_i(op.nterms), MF_SCHED_MAX_TERMS), dst = uniform_i(op.dst), s0 = uniform_i(op.src[0]);
+            f32x4_t v = R[0];
+            ((v = s0 == Rs ? R[Rs] : v), ...);
+            if (nt > 0) {
+                const float c0 = uniform_f(op.coef[0]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = c0 * v[j];
+                for (int k = 1; k < nt; ++k) {
+                    const float ck = uniform_f(op.coef[k]);
+                    const int sk = uniform_i(op.src[k]);
+                    f32x4_t x = R[0];
+                    ((x = sk == Rs ? R[Rs] : x), ...);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(ck, x[j], v[j]);
+                }
+            }
+            ((R[Rs] = dst == Rs ? v : R[Rs]), ...);
+        }
+        if (stm & 2u) lat[i] = R[1];
+        ((void)(Rs >= 2 && Rs - 2 < nslots && ((stm >> Rs) & 1u) && (state[(int64_t)(Rs - 2) * n4 + i] = R[Rs], true)), ...);
+    }
+}
+
+__global__ __launch_bounds__(256) void sched_step_kernel(const f32x4_t* __restrict__ eu, const f32x4_t* __restrict__ ec, float g,
+                                                         f32x4_t* __restrict__ lat, f32x4_t* __restrict__ state,
+                                                         const mf_sched_row* __restrict__ row, int64_t n4) {
+    sched_step_body(eu, ec, g, lat, state, row, n4, std::make_integer_sequence<int, kSchedRegs>{});
 }
 
 // Training loss (train_brushnet_mirror.py:1433-1449): per-sample mean((pred - target)^2) * weight, then the
@@ -391,6 +455,27 @@ extern "C" int mf_axpby_n(const float* const* xs, const float* coefs, int32_t ni
     for (int i = 0; i < nin; ++i) { a.x[i] = xs[i]; a.c[i] = coefs[i]; }
     hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a, y, n);
     MF_CHECK_LAUNCH("mf_axpby_n");
+    return MF_OK;
+}
+
+extern "C" int mf_sched_step_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row,
+                                 int64_t n, void* stream) {
+    MF_CHECK_ARG(eps_u && eps_c && latents && row && n > 0 && n % 4 == 0, "mf_sched_step_dev: bad arguments (n %% 4 == 0 needed)");
+    MF_CHECK_ARG(mf_aligned16(eps_u) && mf_aligned16(eps_c) && mf_aligned16(latents) && (!state || mf_aligned16(state)),
+                 "mf_sched_step_dev: tensors must be 16-byte aligned");
+    // the grid is sized to the device (a few blocks per CU, grid-stride loop), queried once per device
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+        mf_set_error("mf_sched_step_dev: no current device");
+        return MF_ELAUNCH;
+    }
+    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus[dev] = 0;
+    const int64_t n4 = n / 4;
+    const unsigned cap = (unsigned)(cus[dev] > 0 ? 4 * cus[dev] : 1024);
+    hipLaunchKernelGGL(sched_step_kernel, dim3(grid_for(n4, 256, (int)cap)), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
+                       (const f32x4_t*)eps_c, g, (f32x4_t*)latents, (f32x4_t*)state, row, n4);
+    MF_CHECK_LAUNCH("mf_sched_step_dev");
     return MF_OK;
 }
 

@@ -27,7 +27,7 @@ struct Buffer { int32_t kind; int64_t bytes; int64_t data_off; std::string name;
 
 enum Fn {
     F_GEMM_CONV, F_GROUPNORM, F_LAYERNORM, F_SOFTMAX_ROWS, F_ATTN_BF16, F_ATTN_F16, F_ATTN_F16X3, F_ATTN_F16X3_LSE, F_SPLIT_HALVES, F_QUANT_FP8,
-    F_PACK_NHWC, F_UNPACK_NCHW, F_ADD, F_CAST_BF16, F_GEGLU, F_TIMESTEP_EMB, F_SILU_F32, F_CFG_DDIM_DEV, F_CFG_COMBINE, F_VAE_SAMPLE,
+    F_PACK_NHWC, F_UNPACK_NCHW, F_ADD, F_CAST_BF16, F_GEGLU, F_TIMESTEP_EMB, F_SILU_F32, F_CFG_DDIM_DEV, F_CFG_COMBINE, F_SCHED_STEP_DEV, F_VAE_SAMPLE,
     F_NEAREST, F_TRANSPOSE, F_TRANSPOSE_BF16, F_TRANSPOSE_BF16_BF16, F_MEMCPY2D, F_MEMSET, F_COUNT
 };
 // name, argument kinds before the stream (p pointer, i int32, l int64, f float, d descriptor): program.SIGNATURES holds the same table
@@ -37,7 +37,8 @@ const struct { const char* name; const char* sig; } kFns[F_COUNT] = {
     {"mf_attention_f16x3_lse", "pplpplpplplpiiiiif"},
     {"mf_split_halves", "pppl"}, {"mf_quantize_rows_fp8", "pipplippf"}, {"mf_pack_nhwc", "pipipiiii"}, {"mf_unpack_nchw", "pilpiii"},
     {"mf_add", "pipipil"}, {"mf_cast_bf16", "ppl"}, {"mf_geglu", "pipili"}, {"mf_timestep_embedding", "ppiiif"}, {"mf_silu_f32", "ppl"},
-    {"mf_cfg_ddim_step_dev", "ppfpppifl"}, {"mf_cfg_combine", "ppfpl"}, {"mf_vae_sample", "pilppiiif"}, {"mf_nearest_resize", "ppiiiii"},
+    {"mf_cfg_ddim_step_dev", "ppfpppifl"}, {"mf_cfg_combine", "ppfpl"}, {"mf_sched_step_dev", "ppfpppl"},
+    {"mf_vae_sample", "pilppiiif"}, {"mf_nearest_resize", "ppiiiii"},
     {"mf_transpose", "ppiiillll"}, {"mf_transpose_bf16", "ppiiillll"}, {"mf_transpose_bf16_bf16", "ppiiillll"},
     {"mf_memcpy2d", "plplll"}, {"mf_memset", "pil"},
 };
@@ -301,6 +302,7 @@ int run_call(const mf_program* prog, const Call& c, void* s) {
     case F_SILU_F32: return mf_silu_f32(FP(0), (float*)P(1), L(2), s);
     case F_CFG_DDIM_DEV: return mf_cfg_ddim_step_dev(FP(0), FP(1), F(2), FP(3), (float*)P(4), FP(5), I(6), F(7), L(8), s);
     case F_CFG_COMBINE: return mf_cfg_combine(FP(0), FP(1), F(2), (float*)P(3), L(4), s);
+    case F_SCHED_STEP_DEV: return mf_sched_step_dev(FP(0), FP(1), F(2), (float*)P(3), (float*)P(4), (const mf_sched_row*)P(5), L(6), s);
     case F_VAE_SAMPLE: return mf_vae_sample(P(0), I(1), L(2), FP(3), (float*)P(4), I(5), I(6), I(7), F(8), s);
     case F_NEAREST: return mf_nearest_resize(FP(0), (float*)P(1), I(2), I(3), I(4), I(5), I(6), s);
     case F_TRANSPOSE: return mf_transpose(FP(0), (float*)P(1), I(2), I(3), I(4), L(5), L(6), L(7), L(8), s);

@@ -17,7 +17,7 @@ from . import _build
 MF_F32, MF_BF16, MF_F16X3, MF_BF16X3, MF_FP8, MF_BF16X1, MF_F16 = 0, 1, 2, 3, 4, 5, 6
 FP8 = torch.float8_e4m3fn          # OCP e4m3 (gfx950's fp8), 1 byte per element
 ACT_NONE, ACT_SILU, ACT_GEGLU4 = 0, 1, 2
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class MfhipError(RuntimeError):
@@ -126,6 +126,19 @@ class GroupNormDesc(C.Structure):
     ]
 
 
+SCHED_MAX_OPS, SCHED_MAX_TERMS, SCHED_MAX_REGS = 8, 6, 16       # include/mfhip.h MF_SCHED_MAX_*
+
+
+class SchedOp(C.Structure):
+    _fields_ = [("dst", C.c_int32), ("nterms", C.c_int32), ("src", C.c_int32 * SCHED_MAX_TERMS), ("coef", C.c_float * SCHED_MAX_TERMS)]
+
+
+class SchedRow(C.Structure):
+    """mf_sched_row: one denoise step of a multistep scheduler for mf_sched_step_dev (built by schedulers.device_plan)."""
+    _fields_ = [("nops", C.c_int32), ("nslots", C.c_int32), ("load", C.c_uint32), ("store", C.c_uint32),
+                ("ops", SchedOp * SCHED_MAX_OPS)]
+
+
 # every symbol include/mfhip.h declares (tests/test_abi.py checks the header against this list)
 EXPORTS = [
     "mf_abi_version", "mf_last_error", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc",
@@ -136,7 +149,7 @@ EXPORTS = [
     "mf_transpose_bf16_bf16", "mf_geglu_bwd_bf16", "mf_geglu_bwd_bf16_ws_floats", "mf_rowdot_heads_cast", "mf_debug_set_wgrad_dma", "mf_zero_ranges",
     "mf_split_halves", "mf_split_overflow", "mf_quantize_rows_fp8",
     "mf_pack_nhwc", "mf_unpack_nchw", "mf_add", "mf_cast_bf16", "mf_geglu", "mf_timestep_embedding", "mf_silu_f32",
-    "mf_cfg_ddim_step", "mf_cfg_ddim_step_dev", "mf_cfg_combine", "mf_axpby_n", "mf_mse_loss", "mf_vae_sample", "mf_nearest_resize",
+    "mf_cfg_ddim_step", "mf_cfg_ddim_step_dev", "mf_cfg_combine", "mf_axpby_n", "mf_sizeof_sched_row", "mf_sched_step_dev", "mf_mse_loss", "mf_vae_sample", "mf_nearest_resize",
     # image front-end (csrc/frontend.hip)
     "mf_minmax_ws_floats", "mf_minmax", "mf_image_normalize", "mf_mask_keep", "mf_concat_channels", "mf_postprocess",
     "mf_depth_normalize", "mf_select_ws_bytes", "mf_select_ranks", "mf_depth_percentile_normalize", "mf_bicubic_resize_crop",
@@ -190,6 +203,8 @@ def load() -> C.CDLL:
         raise MfhipError("mf_attn_bwd_desc layout mismatch between mfhip.h and the ctypes binding")
     if lib.mf_sizeof_wgrad_desc() != C.sizeof(WgradDesc) or lib.mf_sizeof_groupnorm_bwd_desc() != C.sizeof(GroupNormBwdDesc):
         raise MfhipError("training descriptor struct layout mismatch between mfhip.h and the ctypes binding")
+    if lib.mf_sizeof_sched_row() != C.sizeof(SchedRow):
+        raise MfhipError("mf_sched_row layout mismatch between mfhip.h and the ctypes binding")
     _lib = lib
     return lib
 
@@ -1082,6 +1097,23 @@ def axpby_n(xs, coefs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         out = torch.empty_like(xs[0])
     _check(load().mf_axpby_n(arr, cf, n, C.c_void_p(out.data_ptr()), C.c_int64(out.numel()), _stream()), "mf_axpby_n")
     return out
+
+
+def sched_step_dev(eps_u: torch.Tensor, eps_c: torch.Tensor, g: float, latents: torch.Tensor, state: Optional[torch.Tensor],
+                   row: torch.Tensor) -> torch.Tensor:
+    """One multistep-scheduler step on the device (mf_sched_step_dev): the guided noise prediction, then the ops of `row` (the
+    step's mf_sched_row in device memory, schedulers.device_plan) on `latents` (updated in place) and `state` ([nslots, *latents.shape]
+    fp32, the history kept between steps)."""
+    _req_cuda(eps_u, eps_c, latents, state, row)
+    n = latents.numel()
+    if eps_u.numel() != n or eps_c.numel() != n or (state is not None and state.numel() % n) or row.numel() * row.element_size() < C.sizeof(SchedRow):
+        raise MfhipError("sched_step_dev: mismatched sizes")
+    for t in (eps_u, eps_c, latents, state, row):
+        if t is not None and (not t.is_contiguous() or (t.dtype != torch.float32 and t is not row)):
+            raise MfhipError("sched_step_dev: contiguous fp32 tensors needed")
+    _check(load().mf_sched_step_dev(C.c_void_p(eps_u.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_float(g), C.c_void_p(latents.data_ptr()),
+                                    C.c_void_p(_ptr(state)), C.c_void_p(row.data_ptr()), C.c_int64(n), _stream()), "mf_sched_step_dev")
+    return latents
 
 
 def mse_loss(pred: torch.Tensor, target: torch.Tensor, weights: Optional[torch.Tensor] = None):

@@ -26,7 +26,7 @@ import torch
 from . import hip
 from .models import AutoencoderKL, BrushNetModel, UNet2DConditionModel
 from .rng import randn_tensor
-from .schedulers import DDIMScheduler
+from .schedulers import DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler, device_plan
 
 try:
     import PIL.Image
@@ -652,19 +652,29 @@ class StableDiffusionBrushNetPipeline:
                        cb_inputs, prompt_embeds, negative_prompt_embeds, bar, fused_ddim=True, eta=0.0, generator=None):
         """The hot loop as ONE captured hipGraph replayed per timestep (BrushNet + UNet + CFG [+ DDIM update], ~800
         kernels on two streams): launch overhead disappears and the host only refreshes two tiny device buffers
-        (timestep, scheduler coefficients) between replays.  DDIM's update is inside the graph; multistep schedulers
-        (PNDM, UniPC: host-side state and per-step scalar coefficients) get the guided noise prediction from the graph
-        and step eagerly (a handful of mf_axpby_n launches).  The first step runs eagerly: it autotunes GEMM tiles,
+        (timestep, scheduler coefficients) between replays.  DDIM's update is inside the graph; so is that of the multistep
+        schedulers (PNDM, UniPC): mf_sched_step_dev runs the step's row of schedulers.device_plan (a trace of their own step()) on
+        a state buffer that keeps their history, and the scheduler gets its end state from it after the loop.  With a
+        callback_on_step_end (it may read the scheduler between steps) or while an eps-form step program is exported, they get
+        the guided noise prediction from the graph and step eagerly (a handful of mf_axpby_n launches).  The first step runs eagerly: it autotunes GEMM tiles,
         binds the prompt (cross-attention K/V cache) and sizes every scratch buffer before anything is captured."""
         sched = self.scheduler
         dev = latents.device
         tvals = ts.to(torch.float32).to(dev)
+        plan = None
         if fused_ddim:
             coefs = torch.tensor([sched.step_coefficients(int(t))[:4] for t in ts], dtype=torch.float32).to(dev)
             clip = float(sched.config["clip_sample_range"]) if sched.config["clip_sample"] else 0.0
             ptype = 0 if sched.config["prediction_type"] == "epsilon" else 1
         else:
             coefs, clip, ptype = None, 0.0, type(sched).__name__
+            # PNDM / UniPC update on the device (mf_sched_step_dev, one row per step) unless a callback may read the scheduler between
+            # steps, or an eps-form step program is being exported
+            export_host = getattr(self, "_export_step_to", None) is not None and getattr(self, "_export_sched", "host") == "host"
+            if callback_on_step_end is None and not export_host and isinstance(sched, (PNDMScheduler, UniPCMultistepScheduler)):
+                plan = device_plan(sched, steps=len(ts))
+                coefs = plan.rows.to(dev)
+                ptype = (ptype, "device", plan.nslots)
         # The captured graph (and every buffer it reads) is kept across calls with the same shapes and scalars:
         # new inputs are copied INTO the static buffers, so repeated calls pay no capture / instantiate cost.  The key
         # carries each model's weights generation: load_state_dict / .to() rebuild every weight tensor (and the UNet's
@@ -680,7 +690,10 @@ class StableDiffusionBrushNetPipeline:
                       coef_cur=torch.empty(4, dtype=torch.float32, device=dev))
             if added:
                 st["added"] = {k: torch.empty(v.shape, dtype=torch.float32, device=dev) for k, v in added.items()}
-            if not fused_ddim:
+            if plan is not None:                                 # the step's mf_sched_row, and the scheduler's history (persists between steps)
+                st["row_cur"] = torch.empty(plan.rows.shape[1], dtype=torch.int32, device=dev)
+                st["state"] = torch.empty((max(plan.nslots, 1),) + tuple(latents.shape), dtype=torch.float32, device=dev)
+            elif not fused_ddim:
                 st["eps"] = torch.empty_like(latents)            # guided noise prediction handed to scheduler.step
             self._graph_state = st
         if added:
@@ -722,6 +735,8 @@ class StableDiffusionBrushNetPipeline:
                             return_dict=False, _temb=temb_u)[0]
             if fused_ddim:
                 hip.cfg_ddim_step_dev(eps[:nb], eps[nb:], float(guidance_scale), lat, coef_cur, ptype, clip, out=lat)
+            elif plan is not None:
+                hip.sched_step_dev(eps[:nb], eps[nb:], float(guidance_scale), lat, st["state"], st["row_cur"])
             else:
                 st["eps"].copy_(hip.cfg_combine(eps[:nb], eps[nb:], float(guidance_scale)))         # :1310-1312
 
@@ -736,6 +751,8 @@ class StableDiffusionBrushNetPipeline:
             t_cur.copy_(tvals[i:i + 1])
             if fused_ddim:
                 coef_cur.copy_(coefs[i])
+            elif plan is not None:
+                st["row_cur"].copy_(coefs[i])
             if temb_u is not None:
                 temb_u.copy_(st["temb_tab"][0][i])
                 temb_b.copy_(st["temb_tab"][1][i])
@@ -746,7 +763,7 @@ class StableDiffusionBrushNetPipeline:
                     torch.cuda.synchronize()
                     graph = torch.cuda.CUDAGraph()
                     # export_denoise_step(): the captured pass is ALSO written down as a step program (program.py)
-                    rec = self._export_recorder(st, lat, coef_cur, temb_u, temb_b, cond, coefs, fused_ddim) if export is not None else None
+                    rec = self._export_recorder(st, lat, coef_cur, temb_u, temb_b, cond, coefs, fused_ddim, plan) if export is not None else None
                     self._overlap(True)                      # the side stream forks from / joins the capture stream
                     try:
                         # (thread_local: with an initialised process group its watchdog thread may poll events while this thread captures)
@@ -766,7 +783,7 @@ class StableDiffusionBrushNetPipeline:
                     if rec is not None:                      # (so the buffers still hold what they held BEFORE the recorded step)
                         self._export_save(rec, graph, export, lat, temb_u, temb_b, len(ts), i, guidance_scale, cond_scale)
                 st["graph"].replay()
-            if not fused_ddim:
+            if not fused_ddim and plan is None:
                 # multistep schedulers keep references to their inputs (ets, last_sample): hand them copies, not the
                 # graph's static buffers
                 lat.copy_(self._sched_step(st["eps"].clone(), ts[i], lat.clone(), eta, generator))   # :1315
@@ -777,9 +794,11 @@ class StableDiffusionBrushNetPipeline:
                 if new is not None and new is not lat:
                     lat.copy_(new)
             bar.update()
+        if plan is not None:
+            plan.finish(sched, st["state"])                  # the counters and history the host's step() would have left
         return lat.clone()
 
-    def _export_recorder(self, st, lat, coef_cur, temb_u, temb_b, cond, coefs, fused_ddim):
+    def _export_recorder(self, st, lat, coef_cur, temb_u, temb_b, cond, coefs, fused_ddim, plan=None):
         """The recorder of ONE denoise step (the loop body of pipeline_brushnet.py:1250-1332), entered inside the hipGraph capture
         of that step: the program carries the capture's forks and joins (BrushNet || UNet), replayed by mf_denoise_step_fused."""
         from . import program
@@ -790,6 +809,12 @@ class StableDiffusionBrushNetPipeline:
         if fused_ddim:
             named["coef4"] = coef_cur
             tables["table.coef4"] = coefs.contiguous()
+        elif plan is not None:
+            # export_denoise_step(scheduler="device"): the PNDM / UniPC update is inside (mf_sched_step_dev); the host copies the step's
+            # row in like coef4, and the history slots stay in "sched_state" between runs
+            named["sched_row"] = st["row_cur"]
+            named["sched_state"] = st["state"]
+            tables["table.sched_row"] = coefs.contiguous()
         else:
             # multistep schedulers (PNDM, UniPC: host-side state between steps, scheduling_pndm.py:321-390): the program ends with the
             # guided noise prediction in the io buffer "eps"; the update of the latents is the host's (mf_axpby_n)
@@ -800,25 +825,34 @@ class StableDiffusionBrushNetPipeline:
         import json
         rec.finish(graph.pool())
         meta = dict(entry="mf_denoise_step_fused", reference="pipelines/brushnet/pipeline_brushnet.py:1250-1332", precision=self.unet.prec.name,
-                    result="latents (DDIM update inside)" if "coef4" in rec.named else "eps (guided noise prediction; the scheduler update is the host's)",
+                    result="latents (DDIM update inside)" if "coef4" in rec.named else
+                    f"latents ({type(self.scheduler).__name__} update inside: mf_sched_step_dev; history in sched_state)" if "sched_row" in rec.named else
+                    "eps (guided noise prediction; the scheduler update is the host's)",
                     latents=list(lat.shape), steps=nsteps, recorded_step=step, guidance_scale=float(guidance_scale),
                     conditioning_scale=cond_scale if isinstance(cond_scale, (int, float)) else list(cond_scale),
                     temb_unet=list(temb_u.shape), temb_brushnet=list(temb_b.shape), brushnet_once=bool(self._brushnet_once))
         self._export_info = rec.save(path, meta=json.dumps(meta))
         self._export_info["meta"] = meta
 
-    def export_denoise_step(self, path: str, **call_kwargs) -> dict:
+    def export_denoise_step(self, path: str, scheduler: str = "host", **call_kwargs) -> dict:
         """Run the pipeline once and write the denoise step's program to `path` (see program.py / include/mfhip.h "step programs").
         `call_kwargs`: what __call__ takes; the program is specialised on their shapes, the prompt (its cross-attention K / V^T are
-        constants of the file), the guidance and conditioning scales, and the schedule (its tables travel as named constants)."""
+        constants of the file), the guidance and conditioning scales, and the schedule (its tables travel as named constants).
+        `scheduler` (PNDM, UniPC): "host" ends the step with the guided noise prediction in the io buffer "eps" for the host's own
+        scheduler; "device" records the update too (mf_sched_step_dev: io buffers "sched_row" / "sched_state", table "table.sched_row"),
+        so that mf_denoise_step_fused alone runs a whole step.  DDIM's update is inside either way."""
         if self.device.type != "cuda":
             raise hip.MfhipError("export_denoise_step needs the device: a program is a recording of real launches")
-        self._export_step_to, self._export_info = path, None
+        if scheduler not in ("host", "device"):
+            raise ValueError(f"export_denoise_step: scheduler must be 'host' or 'device', not {scheduler!r}")
+        if scheduler == "device" and not isinstance(self.scheduler, (DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler)):
+            raise NotImplementedError(f"{type(self.scheduler).__name__} has no device update")
+        self._export_step_to, self._export_sched, self._export_info = path, scheduler, None
         try:
             call_kwargs.setdefault("output_type", "latent")
             out = self(**call_kwargs)
         finally:
-            self._export_step_to = None
+            self._export_step_to, self._export_sched = None, "host"
         if self._export_info is None:
             raise hip.MfhipError("export_denoise_step: the call did not reach a second denoise step on the graph path (num_inference_steps >= 2, "
                                  "use_graph left on)")

@@ -42,14 +42,14 @@ SIGNATURES = {
     "mf_pack_nhwc": "pipipiiii", "mf_unpack_nchw": "pilpiii",
     "mf_add": "pipipil", "mf_cast_bf16": "ppl", "mf_geglu": "pipili",
     "mf_timestep_embedding": "ppiiif", "mf_silu_f32": "ppl",
-    "mf_cfg_ddim_step_dev": "ppfpppifl", "mf_cfg_combine": "ppfpl",
+    "mf_cfg_ddim_step_dev": "ppfpppifl", "mf_cfg_combine": "ppfpl", "mf_sched_step_dev": "ppfpppl",
     "mf_vae_sample": "pilppiiif", "mf_nearest_resize": "ppiiiii",
     "mf_transpose": "ppiiillll", "mf_transpose_bf16": "ppiiillll", "mf_transpose_bf16_bf16": "ppiiillll",
     "mf_memcpy2d": "plplll", "mf_memset": "pil",
 }
 # queries / developer switches: forwarded, never recorded
 _PASS_THROUGH = ("mf_last_error", "mf_abi_version", "mf_gemm_num_tiles", "mf_gemm_tile_shape", "mf_gemm_tile_table_version",
-                 "mf_groupnorm_ws_floats", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc")
+                 "mf_groupnorm_ws_floats", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc", "mf_sizeof_sched_row")
 # descriptor fields that are HOST out-pointers (the library reports a choice through them): null in a program
 _HOST_FIELDS = {"gn_part_rows", "gn_grouped", "deferred_splits"}
 

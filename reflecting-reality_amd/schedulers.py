@@ -4,10 +4,13 @@ Reference: MirrorFusion/src/diffusers/schedulers/scheduling_ddim.py (set_timeste
 add_noise :473-497) and scheduling_pndm.py (set_timesteps :168-226, step_prk :261-319, step_plms :321-390,
 _get_prev_sample :407-448).  The scalar coefficients are computed on the host exactly like the reference
 does (fp32 0-dim tensor arithmetic on the alphas_cumprod table); the per-element update is one HIP kernel
-(mf_cfg_ddim_step / mf_axpby_n).  Latents stay fp32 whatever the model precision.
+(mf_cfg_ddim_step / mf_axpby_n).  Latents stay fp32 whatever the model precision.  device_plan (end of the file) turns a PNDM /
+UniPC schedule into rows for mf_sched_step_dev, the whole update of a step in one launch with device-resident coefficients.
 """
 from __future__ import annotations
 
+import copy
+import ctypes as C
 from dataclasses import dataclass
 from typing import List, Optional, Tuple, Union
 
@@ -502,3 +505,192 @@ class UniPCMultistepScheduler(_SchedulerBase):
 
     def add_noise(self, original_samples, noise, timesteps):
         raise NotImplementedError("UniPC.add_noise is only used by the training script (SURVEY.md §8 f-2)")
+
+
+# ---- the multistep schedulers' update on the device (mf_sched_step_dev) ------------------------------------------------------------
+# A step of PNDM / UniPC is a short list of mf_axpby_n calls over the guided noise prediction, the latents and the history the
+# scheduler keeps.  device_plan() runs the scheduler's OWN step() on stand-in tensors that record those calls (terms, order, float
+# coefficients) and maps every value onto the per-element register file of mf_sched_step_dev (include/mfhip.h): 0 = e, 1 = latents,
+# 2 .. 2+S-1 = state slots persisted between steps, then temporaries.  The coefficient math stays in step(); the rows only carry it.
+REG_EPS, REG_LATENTS = 0, 1
+_MAX_OPS, _MAX_TERMS, _MAX_REGS, _Row = hip.SCHED_MAX_OPS, hip.SCHED_MAX_TERMS, hip.SCHED_MAX_REGS, hip.SchedRow
+
+
+class _Sym:
+    """A tensor of a traced step(): which register holds it is decided by the plan."""
+    __slots__ = ("name", "slot")
+
+    def __init__(self, name: str):
+        self.name, self.slot = name, None
+
+    def float(self):
+        return self
+
+    def contiguous(self):
+        return self
+
+    def __repr__(self):
+        return self.name
+
+
+class _TraceHip:
+    """Stands in for the hip module while step() is traced: every axpby_n call is written down, nothing is launched."""
+
+    def __init__(self):
+        self.calls = []
+
+    def axpby_n(self, xs, coefs, out=None):
+        if out is not None or not 1 <= len(xs) <= _MAX_TERMS or not all(isinstance(x, _Sym) for x in xs):
+            raise NotImplementedError("a traced step may only combine its own values, at most MF_SCHED_MAX_TERMS at a time")
+        y = _Sym(f"v{len(self.calls)}")
+        self.calls.append((y, list(xs), [float(c) for c in coefs]))
+        return y
+
+    def __getattr__(self, name):
+        raise NotImplementedError(f"hip.{name} inside a traced scheduler step: only axpby_n has a device form")
+
+
+def _held(sched) -> List[_Sym]:
+    """The traced values the scheduler's attributes keep (its history), in attribute order."""
+    out = {}
+    for v in vars(sched).values():
+        for x in (v if isinstance(v, (list, tuple)) else (v,)):
+            if isinstance(x, _Sym):
+                out.setdefault(id(x), x)
+    return list(out.values())
+
+
+def _plan_step(calls, e: _Sym, x: _Sym, prev: _Sym, held: List[_Sym], slots: list):
+    """Registers for one traced step.  `slots`: the value each state slot holds (carried from step to step, updated here).  Returns
+    ops as (dst, [src], coefs | None for a move) with locations ("r", 0 | 1), ("s", slot), ("t", temporary), and the temporaries used."""
+    keep = {id(s) for s in held}
+    loc = {id(e): ("r", REG_EPS), id(x): ("r", REG_LATENTS)}
+    for i, s in enumerate(slots):
+        if s is not None:
+            loc[id(s)] = ("s", i)
+    reads = {}
+    for _, xs, _ in calls:
+        for i in {id(v) for v in xs}:
+            reads[i] = reads.get(i, 0) + 1
+    temps, ops = [], []
+
+    def free(v):
+        return v is None or (id(v) not in keep and reads.get(id(v), 0) == 0)
+
+    def take(pool, v):
+        for i, occ in enumerate(pool):
+            if free(occ):
+                pool[i] = v
+                return i
+        pool.append(v)
+        return len(pool) - 1
+    # inputs the history keeps (PNDM: ets.append(model_output), cur_sample = sample; UniPC: last_sample = sample): copied into a slot
+    # first, before anything can overwrite register 1; later reads take the copy
+    for v in (e, x):
+        if id(v) in keep:
+            s = take(slots, v)
+            ops.append((("s", s), [loc[id(v)]], None))
+            loc[id(v)], v.slot = ("s", s), s
+    for y, xs, cs in calls:
+        srcs = [loc[id(v)] for v in xs]          # (a KeyError here: a value no register holds any more)
+        for i in {id(v) for v in xs}:
+            reads[i] -= 1
+        if id(y) in keep:
+            s = take(slots, y)
+            d, y.slot = ("s", s), s
+        elif y is prev and (reads.get(id(x), 0) == 0 or loc[id(x)] != ("r", REG_LATENTS)):
+            d = ("r", REG_LATENTS)
+        else:
+            d = ("t", take(temps, y))
+        ops.append((d, srcs, cs))
+        loc[id(y)] = d
+    if loc[id(prev)] != ("r", REG_LATENTS):
+        ops.append((("r", REG_LATENTS), [loc[id(prev)]], None))
+    for v in held:
+        if loc[id(v)][0] != "s":
+            raise AssertionError(f"{v} is kept by the scheduler but holds no state slot")
+    return ops, len(temps)
+
+
+class SchedPlan:
+    """device_plan()'s result: `rows` (int32 [steps, sizeof(mf_sched_row) / 4], one mf_sched_row per step, host memory), `nslots` (S: the
+    state buffer is [S, *latents.shape] fp32) and the traced scheduler, whose end state finish() hands to the real one."""
+
+    def __init__(self, rows: torch.Tensor, nslots: int, traced, steps: int):
+        self.rows, self.nslots, self._traced, self.steps = rows, nslots, traced, steps
+
+    def finish(self, sched, state: torch.Tensor) -> None:
+        """After the last device step: `sched` ends in the state its own step() would have left — the counters of the trace, and the
+        history tensors taken from the slots of `state` (copies)."""
+        def real(v):
+            return state[v.slot].clone() if isinstance(v, _Sym) else v
+        for k, v in vars(self._traced).items():
+            if isinstance(v, list):
+                v = [real(x) for x in v]
+            elif isinstance(v, tuple):
+                v = tuple(real(x) for x in v)
+            else:
+                v = real(v)
+            setattr(sched, k, v)
+
+
+def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
+    """The rows of mf_sched_step_dev for the first `steps` (default: all) entries of `sched.timesteps`, for a PNDMScheduler or
+    UniPCMultistepScheduler right after set_timesteps.  `sched` itself is not changed (a copy is traced)."""
+    global hip
+    if not isinstance(sched, (PNDMScheduler, UniPCMultistepScheduler)):
+        raise NotImplementedError(f"{type(sched).__name__} has no device plan (DDIM updates through mf_cfg_ddim_step_dev)")
+    if sched.num_inference_steps is None:
+        raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+    history = [getattr(sched, k, None) for k in ("model_outputs", "last_sample", "ets", "cur_sample", "cur_model_output")]
+    if getattr(sched, "_step_index", None) is not None or getattr(sched, "counter", 0) != 0 or any(
+            x is not None for v in history for x in (v if isinstance(v, list) else [v])):
+        raise ValueError("device_plan: the scheduler has already stepped; call set_timesteps first")
+    traced = copy.copy(sched)
+    for k, v in list(vars(traced).items()):
+        if isinstance(v, list):
+            setattr(traced, k, list(v))
+    ts = sched.timesteps
+    steps = len(ts) if steps is None else int(steps)
+    slots, per_step, ntemps = [], [], 0
+    real, tracer = hip, _TraceHip()
+    for k in range(steps):
+        e, x = _Sym(f"e{k}"), _Sym(f"x{k}")
+        tracer.calls = []
+        hip = tracer
+        try:
+            prev = traced.step(e, ts[k], x, return_dict=False)[0]
+        finally:
+            hip = real
+        ops, nt = _plan_step(tracer.calls, e, x, prev, _held(traced), slots)
+        per_step.append(ops)
+        ntemps = max(ntemps, nt)
+    nslots = len(slots)
+    if 2 + nslots + ntemps > _MAX_REGS:
+        raise NotImplementedError(f"device_plan: {nslots} state slots + {ntemps} temporaries exceed MF_SCHED_MAX_REGS")
+    base = {"r": 0, "s": 2, "t": 2 + nslots}
+    rows = []
+    for ops in per_step:
+        if len(ops) > _MAX_OPS:
+            raise NotImplementedError(f"device_plan: {len(ops)} ops in one step exceed MF_SCHED_MAX_OPS")
+        row = _Row(nops=len(ops), nslots=nslots)
+        written, load, store = set(), 0, 0
+        for j, (d, srcs, cs) in enumerate(ops):
+            op = row.ops[j]
+            for i, (kind, n) in enumerate(srcs):
+                r = base[kind] + n
+                op.src[i] = r
+                if r not in written and kind != "t" and r != REG_EPS:
+                    load |= 1 << r
+            op.nterms = 0 if cs is None else len(cs)
+            for i, c in enumerate(cs or ()):
+                op.coef[i] = c
+            op.dst = base[d[0]] + d[1]
+            written.add(op.dst)
+            if d[0] != "t":
+                store |= 1 << op.dst
+        row.load, row.store = load, store
+        rows.append(bytes(row))
+    table = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.int32).view(steps, -1).clone() if rows else \
+        torch.zeros(0, C.sizeof(_Row) // 4, dtype=torch.int32)
+    return SchedPlan(table, nslots, traced, steps)

@@ -59,7 +59,7 @@ extern "C" {
 #define MF_ACT_GEGLU4 2
 
 /* ABI version, bumped on any struct change; checked by the Python host at load time. */
-#define MF_ABI_VERSION 21
+#define MF_ABI_VERSION 22
 int mf_abi_version(void);
 const char* mf_last_error(void);
 /* sizeof() of the descriptor structs, so a foreign-language binding can verify its layout */
@@ -243,6 +243,11 @@ int mf_layernorm(const void* x, int32_t in_dtype, void* out, int32_t out_dtype, 
 int mf_softmax_rows(const float* scores, void* out, int32_t out_dtype, int64_t rows, int32_t cols,
                     int32_t ld, void* stream);
 
+/* mf_softmax_rows under a causal mask (the fp32 mode of the CLIP text encoders, modeling_clip's causal_attention_mask): the rows are
+ * [batch * heads][sq] queries, row r keeps columns 0 .. r % sq and everything past them is written as 0.  sq == cols. */
+int mf_softmax_rows_causal(const float* scores, void* out, int32_t out_dtype, int64_t rows, int32_t cols,
+                           int32_t ld, int32_t sq, void* stream);
+
 /* Fused flash-style attention (bf16): out[b][s][h*d + :] = softmax(q k^T * scale) v.
  * q: [B][Sq][ldq], k: [B][Skv][ldk], vt: V^T as [B][heads*d][ldvt] (keys contiguous),
  * replaces F.scaled_dot_product_attention (attention_processor.py:1266-1268). */
@@ -262,6 +267,18 @@ int mf_attention_f16(const void* q, int64_t ldq, const void* k, int64_t ldk, con
 int mf_attention_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
                        const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, int32_t batch,
                        int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream);
+/* The three flavours above under a causal mask (query i attends keys 0 .. i): the self-attention of the CLIP text encoders
+ * (transformers modeling_clip.py CLIPAttention with causal_attention_mask; pipeline_brushnet.py:335-370 encode_prompt).  Same
+ * arguments as their twins; sq == skv (else MF_EINVAL); head_dim 8 / 64.  Key tiles above a block's last query are skipped. */
+int mf_attention_causal_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
+                             void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
+                             int32_t head_dim, float scale, void* stream);
+int mf_attention_causal_f16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
+                            void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
+                            int32_t head_dim, float scale, void* stream);
+int mf_attention_causal_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                              const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, int32_t batch,
+                              int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream);
 /* The same with the row statistics the backward pass needs: lse[b][head][i] = log2 of row i's softmax denominator in the exp2
  * domain (max + log2 sum, with scale * log2 e folded in), fp32 [B][heads][Sq]; lse may be NULL. */
 int mf_attention_f16x3_lse(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
@@ -351,6 +368,18 @@ int mf_timestep_embedding(const float* t, float* out, int32_t n, int32_t dim, in
                           float freq_shift, void* stream);
 /* SiLU on fp32 vector (resnet.py:372 nonlinearity(temb)) */
 int mf_silu_f32(const float* x, float* out, int64_t n, void* stream);
+
+/* CLIP text encoder (transformers modeling_clip.py CLIPTextEmbeddings / CLIPMLP).
+ * mf_embed_tokens: out[b][s][:] = token_table[ids[b][s]][:] + pos_table[s][:], summed in fp32 and rounded once.  ids: int32 in device
+ * memory; the tables are [vocab][hidden] and [>= seq][hidden] in table_dtype (fp32, bf16 or fp16), out in out_dtype; hidden % 8 == 0,
+ * 16-byte accesses.  An id outside [0, vocab) is clamped to the range: the launch never reads out of bounds.
+ * mf_act: elementwise activation over n values (n % 8 == 0), in place when out == x: MF_ACT_QUICK_GELU x * sigmoid(1.702 x),
+ * MF_ACT_GELU_ERF the exact erf GELU. */
+#define MF_ACT_QUICK_GELU 3   /* mf_act only: mf_gemm_conv has no such epilogue */
+#define MF_ACT_GELU_ERF 4
+int mf_embed_tokens(const int32_t* ids, const void* token_table, const void* pos_table, int32_t table_dtype, void* out,
+                    int32_t out_dtype, int32_t batch, int32_t seq, int32_t hidden, int32_t vocab, void* stream);
+int mf_act(const void* x, void* out, int32_t dtype, int32_t kind, int64_t n, void* stream);
 
 /* Fused classifier-free guidance + DDIM step (pipeline_brushnet.py:1310-1315,
  * scheduling_ddim.py:404-450, eta = 0):

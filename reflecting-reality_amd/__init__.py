@@ -12,6 +12,7 @@ Sub-modules:
   distributed  batch sharding for inference, bucketed gradient all-reduce (RCCL) for training
   inference  run_sharded: the examples/brushnet/test_brushnet.py harness (sample list split over ranks, N seeds each)
   pipeline   StableDiffusionBrushNetPipeline, StableDiffusionXLBrushNetPipeline
+  text_encoder  CLIPTextModel, CLIPTextModelWithProjection (the prompt encoders of both pipelines)
 """
 __version__ = "0.1.0"
 
@@ -21,7 +22,7 @@ _LAZY = {
     "MirrorFusionModel": "training", "compute_snr": "training", "training_loss": "training", "train_step": "training",
     "AdamW": "training", "save_state": "training", "load_state": "training", "run_sharded": "inference",
     "MfhipAttnProcessor": "attn_processor", "StableDiffusionBrushNetPipeline": "pipeline", "StableDiffusionXLBrushNetPipeline": "pipeline", "StableDiffusionPipelineOutput": "pipeline",
-    "VaeImageProcessor": "pipeline", "Precision": "ops",
+    "VaeImageProcessor": "pipeline", "Precision": "ops", "CLIPTextModel": "text_encoder", "CLIPTextModelWithProjection": "text_encoder",
 }
 
 

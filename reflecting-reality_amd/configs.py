@@ -50,3 +50,23 @@ def brushnet_config(unet_cfg: dict, conditioning_channels: int = 6) -> dict:
     cfg.update(conditioning_channels=conditioning_channels, down_block_types=("DownBlock2D",) * n,
                up_block_types=("UpBlock2D",) * n, mid_block_type="MidBlock2D")
     return cfg
+
+
+# CLIP text encoders (transformers CLIPTextConfig fields; text_encoder.py).  CLIP_L_TEXT: openai/clip-vit-large-patch14 as shipped in
+# SD1.5 / SDXL `text_encoder/config.json` (legacy eos_token_id 2: the pooled row is argmax(input_ids)); OPENCLIP_BIGG_TEXT: SDXL's
+# `text_encoder_2` (OpenCLIP ViT-bigG/14, 32 layers, with text projection; padded with 0).  The tiny pair has the same two styles.
+# tools/make_golden_clip.py, tools/bench_text_encoder.py and the tests all read these: one source.
+CLIP_L_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
+                   max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5, projection_dim=768, eos_token_id=2)
+OPENCLIP_BIGG_TEXT = dict(vocab_size=49408, hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=20,
+                          max_position_embeddings=77, hidden_act="gelu", layer_norm_eps=1e-5, projection_dim=1280, eos_token_id=49407)
+TINY_CLIP_L_TEXT = dict(vocab_size=1000, hidden_size=32, intermediate_size=128, num_hidden_layers=2, num_attention_heads=4,
+                        max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5, projection_dim=16, eos_token_id=2)
+TINY_CLIP_G_TEXT = dict(vocab_size=1000, hidden_size=32, intermediate_size=128, num_hidden_layers=3, num_attention_heads=4,
+                        max_position_embeddings=77, hidden_act="gelu", layer_norm_eps=1e-5, projection_dim=16, eos_token_id=999)
+# fixture name (tests/golden/clip_<name>.npz) -> (config, has a text projection).  bigg4: bigG at full width, cut to 4 layers so that
+# the float64 run and the fixture stay small.
+CLIP_FIXTURES = {
+    "tiny_l": (TINY_CLIP_L_TEXT, False), "tiny_g": (TINY_CLIP_G_TEXT, True), "clip_l": (CLIP_L_TEXT, False),
+    "bigg4": (dict(OPENCLIP_BIGG_TEXT, num_hidden_layers=4), True),
+}

@@ -47,7 +47,10 @@ __device__ __forceinline__ f32x16_t mfma16(const uint4& a, const uint4& b, const
 
 // F16 (!SP): fp16 operands and output (MF_F16 storage) on the f16 MFMA forms — the byte layout of every tile equals the bf16 one; the
 // packs / unpacks (Q~ scaling, P, the three pieces of the exponent offset, the ones) use fp16 instead of bf16.
-template <int HD, bool DB, bool SP = false, bool F16 = false>
+// CAUSAL (the CLIP text encoders' self-attention, sq == skv): key > query is masked to -inf next to the tail mask, and a block stops
+// after the key tile that holds its last query.  Tiles are walked in ascending order and key 0 is visible to every query, so the
+// running max is finite after the first tile and a wholly masked later tile gives exp2(-inf - m) = 0, never (-inf) - (-inf).
+template <int HD, bool DB, bool SP = false, bool F16 = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2)) void attn_fwd_kernel(const AttnArgs p) {
     static_assert(!(SP && F16), "F16 is the single-plane form");
     constexpr unsigned ONE2 = F16 ? 0x3C003C00u : 0x3F803F80u;   // (1.0, 1.0)
@@ -204,7 +207,11 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
     const unsigned ones_x = (MJ && h) ? ONE2 : 0u, ones_y = (MJ && h) ? (ONE2 & 0xffffu) : 0u;
     (void)ones_x; (void)ones_y;
 
-    const int ntiles = (p.skv + 63) / 64;
+    int ntiles = (p.skv + 63) / 64;
+    if constexpr (CAUSAL) {        // block-uniform: the barriers below stay matched
+        const int qlast = bx * 128 + 127 < p.sq ? bx * 128 + 127 : p.sq - 1;
+        if (qlast / 64 + 1 < ntiles) ntiles = qlast / 64 + 1;
+    }
     __syncthreads();   // zero-fill (and the ones rows) done
     issue_tile(0);
     wait_vmcnt<0>();
@@ -246,6 +253,17 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
                     const int key = kv0 + 32 * tt + (e & 3) + 4 * (e >> 2 & 1) + 16 * (e >> 3) + 8 * h;   // row with bits 2, 3 swapped
                     if (key >= p.skv) st[tt][e] = -INFINITY;
                 }
+        }
+        if constexpr (CAUSAL) {
+            if (kv0 + 63 > q0) {          // wave-uniform: the tile reaches past this wave's first query
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int key = kv0 + 32 * tt + (e & 3) + 4 * (e >> 2 & 1) + 16 * (e >> 3) + 8 * h;
+                        if (key > qi) st[tt][e] = -INFINITY;
+                    }
+            }
         }
         // ---- online softmax (per query = per lane; the two lane halves hold disjoint keys) ----
         float mx = -INFINITY;
@@ -820,10 +838,10 @@ __global__ __launch_bounds__(256) void rowdot_heads_kernel(const float* a, const
     }
 }
 
-template <int HD, bool SP = false, bool F16 = false>
+template <int HD, bool SP = false, bool F16 = false, bool CAUSAL = false>
 void launch_attn(const AttnArgs& a, int batch, hipStream_t s) {
     dim3 grid((unsigned)(((a.sq + 127) / 128) * a.heads * batch));
-    hipLaunchKernelGGL((attn_fwd_kernel<HD, true, SP, F16>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, true, SP, F16, CAUSAL>), grid, dim3(256), 0, s, a);
 }
 
 // fp32 [rows][ld] (first `cols` columns) -> two fp16 planes of the same layout: hi toward zero, lo = x - hi
@@ -860,7 +878,7 @@ extern "C" int mf_attention_bf16(const void* q, int64_t ldq, const void* k, int6
 
 static int attention_16(bool f16, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                         void* out, int64_t ldo, float* lse, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
-                        int32_t head_dim, float scale, void* stream);
+                        int32_t head_dim, float scale, void* stream, bool causal = false);
 
 extern "C" int mf_attention_bf16_lse(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                                      void* out, int64_t ldo, float* lse, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
@@ -874,11 +892,24 @@ extern "C" int mf_attention_f16(const void* q, int64_t ldq, const void* k, int64
     return attention_16(true, q, ldq, k, ldk, vt, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale, stream);
 }
 
+extern "C" int mf_attention_causal_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
+                                        void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
+                                        int32_t head_dim, float scale, void* stream) {
+    return attention_16(false, q, ldq, k, ldk, vt, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale, stream, true);
+}
+
+extern "C" int mf_attention_causal_f16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
+                                       void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
+                                       int32_t head_dim, float scale, void* stream) {
+    return attention_16(true, q, ldq, k, ldk, vt, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale, stream, true);
+}
+
 static int attention_16(bool f16, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                         void* out, int64_t ldo, float* lse, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
-                        int32_t head_dim, float scale, void* stream) {
+                        int32_t head_dim, float scale, void* stream, bool causal) {
     MF_CHECK_ARG(q && k && vt && out, "mf_attention_bf16: null pointer");
     MF_CHECK_ARG(batch >= 1 && heads >= 1 && sq >= 1 && skv >= 1, "mf_attention_bf16: bad sizes");
+    MF_CHECK_ARG(!causal || sq == skv, "mf_attention_causal: the causal mask needs sq == skv (got %d, %d)", sq, skv);
     MF_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 8 == 0 && ldvt >= skv,
                  "mf_attention_bf16: leading dims must be multiples of 8 and ldvt >= skv");
     if (!mf_aligned16(q) || !mf_aligned16(k) || !mf_aligned16(vt) || !mf_aligned16(out)) {
@@ -892,6 +923,19 @@ static int attention_16(bool f16, const void* q, int64_t ldq, const void* k, int
     a.c = scale * 1.44269504088896340736f;
     { static const bool off = getenv("MFHIP_ATTN_NOXCD") != nullptr; a.no_xcd_order = off; }
     hipStream_t s = (hipStream_t)stream;
+    if (causal) {
+        switch (f16 ? -head_dim : head_dim) {
+            case 8: launch_attn<8, false, false, true>(a, batch, s); break;
+            case 64: launch_attn<64, false, false, true>(a, batch, s); break;
+            case -8: launch_attn<8, false, true, true>(a, batch, s); break;
+            case -64: launch_attn<64, false, true, true>(a, batch, s); break;
+            default:
+                mf_set_error("mf_attention_causal: unsupported head_dim %d (have 8, 64)", head_dim);
+                return MF_EINVAL;
+        }
+        MF_CHECK_LAUNCH("mf_attention_causal");
+        return MF_OK;
+    }
     switch (f16 ? -head_dim : head_dim) {
         case 8: launch_attn<8>(a, batch, s); break;
         case 40: launch_attn<40>(a, batch, s); break;
@@ -937,11 +981,28 @@ extern "C" int mf_attention_f16x3(const void* q_hi, const void* q_lo, int64_t ld
                                   stream);
 }
 
+static int attention_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                           const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, float* lse, int32_t batch,
+                           int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream, bool causal);
+
 extern "C" int mf_attention_f16x3_lse(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
                                       const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, float* lse, int32_t batch,
                                       int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream) {
+    return attention_f16x3(q_hi, q_lo, ldq, k_hi, k_lo, ldk, vt_hi, vt_lo, ldvt, out, ldo, lse, batch, heads, sq, skv, head_dim, scale, stream, false);
+}
+
+extern "C" int mf_attention_causal_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                                         const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, int32_t batch,
+                                         int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream) {
+    return attention_f16x3(q_hi, q_lo, ldq, k_hi, k_lo, ldk, vt_hi, vt_lo, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale, stream, true);
+}
+
+static int attention_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                           const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, float* lse, int32_t batch,
+                           int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream, bool causal) {
     MF_CHECK_ARG(q_hi && q_lo && k_hi && k_lo && vt_hi && vt_lo && out, "mf_attention_f16x3: null pointer");
     MF_CHECK_ARG(batch >= 1 && heads >= 1 && sq >= 1 && skv >= 1, "mf_attention_f16x3: bad sizes");
+    MF_CHECK_ARG(!causal || sq == skv, "mf_attention_causal: the causal mask needs sq == skv (got %d, %d)", sq, skv);
     MF_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= skv,
                  "mf_attention_f16x3: leading dims must be multiples of 8 (ldo: 4) and ldvt >= skv");
     if (!mf_aligned16(q_hi) || !mf_aligned16(q_lo) || !mf_aligned16(k_hi) || !mf_aligned16(k_lo) || !mf_aligned16(vt_hi) ||
@@ -957,6 +1018,17 @@ extern "C" int mf_attention_f16x3_lse(const void* q_hi, const void* q_lo, int64_
     a.lse = lse;
     a.c = scale * 1.44269504088896340736f;
     hipStream_t s = (hipStream_t)stream;
+    if (causal) {
+        switch (head_dim) {
+            case 8: launch_attn<8, true, false, true>(a, batch, s); break;
+            case 64: launch_attn<64, true, false, true>(a, batch, s); break;
+            default:
+                mf_set_error("mf_attention_causal: unsupported head_dim %d (have 8, 64)", head_dim);
+                return MF_EINVAL;
+        }
+        MF_CHECK_LAUNCH("mf_attention_causal");
+        return MF_OK;
+    }
     switch (head_dim) {
         case 8: launch_attn<8, true>(a, batch, s); break;
         case 40: launch_attn<40, true>(a, batch, s); break;

@@ -147,6 +147,57 @@ __global__ void timestep_embedding_kernel(const float* t, float* out, int n, int
     }
 }
 
+// ---- CLIP text encoder: token + position embedding gather, and the MLP activations -------------------------------------------
+// 8 consecutive elements of a row as fp32: two 16-byte loads of an fp32 tensor, one of a 16-bit tensor
+__device__ __forceinline__ void load8_as_f32(const char* p, int dt, int64_t i, float* v) {
+    if (dt == MF_F32) {
+        const float4 a = *reinterpret_cast<const float4*>(p + i * 4), b = *reinterpret_cast<const float4*>(p + i * 4 + 16);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+        const uint4 u = *reinterpret_cast<const uint4*>(p + i * 2);
+        if (dt == MF_F16) unpack_h8<true>(u, v);
+        else unpack_h8<false>(u, v);
+    }
+}
+__device__ __forceinline__ void store8_from_f32(char* p, int dt, int64_t i, const float* v) {
+    if (dt == MF_F32) {
+        *reinterpret_cast<float4*>(p + i * 4) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(p + i * 4 + 16) = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+        *reinterpret_cast<uint4*>(p + i * 2) = dt == MF_F16 ? pack_h8<true>(v) : pack_h8<false>(v);
+    }
+}
+
+// out[b][s][:] = token_table[ids[b][s]][:] + pos_table[s][:]; an id outside [0, vocab) is clamped, never read out of range
+__global__ __launch_bounds__(256) void embed_tokens_kernel(const int32_t* ids, const char* tok, const char* pos, int tdt, char* out, int odt,
+                                                           int64_t rows, int seq, int h8, int vocab) {
+    const int64_t total = rows * h8;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / h8;
+        const int c = (int)(i - row * h8) * 8;
+        int id = ids[row];
+        id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+        const int hidden = h8 * 8;
+        float a[8], b[8];
+        load8_as_f32(tok, tdt, (int64_t)id * hidden + c, a);
+        load8_as_f32(pos, tdt, (int64_t)(row % seq) * hidden + c, b);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] += b[e];
+        store8_from_f32(out, odt, row * hidden + c, a);
+    }
+}
+
+// MF_ACT_QUICK_GELU: x * sigmoid(1.702 x) (CLIP-L); MF_ACT_GELU_ERF: exact erf GELU (OpenCLIP bigG); n8 = n / 8
+__global__ __launch_bounds__(256) void act_kernel(const char* x, char* out, int dt, int kind, int64_t n8) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+        float v[8];
+        load8_as_f32(x, dt, i * 8, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = kind == MF_ACT_QUICK_GELU ? v[e] / (1.0f + expf(-1.702f * v[e])) : gelu_erf(v[e]);
+        store8_from_f32(out, dt, i * 8, v);
+    }
+}
+
 __global__ void silu_f32_kernel(const float* x, float* o, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         o[i] = silu_precise(x[i]);
@@ -408,6 +459,38 @@ extern "C" int mf_timestep_embedding(const float* t, float* out, int32_t n, int3
     hipLaunchKernelGGL(timestep_embedding_kernel, dim3(grid_for((int64_t)n * (dim / 2))), dim3(256), 0,
                        (hipStream_t)stream, t, out, n, dim, flip_sin_to_cos, freq_shift);
     MF_CHECK_LAUNCH("mf_timestep_embedding");
+    return MF_OK;
+}
+
+extern "C" int mf_embed_tokens(const int32_t* ids, const void* token_table, const void* pos_table, int32_t table_dtype, void* out,
+                               int32_t out_dtype, int32_t batch, int32_t seq, int32_t hidden, int32_t vocab, void* stream) {
+    MF_CHECK_ARG(ids && token_table && pos_table && out, "mf_embed_tokens: null pointer");
+    MF_CHECK_ARG(batch >= 1 && seq >= 1 && vocab >= 1 && hidden >= 8 && hidden % 8 == 0, "mf_embed_tokens: bad sizes (hidden %% 8 == 0)");
+    MF_CHECK_ARG((table_dtype == MF_F32 || mf_is16(table_dtype)) && (out_dtype == MF_F32 || mf_is16(out_dtype)),
+                 "mf_embed_tokens: tables and out are fp32, bf16 or fp16");
+    MF_CHECK_ARG(!(mf_any_f16(table_dtype, out_dtype) && mf_any_bf16(table_dtype, out_dtype)), "mf_embed_tokens: fp16 and bf16 operands in one launch");
+    if (!mf_aligned16(token_table) || !mf_aligned16(pos_table) || !mf_aligned16(out)) {
+        mf_set_error("mf_embed_tokens: tables and out must be 16-byte aligned");
+        return MF_EALIGN;
+    }
+    const int64_t rows = (int64_t)batch * seq;
+    hipLaunchKernelGGL(embed_tokens_kernel, dim3(grid_for(rows * (hidden / 8))), dim3(256), 0, (hipStream_t)stream, ids,
+                       (const char*)token_table, (const char*)pos_table, table_dtype, (char*)out, out_dtype, rows, seq, hidden / 8, vocab);
+    MF_CHECK_LAUNCH("mf_embed_tokens");
+    return MF_OK;
+}
+
+extern "C" int mf_act(const void* x, void* out, int32_t dtype, int32_t kind, int64_t n, void* stream) {
+    MF_CHECK_ARG(x && out && n >= 0 && n % 8 == 0, "mf_act: null pointer or n not a multiple of 8");
+    MF_CHECK_ARG(dtype == MF_F32 || mf_is16(dtype), "mf_act: fp32, bf16 or fp16");
+    MF_CHECK_ARG(kind == MF_ACT_QUICK_GELU || kind == MF_ACT_GELU_ERF, "mf_act: kind must be MF_ACT_QUICK_GELU or MF_ACT_GELU_ERF");
+    if (!mf_aligned16(x) || !mf_aligned16(out)) {
+        mf_set_error("mf_act: pointers must be 16-byte aligned");
+        return MF_EALIGN;
+    }
+    if (n == 0) return MF_OK;
+    hipLaunchKernelGGL(act_kernel, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const char*)x, (char*)out, dtype, kind, n / 8);
+    MF_CHECK_LAUNCH("mf_act");
     return MF_OK;
 }
 

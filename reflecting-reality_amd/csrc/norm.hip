@@ -680,12 +680,18 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const char* x, int in_dt
 }
 
 // One wave per row: max, sum(exp), normalise; pad columns [cols, ld) are zeroed.
+// CAUSAL (sq > 0): row r is query r % sq and keeps columns 0 .. r % sq; the rest of the row is written as 0 like the pad.
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* s, char* out, int out_dt, int64_t rows,
-                                                           int cols, int ld) {
+                                                           int cols, int ld, int sq) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* r = s + row * ld;
+    if constexpr (CAUSAL) {
+        const int keep = (int)(row % sq) + 1;
+        if (keep < cols) cols = keep;
+    }
     float mx = -INFINITY;
     for (int c = lane; c < cols; c += 64) mx = fmaxf(mx, r[c]);
 #pragma unroll
@@ -839,8 +845,19 @@ extern "C" int mf_softmax_rows(const float* scores, void* out, int32_t out_dtype
                                int32_t ld, void* stream) {
     MF_CHECK_ARG(scores && out && cols >= 1 && ld >= cols, "mf_softmax_rows: bad arguments");
     if (rows <= 0) return MF_OK;
-    hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       scores, (char*)out, out_dtype, rows, cols, ld);
+    hipLaunchKernelGGL(softmax_rows_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       scores, (char*)out, out_dtype, rows, cols, ld, 0);
     MF_CHECK_LAUNCH("mf_softmax_rows");
+    return MF_OK;
+}
+
+extern "C" int mf_softmax_rows_causal(const float* scores, void* out, int32_t out_dtype, int64_t rows, int32_t cols,
+                                      int32_t ld, int32_t sq, void* stream) {
+    MF_CHECK_ARG(scores && out && cols >= 1 && ld >= cols, "mf_softmax_rows_causal: bad arguments");
+    MF_CHECK_ARG(sq >= 1 && sq == cols && rows % sq == 0, "mf_softmax_rows_causal: the causal mask needs sq == cols and rows %% sq == 0");
+    if (rows <= 0) return MF_OK;
+    hipLaunchKernelGGL(softmax_rows_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       scores, (char*)out, out_dtype, rows, cols, ld, sq);
+    MF_CHECK_LAUNCH("mf_softmax_rows_causal");
     return MF_OK;
 }

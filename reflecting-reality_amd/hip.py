@@ -17,7 +17,8 @@ from . import _build
 MF_F32, MF_BF16, MF_F16X3, MF_BF16X3, MF_FP8, MF_BF16X1, MF_F16 = 0, 1, 2, 3, 4, 5, 6
 FP8 = torch.float8_e4m3fn          # OCP e4m3 (gfx950's fp8), 1 byte per element
 ACT_NONE, ACT_SILU, ACT_GEGLU4 = 0, 1, 2
-ABI_VERSION = 21
+ACT_QUICK_GELU, ACT_GELU_ERF = 3, 4      # mf_act only (the CLIP text encoders' MLP): mf_gemm_conv has no such epilogue
+ABI_VERSION = 22
 
 
 class MfhipError(RuntimeError):
@@ -144,7 +145,8 @@ EXPORTS = [
     "mf_abi_version", "mf_last_error", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc",
     "mf_gemm_conv", "mf_gemm_num_tiles", "mf_gemm_tile_shape", "mf_gemm_tile_table_version",
     "mf_groupnorm", "mf_groupnorm_ws_floats", "mf_layernorm", "mf_softmax_rows", "mf_attention_bf16", "mf_attention_f16",
-    "mf_attention_f16x3", "mf_attention_f16x3_lse", "mf_sizeof_attn_bwd_desc", "mf_attention_bwd_f16x3", "mf_rowdot_heads",
+    "mf_attention_f16x3", "mf_attention_f16x3_lse", "mf_attention_causal_bf16", "mf_attention_causal_f16", "mf_attention_causal_f16x3",
+    "mf_softmax_rows_causal", "mf_embed_tokens", "mf_act", "mf_sizeof_attn_bwd_desc", "mf_attention_bwd_f16x3", "mf_rowdot_heads",
     "mf_attention_bwd_bf16", "mf_attention_bf16_lse", "mf_rowdot_heads_bf16", "mf_cast_bf16_colsum", "mf_cast_bf16_colsum_ws_floats",
     "mf_transpose_bf16_bf16", "mf_geglu_bwd_bf16", "mf_geglu_bwd_bf16_ws_floats", "mf_rowdot_heads_cast", "mf_debug_set_wgrad_dma", "mf_zero_ranges",
     "mf_split_halves", "mf_split_overflow", "mf_quantize_rows_fp8",
@@ -781,11 +783,68 @@ def softmax_rows(scores: torch.Tensor, cols: int, out_dtype: torch.dtype) -> tor
     return out
 
 
+def softmax_rows_causal(scores: torch.Tensor, cols: int, sq: int, out_dtype: torch.dtype) -> torch.Tensor:
+    """softmax_rows under a causal mask: scores [batch * heads, sq, ld]; query i keeps columns 0 .. i, the rest is written as 0."""
+    _req_cuda(scores)
+    ld = scores.shape[-1]
+    rows = scores.numel() // ld
+    out = torch.empty(scores.shape, dtype=out_dtype, device=scores.device)
+    _check(load().mf_softmax_rows_causal(C.c_void_p(scores.data_ptr()), C.c_void_p(out.data_ptr()), dt_code(out_dtype),
+                                         C.c_int64(rows), cols, ld, sq, _stream()), "mf_softmax_rows_causal")
+    return out
+
+
+def embed_tokens(ids: torch.Tensor, token_table: torch.Tensor, pos_table: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+    """out[b][s] = token_table[ids[b][s]] + pos_table[s] (mf_embed_tokens).  `ids`: [B, S] integers.  A HOST tensor is checked against
+    the vocabulary here (ValueError) before it is copied; on the device the kernel clamps, so no id ever reads out of range."""
+    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
+        raise MfhipError("embed_tokens: ids is a [batch, seq] int32 / int64 tensor")
+    vocab, hidden = token_table.shape
+    b, s = ids.shape
+    if not ids.is_cuda:
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= vocab):
+            raise ValueError(f"embed_tokens: token ids must lie in [0, {vocab}), got [{int(ids.min())}, {int(ids.max())}]")
+        ids = ids.to(torch.int32).to(token_table.device)
+    _req_cuda(ids, token_table, pos_table)
+    ids = ids.to(torch.int32).contiguous()
+    if (token_table.dtype != pos_table.dtype or pos_table.shape[0] < s or pos_table.shape[1] != hidden
+            or not token_table.is_contiguous() or not pos_table.is_contiguous()):
+        raise MfhipError("embed_tokens: contiguous tables of one dtype, [vocab, hidden] and [>= seq, hidden]")
+    out = torch.empty(b, s, hidden, dtype=out_dtype, device=token_table.device)
+    _check(load().mf_embed_tokens(C.c_void_p(ids.data_ptr()), C.c_void_p(token_table.data_ptr()), C.c_void_p(pos_table.data_ptr()),
+                                  dt_code(token_table.dtype), C.c_void_p(out.data_ptr()), dt_code(out_dtype), b, s, hidden, vocab,
+                                  _stream()), "mf_embed_tokens")
+    return out
+
+
+def act(x: torch.Tensor, kind: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ACT_QUICK_GELU (x * sigmoid(1.702 x)) or ACT_GELU_ERF over a contiguous fp32 / bf16 / fp16 tensor; `out=x` runs in place."""
+    _req_cuda(x, out)
+    if not x.is_contiguous():
+        raise MfhipError("act: contiguous input")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != x.dtype or out.shape != x.shape or not out.is_contiguous():
+        raise MfhipError("act: out has x's dtype and shape")
+    _check(load().mf_act(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), dt_code(x.dtype), kind, C.c_int64(x.numel()),
+                         _stream()), "mf_act")
+    return out
+
+
 def attention_bf16(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, *, ldq: int, ldk: int,
                    ldvt: int, ldo: int, batch: int, heads: int, sq: int, skv: int, head_dim: int, scale: float,
-                   lse: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """`lse` (fp32 [batch, heads, sq], written): the row statistic of the flash backward (mf_attention_bf16_lse)."""
+                   lse: Optional[torch.Tensor] = None, causal: bool = False) -> torch.Tensor:
+    """`lse` (fp32 [batch, heads, sq], written): the row statistic of the flash backward (mf_attention_bf16_lse).
+    `causal`: query i attends keys 0 .. i (mf_attention_causal_bf16 / _f16; sq == skv, inference: no lse)."""
     _req_cuda(q, k, vt, out, lse)
+    if causal:
+        if lse is not None or not (q.dtype == k.dtype == vt.dtype == out.dtype) or q.dtype not in (torch.bfloat16, torch.float16):
+            raise MfhipError("attention_bf16(causal=True): bf16 or fp16 q / k / vt / out of one dtype and no lse")
+        fn = "mf_attention_causal_f16" if q.dtype == torch.float16 else "mf_attention_causal_bf16"
+        _check(getattr(load(), fn)(C.c_void_p(q.data_ptr()), C.c_int64(ldq), C.c_void_p(k.data_ptr()), C.c_int64(ldk),
+                                   C.c_void_p(vt.data_ptr()), C.c_int64(ldvt), C.c_void_p(out.data_ptr()),
+                                   C.c_int64(ldo), batch, heads, sq, skv, head_dim, C.c_float(scale), _stream()), fn)
+        return out
     if PROFILE is not None:               # bench.py's FLOP census (no timing here: the GEMM family is the timed one)
         global PROFILE_ATTN_FLOPS
         PROFILE_ATTN_FLOPS += 4.0 * batch * heads * sq * skv * head_dim
@@ -879,10 +938,19 @@ def split_halves(x: torch.Tensor):
 
 
 def attention_f16x3(q, k, vt, out: torch.Tensor, *, ldq: int, ldk: int, ldvt: int, ldo: int, batch: int, heads: int,
-                    sq: int, skv: int, head_dim: int, scale: float, lse: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    sq: int, skv: int, head_dim: int, scale: float, lse: Optional[torch.Tensor] = None, causal: bool = False) -> torch.Tensor:
     """q / k / vt: (hi, lo) pairs from split_halves; out fp32.  lse (optional, fp32 [batch, heads, sq]): the row statistics the
-    flash backward needs."""
+    flash backward needs.  causal: mf_attention_causal_f16x3 (sq == skv, no lse)."""
     _req_cuda(*q, *k, *vt, out, lse)
+    if causal:
+        if lse is not None:
+            raise MfhipError("attention_f16x3(causal=True): inference only, no lse")
+        _check(load().mf_attention_causal_f16x3(C.c_void_p(q[0].data_ptr()), C.c_void_p(q[1].data_ptr()), C.c_int64(ldq),
+                                                C.c_void_p(k[0].data_ptr()), C.c_void_p(k[1].data_ptr()), C.c_int64(ldk),
+                                                C.c_void_p(vt[0].data_ptr()), C.c_void_p(vt[1].data_ptr()), C.c_int64(ldvt),
+                                                C.c_void_p(out.data_ptr()), C.c_int64(ldo), batch, heads, sq, skv, head_dim,
+                                                C.c_float(scale), _stream()), "mf_attention_causal_f16x3")
+        return out
     _check(load().mf_attention_f16x3_lse(C.c_void_p(q[0].data_ptr()), C.c_void_p(q[1].data_ptr()), C.c_int64(ldq),
                                          C.c_void_p(k[0].data_ptr()), C.c_void_p(k[1].data_ptr()), C.c_int64(ldk),
                                          C.c_void_p(vt[0].data_ptr()), C.c_void_p(vt[1].data_ptr()), C.c_int64(ldvt),

@@ -558,8 +558,9 @@ def attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
 
 
 def attention_unfused(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, skv: int, scale: float,
-                      prec: Precision) -> torch.Tensor:
+                      prec: Precision, causal: bool = False) -> torch.Tensor:
     """softmax(q k^T * scale) v through two strided-batched GEMMs and a row softmax (scores in fp32).
+    causal: query i keeps keys 0 .. i (mf_softmax_rows_causal; sq == skv).
 
     q: [B, Sq, C], k: [B, Skv, C], vt: [B, C, ldv] (V^T, pad columns zero).  Used by the fp32 parity
     mode and by head dims the fused kernel does not cover (the VAE's single 512-wide head).
@@ -571,7 +572,9 @@ def attention_unfused(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads:
     hip.gemm_conv(q, k, scores, dtype=prec.code, c0=d, lda0=c, batch=sq, h_in=1, w_in=1, h_out=1, w_out=1,
                   ldw=c, n=skv, ldc=ldv, alpha=scale, nz=b * heads, zdiv=heads,
                   a_zs=(sq * c, d), w_zs=(k.shape[1] * c, d), o_zs=(heads * sq * ldv, sq * ldv), splitk=1)
-    p = hip.softmax_rows(scores, skv, prec.act)
+    if causal and sq != skv:
+        raise hip.MfhipError(f"attention_unfused: the causal mask needs sq == skv (got {sq}, {skv})")
+    p = hip.softmax_rows_causal(scores, skv, sq, prec.act) if causal else hip.softmax_rows(scores, skv, prec.act)
     out = torch.empty(b, sq, c, dtype=prec.act, device=q.device)
     hip.gemm_conv(p, vt, out, dtype=prec.code, c0=ldv, lda0=ldv, batch=sq, h_in=1, w_in=1, h_out=1, w_out=1,
                   ldw=ldv, n=d, ldc=c, nz=b * heads, zdiv=heads,
@@ -587,19 +590,27 @@ import os as _os
 FLASH_BWD = _os.environ.get("MFHIP_NO_FLASH_BWD") != "1"       # A/B switch
 FLASH_HEAD_DIMS = (8, 40, 64, 80, 160)
 FLASH_SPLIT_HEAD_DIMS = (8, 40, 64, 80)          # 160 (two split K / V^T planes, double buffered) does not fit in LDS
+FLASH_CAUSAL_HEAD_DIMS = (8, 64)                 # mf_attention_causal_*: both CLIP text encoders and the tiny test configs
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, skv: int, scale: float,
-              prec: Precision, c: Optional[int] = None) -> torch.Tensor:
-    """q: [B, Sq, ldq] and k: [B, Skv, ldk] may be column slices of a fused projection (`c` = model width)."""
+              prec: Precision, c: Optional[int] = None, causal: bool = False) -> torch.Tensor:
+    """q: [B, Sq, ldq] and k: [B, Skv, ldk] may be column slices of a fused projection (`c` = model width).
+    causal: query i attends keys 0 .. i (the CLIP text encoders; sq == skv, inference only)."""
     b, sq, ldq = q.shape
     c = c or ldq
     d = c // heads
-    if prec.half and d in FLASH_HEAD_DIMS:           # bf16, or fp16 on the f16 MFMA forms (hip.attention_bf16 dispatches on q.dtype)
+    if causal:
+        if TAPE is not None or sq != skv:
+            raise hip.MfhipError(f"attention(causal=True): inference only and sq == skv (got {sq}, {skv})")
+        if prec.code != hip.MF_F32 and d not in FLASH_CAUSAL_HEAD_DIMS:
+            raise hip.MfhipError(f"attention(causal=True): head_dim {d} has no causal flash kernel (have {FLASH_CAUSAL_HEAD_DIMS})")
+    flash_dims, split_dims = (FLASH_CAUSAL_HEAD_DIMS,) * 2 if causal else (FLASH_HEAD_DIMS, FLASH_SPLIT_HEAD_DIMS)
+    if prec.half and d in flash_dims:           # bf16, or fp16 on the f16 MFMA forms (hip.attention_bf16 dispatches on q.dtype)
         out = torch.empty(b, sq, c, dtype=prec.compute, device=q.device)
         return hip.attention_bf16(q, k, vt, out, ldq=q.stride(1), ldk=k.stride(1), ldvt=vt.shape[-1], ldo=c, batch=b,
-                                  heads=heads, sq=sq, skv=skv, head_dim=d, scale=scale)
-    if prec.code == hip.MF_F16X3 and d in FLASH_SPLIT_HEAD_DIMS and vt.shape[-1] % 8 == 0:
+                                  heads=heads, sq=sq, skv=skv, head_dim=d, scale=scale, causal=causal)
+    if prec.code == hip.MF_F16X3 and d in split_dims and vt.shape[-1] % 8 == 0:
         # the parity mode runs the same flash kernel: operands as (hi, lo) fp16 planes, fp32 output.  q and k may be
         # column slices of one fused projection: split the parent once and slice the planes
         if q.stride(1) != c and q.storage_offset() + c == k.storage_offset() and q.stride(1) == k.stride(1) == 2 * c:
@@ -611,7 +622,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, sk
         vs = hip.split_halves(vt)
         out = torch.empty(b, sq, c, dtype=torch.float32, device=q.device)
         return hip.attention_f16x3(qs, ks, vs, out, ldq=qs[0].stride(1), ldk=ks[0].stride(1), ldvt=vt.shape[-1], ldo=c,
-                                   batch=b, heads=heads, sq=sq, skv=skv, head_dim=d, scale=scale)
+                                   batch=b, heads=heads, sq=sq, skv=skv, head_dim=d, scale=scale, causal=causal)
     if q.stride(1) != c or k.stride(1) != c:
         q, k = q.contiguous(), k.contiguous()
-    return attention_unfused(q, k, vt, heads, skv, scale, prec)
+    return attention_unfused(q, k, vt, heads, skv, scale, prec, causal=causal)

@@ -173,7 +173,9 @@ class StableDiffusionBrushNetPipeline:
         a default are modules — taken from kwargs, else loaded from the sub-folder `model_index.json` names (`brushnet`
         is never in an SD1.5 index, so it must be passed, like in the reference); parameters with a default
         (`depth_conditioning_mode`, ...) are plain kwargs.  `unet=None` means "load it from the base directory".
-        Text encoder / tokenizer are outside the accelerated path: passed-in objects are kept, nothing is loaded."""
+        `text_encoder/` is loaded into the HIP CLIPTextModel (text_encoder.py) when the folder exists and no `text_encoder=` was
+        passed.  The tokenizer is string processing and stays the caller's object; `tokenizer/` is loaded through
+        transformers.CLIPTokenizer when transformers is importable, else left None."""
         import json
         import os
         from . import schedulers as S
@@ -202,7 +204,18 @@ class StableDiffusionBrushNetPipeline:
         if kwargs.pop("safety_checker", None) is not None:
             raise NotImplementedError("the safety checker is outside the accelerated path; pass safety_checker=None")
         kwargs.pop("low_cpu_mem_usage", None)
-        return cls(vae=mods["vae"], text_encoder=kwargs.pop("text_encoder", None), tokenizer=kwargs.pop("tokenizer", None),
+        text_encoder, tokenizer = kwargs.pop("text_encoder", None), kwargs.pop("tokenizer", None)
+        if text_encoder is None and os.path.isdir(os.path.join(root, "text_encoder")):
+            from .text_encoder import CLIPTextModel
+            text_encoder = CLIPTextModel.from_pretrained(root, subfolder="text_encoder", torch_dtype=torch_dtype, device=device)
+        if tokenizer is None and os.path.isdir(os.path.join(root, "tokenizer")):
+            try:
+                from transformers import CLIPTokenizer
+            except ImportError:
+                CLIPTokenizer = None
+            if CLIPTokenizer is not None:
+                tokenizer = CLIPTokenizer.from_pretrained(root, subfolder="tokenizer")
+        return cls(vae=mods["vae"], text_encoder=text_encoder, tokenizer=tokenizer,
                    unet=mods["unet"], brushnet=mods["brushnet"], scheduler=sched, safety_checker=None,
                    feature_extractor=kwargs.pop("feature_extractor", None),
                    requires_safety_checker=kwargs.pop("requires_safety_checker", False),
@@ -224,6 +237,10 @@ class StableDiffusionBrushNetPipeline:
         index["scheduler"] = ["diffusers", type(self.scheduler).__name__]
         for name in ("text_encoder", "tokenizer", "safety_checker", "feature_extractor"):
             index[name] = [None, None]
+        from .text_encoder import CLIPTextModel
+        if isinstance(self.text_encoder, CLIPTextModel):
+            self.text_encoder.save_pretrained(os.path.join(save_directory, "text_encoder"))
+            index["text_encoder"] = ["transformers", self.text_encoder._class_name]
         index.update(requires_safety_checker=False, depth_conditioning_mode=self.depth_conditioning_mode,
                      normals_conditioning_mode=self.normals_conditioning_mode)
         with open(os.path.join(save_directory, "model_index.json"), "w") as f:
@@ -237,8 +254,10 @@ class StableDiffusionBrushNetPipeline:
     _execution_device = device
 
     def to(self, *args, **kwargs):
-        for m in (self.vae, self.unet, self.brushnet):
-            m.to(*args, **kwargs)
+        from .models import HipModel
+        for m in (self.vae, self.unet, self.brushnet, self.text_encoder, getattr(self, "text_encoder_2", None)):
+            if isinstance(m, HipModel):
+                m.to(*args, **kwargs)
         return self
 
     def set_progress_bar_config(self, **kwargs):
@@ -347,7 +366,7 @@ class StableDiffusionBrushNetPipeline:
                       negative_prompt_embeds=None, clip_skip: Optional[int] = None):
         """pipeline_brushnet.py:271-450 without LoRA / textual inversion.  clip_skip (:352-370): the hidden state clip_skip layers
         before the last one, through the text model's final LayerNorm (the text encoder is the caller's torch module: outside the
-        accelerated path)."""
+        accelerated path, or text_encoder.CLIPTextModel: the same calls on the HIP kernels)."""
         if prompt_embeds is None:
             if self.text_encoder is None or self.tokenizer is None:
                 raise ValueError("pass `prompt_embeds` or construct the pipeline with a text_encoder and tokenizer")
@@ -502,8 +521,9 @@ class StableDiffusionBrushNetPipeline:
         else:
             batch_size = prompt_embeds.shape[0]
         do_cfg = self.do_classifier_free_guidance
-        prompt_embeds, negative_prompt_embeds = self.encode_prompt(
-            prompt, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds, clip_skip=clip_skip)
+        # (the SD1.5 form by name: the XL subclass has its own encode_prompt and hands this loop finished embeddings)
+        prompt_embeds, negative_prompt_embeds = StableDiffusionBrushNetPipeline.encode_prompt(
+            self, prompt, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds, negative_prompt_embeds, clip_skip=clip_skip)
         pe = torch.cat([negative_prompt_embeds, prompt_embeds]) if do_cfg else prompt_embeds         # :1103
         pe = pe.to(self.device)
         nb = batch_size * num_images_per_prompt
@@ -874,7 +894,8 @@ class StableDiffusionXLBrushNetPipeline(StableDiffusionBrushNetPipeline):
     """pipelines/brushnet/pipeline_brushnet_sd_xl.py:936-1535 on the same engine: the SDXL UNet / BrushNet-XL add the
     'text_time' embedding (pooled text embedding + Fourier features of original size / crop / target size) to the time
     embedding; conditioning is [masked-image latents | mask] (5 channels, :1301-1310); everything else is the
-    SD1.5 loop.  Text encoders are outside the accelerated path: pass prompt_embeds and pooled_prompt_embeds."""
+    SD1.5 loop.  Prompts go through encode_prompt (text_encoder.CLIPTextModel / CLIPTextModelWithProjection, or the caller's
+    torch modules); prompt_embeds / pooled_prompt_embeds are taken as they are."""
 
     def __init__(self, vae, text_encoder, text_encoder_2, tokenizer, tokenizer_2, unet, brushnet, scheduler,
                  force_zeros_for_empty_prompt: bool = True, add_watermarker=None, feature_extractor=None,
@@ -899,6 +920,74 @@ class StableDiffusionXLBrushNetPipeline(StableDiffusionBrushNetPipeline):
         return torch.tensor([ids], dtype=torch.float32)
 
     @torch.no_grad()
+    def encode_prompt(self, prompt, prompt_2=None, device=None, num_images_per_prompt: int = 1,
+                      do_classifier_free_guidance: bool = True, negative_prompt=None, negative_prompt_2=None, prompt_embeds=None,
+                      negative_prompt_embeds=None, pooled_prompt_embeds=None, negative_pooled_prompt_embeds=None,
+                      lora_scale=None, clip_skip: Optional[int] = None):
+        """pipeline_brushnet_sd_xl.py:213-420 without LoRA / textual inversion: returns (prompt_embeds, negative_prompt_embeds,
+        pooled_prompt_embeds, negative_pooled_prompt_embeds), fp32 on the pipeline's device.  Either text encoder may be None
+        when the other exists (:299-302)."""
+        device = device or self.device
+        if lora_scale is not None:
+            raise NotImplementedError("LoRA layers of the text encoders are outside the accelerated path")
+        prompt = [prompt] if isinstance(prompt, str) else prompt
+        batch_size = len(prompt) if prompt is not None else prompt_embeds.shape[0]
+        tokenizers = [self.tokenizer, self.tokenizer_2] if self.tokenizer is not None else [self.tokenizer_2]
+        text_encoders = [self.text_encoder, self.text_encoder_2] if self.text_encoder is not None else [self.text_encoder_2]
+        if prompt_embeds is None or (do_classifier_free_guidance and negative_prompt_embeds is None):
+            if any(m is None for m in tokenizers + text_encoders):
+                raise ValueError("pass `prompt_embeds` / `pooled_prompt_embeds` or construct the pipeline with text encoders and tokenizers")
+
+        def encode(texts, tokenizer, text_encoder, max_length):
+            ids = tokenizer(texts, padding="max_length", max_length=max_length, truncation=True, return_tensors="pt").input_ids
+            return text_encoder(ids.to(device), output_hidden_states=True)
+
+        if prompt_embeds is None:
+            prompt_2 = prompt_2 or prompt
+            prompt_2 = [prompt_2] if isinstance(prompt_2, str) else prompt_2
+            embeds_list = []
+            for texts, tokenizer, text_encoder in zip([prompt, prompt_2], tokenizers, text_encoders):
+                out = encode(texts, tokenizer, text_encoder, tokenizer.model_max_length)
+                pooled_prompt_embeds = out[0]           # "We are only ALWAYS interested in the pooled output of the final text encoder"
+                embeds_list.append(out.hidden_states[-2] if clip_skip is None else out.hidden_states[-(clip_skip + 2)])
+            prompt_embeds = torch.concat(embeds_list, dim=-1)
+        zero_out_negative_prompt = negative_prompt is None and self.config["force_zeros_for_empty_prompt"]
+        if do_classifier_free_guidance and negative_prompt_embeds is None and zero_out_negative_prompt:
+            negative_prompt_embeds = torch.zeros_like(prompt_embeds)
+            negative_pooled_prompt_embeds = torch.zeros_like(pooled_prompt_embeds)
+        elif do_classifier_free_guidance and negative_prompt_embeds is None:
+            negative_prompt = negative_prompt or ""
+            negative_prompt_2 = negative_prompt_2 or negative_prompt
+            negative_prompt = batch_size * [negative_prompt] if isinstance(negative_prompt, str) else negative_prompt
+            negative_prompt_2 = batch_size * [negative_prompt_2] if isinstance(negative_prompt_2, str) else negative_prompt_2
+            if prompt is not None and type(prompt) is not type(negative_prompt):
+                raise TypeError(f"`negative_prompt` should be the same type to `prompt`, but got {type(negative_prompt)} !="
+                                f" {type(prompt)}.")
+            elif batch_size != len(negative_prompt):
+                raise ValueError(f"`negative_prompt`: {negative_prompt} has batch size {len(negative_prompt)}, but `prompt`:"
+                                 f" {prompt} has batch size {batch_size}. Please make sure that passed `negative_prompt` matches"
+                                 " the batch size of `prompt`.")
+            embeds_list = []
+            for texts, tokenizer, text_encoder in zip([negative_prompt, negative_prompt_2], tokenizers, text_encoders):
+                out = encode(texts, tokenizer, text_encoder, prompt_embeds.shape[1])
+                negative_pooled_prompt_embeds = out[0]
+                embeds_list.append(out.hidden_states[-2])
+            negative_prompt_embeds = torch.concat(embeds_list, dim=-1)
+        bs_embed, seq_len, _ = prompt_embeds.shape
+        prompt_embeds = prompt_embeds.to(device, torch.float32).repeat(1, num_images_per_prompt, 1).view(
+            bs_embed * num_images_per_prompt, seq_len, -1)
+        if do_classifier_free_guidance:
+            seq_len = negative_prompt_embeds.shape[1]
+            negative_prompt_embeds = negative_prompt_embeds.to(device, torch.float32).repeat(1, num_images_per_prompt, 1).view(
+                batch_size * num_images_per_prompt, seq_len, -1)
+        pooled_prompt_embeds = pooled_prompt_embeds.to(device, torch.float32).repeat(1, num_images_per_prompt).view(
+            bs_embed * num_images_per_prompt, -1)
+        if do_classifier_free_guidance:
+            negative_pooled_prompt_embeds = negative_pooled_prompt_embeds.to(device, torch.float32).repeat(
+                1, num_images_per_prompt).view(bs_embed * num_images_per_prompt, -1)
+        return prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds
+
+    @torch.no_grad()
     def __call__(self, prompt=None, prompt_2=None, image=None, mask=None, height=None, width=None,
                  num_inference_steps: int = 50, denoising_end=None, guidance_scale: float = 5.0, negative_prompt=None,
                  negative_prompt_2=None, num_images_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None,
@@ -911,8 +1000,16 @@ class StableDiffusionXLBrushNetPipeline(StableDiffusionBrushNetPipeline):
                  callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), conditioning_noise=None,
                  **kwargs):
         if prompt is not None or prompt_2 is not None or negative_prompt is not None or negative_prompt_2 is not None:
-            raise NotImplementedError("the two CLIP text encoders are outside the accelerated path: pass prompt_embeds, "
-                                      "negative_prompt_embeds, pooled_prompt_embeds and negative_pooled_prompt_embeds")
+            # pipeline_brushnet_sd_xl.py:1283-1302: prompts (and whichever embeddings were passed) through encode_prompt once, for ONE
+            # image per prompt: the shared path below does the per-image repeats exactly as it does for passed-in embeddings
+            if prompt is not None and prompt_embeds is not None:
+                raise ValueError(f"Cannot forward both `prompt`: {prompt} and `prompt_embeds`. Please make sure to only forward one of the two.")
+            if prompt is None and prompt_embeds is None:
+                raise ValueError("Provide either `prompt` or `prompt_embeds`. Cannot leave both `prompt` and `prompt_embeds` undefined.")
+            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = self.encode_prompt(
+                prompt, prompt_2, self.device, 1, guidance_scale > 1, negative_prompt, negative_prompt_2, prompt_embeds=prompt_embeds,
+                negative_prompt_embeds=negative_prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
+                negative_pooled_prompt_embeds=negative_pooled_prompt_embeds, clip_skip=clip_skip)
         if prompt_embeds is None or pooled_prompt_embeds is None:
             raise ValueError("If `prompt_embeds` are provided, `pooled_prompt_embeds` also have to be passed. Make sure to "
                              "generate `pooled_prompt_embeds` from the same text encoder that was used to generate `prompt_embeds`.")

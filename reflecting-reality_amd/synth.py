@@ -25,7 +25,7 @@ def fill(key: str, shape: Iterable[int], seed: int = 0) -> torch.Tensor:
     parts = key.split(".")
     leaf = parts[-1]
     parent = parts[-2] if len(parts) >= 2 else ""
-    is_norm = parent.startswith("norm") or parent in ("conv_norm_out", "group_norm")
+    is_norm = parent.startswith("norm") or parent in ("conv_norm_out", "group_norm") or "layer_norm" in parent   # (CLIP: layer_norm1, final_layer_norm)
     if leaf == "weight" and is_norm and len(shape) == 1:
         return 1.0 + 0.1 * torch.randn(shape, generator=g)
     if leaf == "bias":
@@ -61,3 +61,42 @@ def pipeline_inputs(batch: int, height: int, width: int, seed: int = 1234, cross
     vae_noise = torch.randn(2 * batch, latent_channels, hl, wl, generator=g)   # uncond half, then cond half
     return dict(prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, image=image, mask=mask,
                 depth=depth, latents=latents, vae_noise=vae_noise)
+
+
+class HashTokenizer:
+    """Deterministic stand-in for CLIPTokenizer (no vocabulary file exists offline): lower-cased whitespace words hash to ids in
+    [1, vocab_size - 3], wrapped in <bos> = vocab_size - 2 and <eos> = vocab_size - 1 (the highest id, as in CLIP's 49406 / 49407).
+    `pad_token_id` None pads with <eos> (CLIP-L's tokenizer), 0 pads with "!" like SDXL's second tokenizer.  Provides what both
+    pipelines' encode_prompt touch: model_max_length, __call__ with padding / max_length / truncation / return_tensors, batch_decode."""
+
+    class _Encoding:
+        def __init__(self, input_ids):
+            self.input_ids = input_ids
+
+    def __init__(self, vocab_size: int = 49408, model_max_length: int = 77, pad_token_id=None):
+        self.vocab_size, self.model_max_length = int(vocab_size), int(model_max_length)
+        self.bos_token_id, self.eos_token_id = self.vocab_size - 2, self.vocab_size - 1
+        self.pad_token_id = self.eos_token_id if pad_token_id is None else int(pad_token_id)
+
+    def _ids(self, text: str):
+        return [self.bos_token_id] + [1 + zlib.crc32(w.encode()) % (self.vocab_size - 3) for w in text.lower().split()] + [self.eos_token_id]
+
+    def __call__(self, text, padding=False, max_length=None, truncation=False, return_tensors=None):
+        rows = [self._ids(t) for t in ([text] if isinstance(text, str) else list(text))]
+        limit = max_length if max_length is not None else self.model_max_length
+        if truncation:
+            rows = [r if len(r) <= limit else r[:limit - 1] + [self.eos_token_id] for r in rows]
+        if padding == "max_length":
+            width = limit
+        elif padding in ("longest", True):
+            width = max(len(r) for r in rows)
+        else:
+            width = None
+        if width is not None:
+            rows = [r + [self.pad_token_id] * (width - len(r)) for r in rows]
+        if return_tensors == "pt":
+            return self._Encoding(torch.tensor(rows, dtype=torch.int64))
+        return self._Encoding(rows if not isinstance(text, str) else rows[0])
+
+    def batch_decode(self, ids):
+        return [" ".join(f"<{int(i)}>" for i in row) for row in ids]

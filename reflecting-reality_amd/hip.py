@@ -140,32 +140,56 @@ class SchedRow(C.Structure):
                 ("ops", SchedOp * SCHED_MAX_OPS)]
 
 
-# every symbol include/mfhip.h declares (tests/test_abi.py checks the header against this list)
-EXPORTS = [
-    "mf_abi_version", "mf_last_error", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc",
-    "mf_gemm_conv", "mf_gemm_num_tiles", "mf_gemm_tile_shape", "mf_gemm_tile_table_version",
-    "mf_groupnorm", "mf_groupnorm_ws_floats", "mf_layernorm", "mf_softmax_rows", "mf_attention_bf16", "mf_attention_f16",
-    "mf_attention_f16x3", "mf_attention_f16x3_lse", "mf_attention_causal_bf16", "mf_attention_causal_f16", "mf_attention_causal_f16x3",
-    "mf_softmax_rows_causal", "mf_embed_tokens", "mf_act", "mf_sizeof_attn_bwd_desc", "mf_attention_bwd_f16x3", "mf_rowdot_heads",
-    "mf_attention_bwd_bf16", "mf_attention_bf16_lse", "mf_rowdot_heads_bf16", "mf_cast_bf16_colsum", "mf_cast_bf16_colsum_ws_floats",
-    "mf_transpose_bf16_bf16", "mf_geglu_bwd_bf16", "mf_geglu_bwd_bf16_ws_floats", "mf_rowdot_heads_cast", "mf_debug_set_wgrad_dma", "mf_zero_ranges",
-    "mf_split_halves", "mf_split_overflow", "mf_quantize_rows_fp8",
-    "mf_pack_nhwc", "mf_unpack_nchw", "mf_add", "mf_cast_bf16", "mf_geglu", "mf_timestep_embedding", "mf_silu_f32",
-    "mf_cfg_ddim_step", "mf_cfg_ddim_step_dev", "mf_cfg_combine", "mf_axpby_n", "mf_sizeof_sched_row", "mf_sched_step_dev", "mf_mse_loss", "mf_vae_sample", "mf_nearest_resize",
+# The C ABI, once: every function include/mfhip.h declares, as "<return kind>:<one kind per parameter>" (the stream included).
+# p pointer (device or host memory, an opaque handle, a C string), i int / int32_t, l int64_t, f float; returns also s (const char*) and
+# v (void); one letter per host descriptor struct (DESC_KINDS), so that a descriptor parameter takes a pointer to ITS struct only.
+# load() turns the table into argtypes / restype, so ctypes converts plain Python values and refuses the wrong ones before the library
+# is entered; program.py derives the recorder's signatures from it; tests/test_abi.py checks it against the header's prototypes in full.
+# A new entry is its prototype in mfhip.h and its line here.
+DESC_KINDS = {"G": GemmDesc, "N": GroupNormDesc, "A": AttnBwdDesc, "W": WgradDesc, "B": GroupNormBwdDesc}
+SIGNATURES = {
+    "mf_abi_version": "i:", "mf_last_error": "s:", "mf_sizeof_gemm_desc": "i:", "mf_sizeof_groupnorm_desc": "i:",
+    "mf_gemm_conv": "i:Gp", "mf_gemm_num_tiles": "i:", "mf_gemm_tile_shape": "i:ipp", "mf_gemm_tile_table_version": "i:",
+    "mf_groupnorm": "i:Np", "mf_groupnorm_ws_floats": "l:iii", "mf_layernorm": "i:pipipplifp", "mf_softmax_rows": "i:ppiliip",
+    "mf_attention_bf16": "i:plplplpliiiiifp", "mf_attention_f16": "i:plplplpliiiiifp",
+    "mf_attention_f16x3": "i:pplpplpplpliiiiifp", "mf_attention_f16x3_lse": "i:pplpplpplplpiiiiifp", "mf_attention_causal_bf16": "i:plplplpliiiiifp",
+    "mf_attention_causal_f16": "i:plplplpliiiiifp", "mf_attention_causal_f16x3": "i:pplpplpplpliiiiifp",
+    "mf_softmax_rows_causal": "i:ppiliiip", "mf_embed_tokens": "i:pppipiiiiip", "mf_act": "i:ppiilp", "mf_sizeof_attn_bwd_desc": "i:",
+    "mf_attention_bwd_f16x3": "i:Ap", "mf_rowdot_heads": "i:pppiiiilp",
+    "mf_attention_bwd_bf16": "i:Ap", "mf_attention_bf16_lse": "i:plplplplpiiiiifp", "mf_rowdot_heads_bf16": "i:pppiiiilp",
+    "mf_cast_bf16_colsum": "i:ppiliplipipp", "mf_cast_bf16_colsum_ws_floats": "l:ili",
+    "mf_transpose_bf16_bf16": "i:ppiiillllp", "mf_geglu_bwd_bf16": "i:ppplippp", "mf_geglu_bwd_bf16_ws_floats": "l:li",
+    "mf_rowdot_heads_cast": "i:ppppiiiip", "mf_debug_set_wgrad_dma": "v:i", "mf_zero_ranges": "i:pppip",
+    "mf_split_halves": "i:ppplp", "mf_split_overflow": "i:ipp", "mf_quantize_rows_fp8": "i:pipplippfp",
+    "mf_pack_nhwc": "i:pipipiiiip", "mf_unpack_nchw": "i:pilpiiip", "mf_add": "i:pipipilp", "mf_cast_bf16": "i:pplp", "mf_geglu": "i:pipilip",
+    "mf_timestep_embedding": "i:ppiiifp", "mf_silu_f32": "i:pplp",
+    "mf_cfg_ddim_step": "i:ppfppffffifplp", "mf_cfg_ddim_step_dev": "i:ppfpppiflp", "mf_cfg_combine": "i:ppfplp", "mf_axpby_n": "i:ppiplp",
+    "mf_sizeof_sched_row": "i:", "mf_sched_step_dev": "i:ppfppplp", "mf_mse_loss": "i:pppppilp", "mf_vae_sample": "i:pilppiiifp",
+    "mf_nearest_resize": "i:ppiiiiip",
     # image front-end (csrc/frontend.hip)
-    "mf_minmax_ws_floats", "mf_minmax", "mf_image_normalize", "mf_mask_keep", "mf_concat_channels", "mf_postprocess",
-    "mf_depth_normalize", "mf_select_ws_bytes", "mf_select_ranks", "mf_depth_percentile_normalize", "mf_bicubic_resize_crop",
-    "mf_bicubic_aa_resize_crop",
-    "mf_hwc_to_chw_affine",
+    "mf_minmax_ws_floats": "l:", "mf_minmax": "i:pplppp", "mf_image_normalize": "i:pplpp", "mf_mask_keep": "i:ppiilp",
+    "mf_concat_channels": "i:pppipilp", "mf_postprocess": "i:pppiilip",
+    "mf_depth_normalize": "i:ppplffipp", "mf_select_ws_bytes": "l:", "mf_select_ranks": "i:plpippp", "mf_depth_percentile_normalize": "i:pplpffippp",
+    "mf_bicubic_resize_crop": "i:ppiiiiiiiiiffp", "mf_bicubic_aa_resize_crop": "i:ppiiiiiiiiiffp", "mf_hwc_to_chw_affine": "i:ppliffp",
     # training (csrc/train.hip)
-    "mf_sizeof_wgrad_desc", "mf_conv_wgrad_ws_floats", "mf_conv_wgrad", "mf_split_pack", "mf_transpose", "mf_transpose_bf16", "mf_colsum_ws_floats", "mf_colsum",
-    "mf_sizeof_groupnorm_bwd_desc", "mf_groupnorm_bwd", "mf_groupnorm_bwd_ws_floats", "mf_groupnorm_bwd_streams", "mf_layernorm_bwd", "mf_layernorm_bwd_parts", "mf_softmax_bwd", "mf_silu_bwd", "mf_geglu_bwd",
-    "mf_zero_insert2x", "mf_sumpool2x2", "mf_mse_grad", "mf_sumsq_ws_doubles", "mf_sumsq", "mf_clip_coef", "mf_adamw",
-    # step programs (csrc/program.cpp; program.py records them)
-    "mf_memcpy2d", "mf_memset", "mf_program_load", "mf_program_destroy", "mf_program_num_buffers", "mf_program_buffer_info",
-    "mf_program_find_buffer", "mf_program_bind", "mf_program_num_calls", "mf_program_meta", "mf_program_run",
-    "mf_denoise_step_fused", "mf_unet_forward", "mf_brushnet_forward", "mf_vae_decode", "mf_vae_encode_moments",
-]
+    "mf_sizeof_wgrad_desc": "i:", "mf_conv_wgrad_ws_floats": "l:W", "mf_conv_wgrad": "i:Wp", "mf_split_pack": "i:plpliip",
+    "mf_transpose": "i:ppiiillllp", "mf_transpose_bf16": "i:ppiiillllp", "mf_colsum_ws_floats": "l:ili", "mf_colsum": "i:plpliliipp",
+    "mf_sizeof_groupnorm_bwd_desc": "i:", "mf_groupnorm_bwd": "i:Bp", "mf_groupnorm_bwd_ws_floats": "l:iiii", "mf_groupnorm_bwd_streams": "i:iiii",
+    "mf_layernorm_bwd": "i:pppppplifpp", "mf_layernorm_bwd_parts": "l:l", "mf_softmax_bwd": "i:pppliifp", "mf_silu_bwd": "i:ppplp",
+    "mf_geglu_bwd": "i:ppplip", "mf_zero_insert2x": "i:ppiiiip", "mf_sumpool2x2": "i:ppiiiip", "mf_mse_grad": "i:ppppilp",
+    "mf_sumsq_ws_doubles": "l:", "mf_sumsq": "i:plpipp", "mf_clip_coef": "i:pffppp", "mf_adamw": "i:pppplfffffipp",
+    # step programs (csrc/program.hip; program.py records them)
+    "mf_memcpy2d": "i:plplllp", "mf_memset": "i:pilp", "mf_program_load": "i:plp", "mf_program_destroy": "v:p", "mf_program_num_buffers": "i:p",
+    "mf_program_buffer_info": "i:pipppp", "mf_program_find_buffer": "i:pp", "mf_program_bind": "i:pip", "mf_program_num_calls": "i:p",
+    "mf_program_meta": "s:p", "mf_program_run": "i:pp", "mf_denoise_step_fused": "i:pppppp", "mf_unet_forward": "i:ppppipp",
+    "mf_brushnet_forward": "i:pppppip", "mf_vae_decode": "i:pppp", "mf_vae_encode_moments": "i:pppp",
+}
+EXPORTS = list(SIGNATURES)
+# (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
+_LAYOUTS = ((GemmDesc, "mf_sizeof_gemm_desc"), (GroupNormDesc, "mf_sizeof_groupnorm_desc"), (AttnBwdDesc, "mf_sizeof_attn_bwd_desc"),
+            (WgradDesc, "mf_sizeof_wgrad_desc"), (GroupNormBwdDesc, "mf_sizeof_groupnorm_bwd_desc"), (SchedRow, "mf_sizeof_sched_row"))
+_CTYPES = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "s": C.c_char_p, "v": None,
+           **{kind: C.POINTER(struct) for kind, struct in DESC_KINDS.items()}}
 
 _lib: Optional[C.CDLL] = None
 _RECORDER = None        # program.Recorder's proxy while a step program is being recorded: every launch goes through it
@@ -189,24 +213,17 @@ def load() -> C.CDLL:
             f"{path} not found: the HIP extension has not been built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` (needs hipcc). There is no CPU fallback for the MirrorFusion hot path.")
     lib = C.CDLL(path)
-    lib.mf_last_error.restype = C.c_char_p
-    lib.mf_groupnorm_ws_floats.restype = C.c_int64
-    lib.mf_groupnorm_bwd_ws_floats.restype = C.c_int64
-    lib.mf_layernorm_bwd_parts.restype = C.c_int64
-    lib.mf_layernorm_bwd_parts.argtypes = [C.c_int64]
-    for fn in ("mf_conv_wgrad_ws_floats", "mf_colsum_ws_floats", "mf_sumsq_ws_doubles", "mf_minmax_ws_floats", "mf_select_ws_bytes",
-               "mf_cast_bf16_colsum_ws_floats", "mf_geglu_bwd_bf16_ws_floats"):
-        getattr(lib, fn).restype = C.c_int64
+    for name, sig in SIGNATURES.items():      # (symbols beyond the table — a developer build's — stay untyped)
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise MfhipError(f"{path} does not export {name}, which include/mfhip.h declares: rebuild the library")
+        ret, _, params = sig.partition(":")
+        fn.restype, fn.argtypes = _CTYPES[ret], [_CTYPES[kind] for kind in params]
     if lib.mf_abi_version() != ABI_VERSION:
         raise MfhipError(f"libmfhip ABI {lib.mf_abi_version()} != binding ABI {ABI_VERSION}: rebuild the library")
-    if lib.mf_sizeof_gemm_desc() != C.sizeof(GemmDesc) or lib.mf_sizeof_groupnorm_desc() != C.sizeof(GroupNormDesc):
-        raise MfhipError("descriptor struct layout mismatch between mfhip.h and the ctypes binding")
-    if lib.mf_sizeof_attn_bwd_desc() != C.sizeof(AttnBwdDesc):
-        raise MfhipError("mf_attn_bwd_desc layout mismatch between mfhip.h and the ctypes binding")
-    if lib.mf_sizeof_wgrad_desc() != C.sizeof(WgradDesc) or lib.mf_sizeof_groupnorm_bwd_desc() != C.sizeof(GroupNormBwdDesc):
-        raise MfhipError("training descriptor struct layout mismatch between mfhip.h and the ctypes binding")
-    if lib.mf_sizeof_sched_row() != C.sizeof(SchedRow):
-        raise MfhipError("mf_sched_row layout mismatch between mfhip.h and the ctypes binding")
+    for struct, sizeof in _LAYOUTS:
+        if getattr(lib, sizeof)() != C.sizeof(struct):
+            raise MfhipError(f"{struct.__name__} layout mismatch between mfhip.h ({sizeof}) and the ctypes binding")
     _lib = lib
     return lib
 
@@ -234,6 +251,14 @@ def _stream() -> C.c_void_p:
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+def _launch(entry: str, *args) -> None:
+    """lib.<entry>(*args, current stream), raising on a non-zero return.  A tensor stands for its address (None: a null pointer); it is
+    resolved HERE, so the library object — or the Recorder's proxy in its place — only ever sees addresses, ints, floats and ctypes objects."""
+    fn = getattr(load(), entry)
+    kinds = SIGNATURES[entry][2:]         # (only a pointer parameter takes a tensor: elsewhere ctypes converts or refuses it, as it always did)
+    _check(fn(*[a.data_ptr() if k == "p" and isinstance(a, torch.Tensor) else a for a, k in zip(args, kinds)], _stream()), entry)
 
 
 def _req_cuda(*ts: Optional[torch.Tensor]) -> None:
@@ -735,7 +760,7 @@ def groupnorm(x0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, grou
     d.gamma, d.beta, d.silu = _ptr(gamma), _ptr(beta), int(silu)
     d.out, d.out_dtype = _ptr(out), dt_code(out.dtype)
     lib = load()
-    ws = scratch("gn", int(lib.mf_groupnorm_ws_floats(b, groups, c0 + c1)), x0.device)
+    ws = scratch("gn", lib.mf_groupnorm_ws_floats(b, groups, c0 + c1), x0.device)
     d.ws = ws.data_ptr()
     if stats_out is not None:
         _f32(stats_out)
@@ -756,7 +781,7 @@ def groupnorm(x0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, grou
                 d.part1, d.part1_rows = p1[0].data_ptr(), p1[1]
             if x1 is None and len(p0) > 2 and p0[2] == groups and GN_FROM_GROUPS:
                 d.grp0, d.grp0_rows = p0[0].data_ptr() + 4 * 2 * c0 * (b * hw // p0[1]), p0[1]
-    _check(lib.mf_groupnorm(C.byref(d), _stream()), "mf_groupnorm")
+    _launch("mf_groupnorm", C.byref(d))
     return out
 
 
@@ -766,9 +791,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     c = x.shape[-1]
     rows = x.numel() // c
     out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    _check(load().mf_layernorm(C.c_void_p(x.data_ptr()), dt_code(x.dtype), C.c_void_p(out.data_ptr()),
-                               dt_code(out_dtype), C.c_void_p(gamma.data_ptr()), C.c_void_p(beta.data_ptr()),
-                               C.c_int64(rows), c, C.c_float(eps), _stream()), "mf_layernorm")
+    _launch("mf_layernorm", x, dt_code(x.dtype), out, dt_code(out_dtype), gamma, beta, rows, c, eps)
     return out
 
 
@@ -778,8 +801,7 @@ def softmax_rows(scores: torch.Tensor, cols: int, out_dtype: torch.dtype) -> tor
     ld = scores.shape[-1]
     rows = scores.numel() // ld
     out = torch.empty(scores.shape, dtype=out_dtype, device=scores.device)
-    _check(load().mf_softmax_rows(C.c_void_p(scores.data_ptr()), C.c_void_p(out.data_ptr()), dt_code(out_dtype),
-                                  C.c_int64(rows), cols, ld, _stream()), "mf_softmax_rows")
+    _launch("mf_softmax_rows", scores, out, dt_code(out_dtype), rows, cols, ld)
     return out
 
 
@@ -789,8 +811,7 @@ def softmax_rows_causal(scores: torch.Tensor, cols: int, sq: int, out_dtype: tor
     ld = scores.shape[-1]
     rows = scores.numel() // ld
     out = torch.empty(scores.shape, dtype=out_dtype, device=scores.device)
-    _check(load().mf_softmax_rows_causal(C.c_void_p(scores.data_ptr()), C.c_void_p(out.data_ptr()), dt_code(out_dtype),
-                                         C.c_int64(rows), cols, ld, sq, _stream()), "mf_softmax_rows_causal")
+    _launch("mf_softmax_rows_causal", scores, out, dt_code(out_dtype), rows, cols, ld, sq)
     return out
 
 
@@ -811,9 +832,7 @@ def embed_tokens(ids: torch.Tensor, token_table: torch.Tensor, pos_table: torch.
             or not token_table.is_contiguous() or not pos_table.is_contiguous()):
         raise MfhipError("embed_tokens: contiguous tables of one dtype, [vocab, hidden] and [>= seq, hidden]")
     out = torch.empty(b, s, hidden, dtype=out_dtype, device=token_table.device)
-    _check(load().mf_embed_tokens(C.c_void_p(ids.data_ptr()), C.c_void_p(token_table.data_ptr()), C.c_void_p(pos_table.data_ptr()),
-                                  dt_code(token_table.dtype), C.c_void_p(out.data_ptr()), dt_code(out_dtype), b, s, hidden, vocab,
-                                  _stream()), "mf_embed_tokens")
+    _launch("mf_embed_tokens", ids, token_table, pos_table, dt_code(token_table.dtype), out, dt_code(out_dtype), b, s, hidden, vocab)
     return out
 
 
@@ -826,8 +845,7 @@ def act(x: torch.Tensor, kind: int, out: Optional[torch.Tensor] = None) -> torch
         out = torch.empty_like(x)
     elif out.dtype != x.dtype or out.shape != x.shape or not out.is_contiguous():
         raise MfhipError("act: out has x's dtype and shape")
-    _check(load().mf_act(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), dt_code(x.dtype), kind, C.c_int64(x.numel()),
-                         _stream()), "mf_act")
+    _launch("mf_act", x, out, dt_code(x.dtype), kind, x.numel())
     return out
 
 
@@ -841,9 +859,7 @@ def attention_bf16(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torc
         if lse is not None or not (q.dtype == k.dtype == vt.dtype == out.dtype) or q.dtype not in (torch.bfloat16, torch.float16):
             raise MfhipError("attention_bf16(causal=True): bf16 or fp16 q / k / vt / out of one dtype and no lse")
         fn = "mf_attention_causal_f16" if q.dtype == torch.float16 else "mf_attention_causal_bf16"
-        _check(getattr(load(), fn)(C.c_void_p(q.data_ptr()), C.c_int64(ldq), C.c_void_p(k.data_ptr()), C.c_int64(ldk),
-                                   C.c_void_p(vt.data_ptr()), C.c_int64(ldvt), C.c_void_p(out.data_ptr()),
-                                   C.c_int64(ldo), batch, heads, sq, skv, head_dim, C.c_float(scale), _stream()), fn)
+        _launch(fn, q, ldq, k, ldk, vt, ldvt, out, ldo, batch, heads, sq, skv, head_dim, scale)
         return out
     if PROFILE is not None:               # bench.py's FLOP census (no timing here: the GEMM family is the timed one)
         global PROFILE_ATTN_FLOPS
@@ -851,24 +867,15 @@ def attention_bf16(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torc
     if q.dtype == torch.float16:          # the fp16 storage mode: the same kernel on the f16 MFMA forms (inference: no row statistics)
         if lse is not None or not (k.dtype == vt.dtype == out.dtype == torch.float16):
             raise MfhipError("attention_bf16: fp16 operands take fp16 k / vt / out and no lse")
-        _check(load().mf_attention_f16(C.c_void_p(q.data_ptr()), C.c_int64(ldq), C.c_void_p(k.data_ptr()), C.c_int64(ldk),
-                                       C.c_void_p(vt.data_ptr()), C.c_int64(ldvt), C.c_void_p(out.data_ptr()),
-                                       C.c_int64(ldo), batch, heads, sq, skv, head_dim, C.c_float(scale), _stream()),
-               "mf_attention_f16")
+        _launch("mf_attention_f16", q, ldq, k, ldk, vt, ldvt, out, ldo, batch, heads, sq, skv, head_dim, scale)
         return out
     if lse is None:
-        _check(load().mf_attention_bf16(C.c_void_p(q.data_ptr()), C.c_int64(ldq), C.c_void_p(k.data_ptr()), C.c_int64(ldk),
-                                        C.c_void_p(vt.data_ptr()), C.c_int64(ldvt), C.c_void_p(out.data_ptr()),
-                                        C.c_int64(ldo), batch, heads, sq, skv, head_dim, C.c_float(scale), _stream()),
-               "mf_attention_bf16")
+        _launch("mf_attention_bf16", q, ldq, k, ldk, vt, ldvt, out, ldo, batch, heads, sq, skv, head_dim, scale)
         return out
     _f32(lse)
     if lse.numel() != batch * heads * sq or not lse.is_contiguous():
         raise MfhipError("attention_bf16: lse is a contiguous [batch, heads, sq] tensor")
-    _check(load().mf_attention_bf16_lse(C.c_void_p(q.data_ptr()), C.c_int64(ldq), C.c_void_p(k.data_ptr()), C.c_int64(ldk),
-                                        C.c_void_p(vt.data_ptr()), C.c_int64(ldvt), C.c_void_p(out.data_ptr()), C.c_int64(ldo),
-                                        C.c_void_p(lse.data_ptr()), batch, heads, sq, skv, head_dim, C.c_float(scale), _stream()),
-           "mf_attention_bf16_lse")
+    _launch("mf_attention_bf16_lse", q, ldq, k, ldk, vt, ldvt, out, ldo, lse, batch, heads, sq, skv, head_dim, scale)
     return out
 
 
@@ -883,9 +890,7 @@ def quantize_rows_fp8(x: torch.Tensor, norm=None, eps: float = 1e-5):
     q = torch.empty(x.shape, dtype=FP8, device=x.device)
     sc = torch.empty(rows, dtype=torch.float32, device=x.device)
     g, b = norm if norm is not None else (None, None)
-    _check(load().mf_quantize_rows_fp8(C.c_void_p(x.data_ptr()), dt_code(x.dtype), C.c_void_p(q.data_ptr()), C.c_void_p(sc.data_ptr()),
-                                       C.c_int64(rows), c, C.c_void_p(_ptr(g)), C.c_void_p(_ptr(b)), C.c_float(eps), _stream()),
-           "mf_quantize_rows_fp8")
+    _launch("mf_quantize_rows_fp8", x, dt_code(x.dtype), q, sc, rows, c, g, b, eps)
     return q, sc
 
 
@@ -893,7 +898,7 @@ def split_overflow(reset: bool = True) -> int:
     """Bit mask of the fp16 split precision's range-guard flags (0 = every f16x3 operand since the last reset was inside
     |x| <= 65504; bit 0 GEMM / conv, bit 1 attention operands, bit 2 weight gradients).  Synchronises the current stream."""
     raised = C.c_int32(0)
-    _check(load().mf_split_overflow(int(reset), C.byref(raised), _stream()), "mf_split_overflow")
+    _launch("mf_split_overflow", int(reset), C.byref(raised))
     return int(raised.value)
 
 
@@ -920,8 +925,7 @@ def split_pack(w: torch.Tensor, code: int, out: Optional[torch.Tensor] = None):
         out = torch.empty(rows, 2 * kp, dtype=half, device=w.device)
     elif out.dtype != half or out.numel() != rows * 2 * kp or not out.is_contiguous():
         raise MfhipError("split_pack: out must be a contiguous 16-bit [rows, 2 * kp] tensor")
-    _check(load().mf_split_pack(C.c_void_p(w.data_ptr()), C.c_int64(w.stride(0)), C.c_void_p(out.data_ptr()), C.c_int64(rows), k, code,
-                                _stream()), "mf_split_pack")
+    _launch("mf_split_pack", w, w.stride(0), out, rows, k, code)
     return out, kp
 
 
@@ -932,8 +936,7 @@ def split_halves(x: torch.Tensor):
         raise MfhipError("split_halves: contiguous fp32 input")
     hi = torch.empty(x.shape, dtype=torch.float16, device=x.device)
     lo = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-    _check(load().mf_split_halves(C.c_void_p(x.data_ptr()), C.c_void_p(hi.data_ptr()), C.c_void_p(lo.data_ptr()),
-                                  C.c_int64(x.numel()), _stream()), "mf_split_halves")
+    _launch("mf_split_halves", x, hi, lo, x.numel())
     return hi, lo
 
 
@@ -945,17 +948,9 @@ def attention_f16x3(q, k, vt, out: torch.Tensor, *, ldq: int, ldk: int, ldvt: in
     if causal:
         if lse is not None:
             raise MfhipError("attention_f16x3(causal=True): inference only, no lse")
-        _check(load().mf_attention_causal_f16x3(C.c_void_p(q[0].data_ptr()), C.c_void_p(q[1].data_ptr()), C.c_int64(ldq),
-                                                C.c_void_p(k[0].data_ptr()), C.c_void_p(k[1].data_ptr()), C.c_int64(ldk),
-                                                C.c_void_p(vt[0].data_ptr()), C.c_void_p(vt[1].data_ptr()), C.c_int64(ldvt),
-                                                C.c_void_p(out.data_ptr()), C.c_int64(ldo), batch, heads, sq, skv, head_dim,
-                                                C.c_float(scale), _stream()), "mf_attention_causal_f16x3")
+        _launch("mf_attention_causal_f16x3", q[0], q[1], ldq, k[0], k[1], ldk, vt[0], vt[1], ldvt, out, ldo, batch, heads, sq, skv, head_dim, scale)
         return out
-    _check(load().mf_attention_f16x3_lse(C.c_void_p(q[0].data_ptr()), C.c_void_p(q[1].data_ptr()), C.c_int64(ldq),
-                                         C.c_void_p(k[0].data_ptr()), C.c_void_p(k[1].data_ptr()), C.c_int64(ldk),
-                                         C.c_void_p(vt[0].data_ptr()), C.c_void_p(vt[1].data_ptr()), C.c_int64(ldvt),
-                                         C.c_void_p(out.data_ptr()), C.c_int64(ldo), C.c_void_p(_ptr(lse)), batch, heads, sq, skv, head_dim,
-                                         C.c_float(scale), _stream()), "mf_attention_f16x3")
+    _launch("mf_attention_f16x3_lse", q[0], q[1], ldq, k[0], k[1], ldk, vt[0], vt[1], ldvt, out, ldo, lse, batch, heads, sq, skv, head_dim, scale)
     return out
 
 
@@ -969,12 +964,10 @@ def rowdot_heads(a: torch.Tensor, b: torch.Tensor, heads: int) -> torch.Tensor:
         _req_cuda(b)
         if b.shape != a.shape or not (a.is_contiguous() and b.is_contiguous()):
             raise MfhipError("rowdot_heads: contiguous operands of one shape")
-        _check(load().mf_rowdot_heads_bf16(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(out.data_ptr()), bsz, s, heads,
-                                           c // heads, C.c_int64(c), _stream()), "mf_rowdot_heads_bf16")
+        _launch("mf_rowdot_heads_bf16", a, b, out, bsz, s, heads, c // heads, c)
         return out
     _f32(b)
-    _check(load().mf_rowdot_heads(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(out.data_ptr()), bsz, s, heads, c // heads,
-                                  C.c_int64(c), _stream()), "mf_rowdot_heads")
+    _launch("mf_rowdot_heads", a, b, out, bsz, s, heads, c // heads, c)
     return out
 
 
@@ -987,8 +980,7 @@ def rowdot_heads_cast(a: torch.Tensor, b16: torch.Tensor, heads: int):
         raise MfhipError("rowdot_heads_cast: contiguous fp32 / bf16 operands of one shape")
     out = torch.empty(bsz, heads, s, dtype=torch.float32, device=a.device)
     a16 = torch.empty_like(b16)
-    _check(load().mf_rowdot_heads_cast(C.c_void_p(a.data_ptr()), C.c_void_p(b16.data_ptr()), C.c_void_p(a16.data_ptr()), C.c_void_p(out.data_ptr()),
-                                       bsz, s, heads, c // heads, _stream()), "mf_rowdot_heads_cast")
+    _launch("mf_rowdot_heads_cast", a, b16, a16, out, bsz, s, heads, c // heads)
     return out, a16
 
 
@@ -1010,7 +1002,7 @@ def attention_bwd_f16x3(q, k, v, do, qt, kt, dot, lse: torch.Tensor, dd: torch.T
     d.dq, d.dk, d.dv, d.ldo = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), c
     d.batch, d.heads, d.sq, d.skv, d.head_dim, d.scale = b, heads, sq, skv, c // heads, scale
     d.out_dtype = dt_code(dq.dtype)
-    _check(getattr(load(), _entry)(C.byref(d), _stream()), _entry)
+    _launch(_entry, C.byref(d))
 
 
 def attention_bwd_bf16(q, k, v, do, qt, kt, dot, lse: torch.Tensor, dd: torch.Tensor, dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor, *,
@@ -1035,9 +1027,7 @@ def pack_nhwc(src0: torch.Tensor, src1: Optional[torch.Tensor], c_pad: int, out_
     if src1 is not None:
         src1 = src1.contiguous().float()
     out = torch.empty(b, h, w, c_pad, dtype=out_dtype, device=src0.device)
-    _check(load().mf_pack_nhwc(C.c_void_p(src0.data_ptr()), c0, C.c_void_p(_ptr(src1)), c1,
-                               C.c_void_p(out.data_ptr()), dt_code(out_dtype), c_pad, b, h * w, _stream()),
-           "mf_pack_nhwc")
+    _launch("mf_pack_nhwc", src0, c0, src1, c1, out, dt_code(out_dtype), c_pad, b, h * w)
     return out
 
 
@@ -1046,8 +1036,7 @@ def unpack_nchw(src: torch.Tensor, c: int) -> torch.Tensor:
     _req_cuda(src)
     b, h, w, ld = src.shape
     out = torch.empty(b, c, h, w, dtype=torch.float32, device=src.device)
-    _check(load().mf_unpack_nchw(C.c_void_p(src.data_ptr()), dt_code(src.dtype), C.c_int64(ld),
-                                 C.c_void_p(out.data_ptr()), c, b, h * w, _stream()), "mf_unpack_nchw")
+    _launch("mf_unpack_nchw", src, dt_code(src.dtype), ld, out, c, b, h * w)
     return out
 
 
@@ -1059,8 +1048,7 @@ def add(a: torch.Tensor, b: torch.Tensor, out_dtype: torch.dtype, out: Optional[
         out = torch.empty(a.shape, dtype=out_dtype, device=a.device)
     elif out.shape != a.shape or out.dtype != out_dtype or not out.is_contiguous():
         raise MfhipError("mf_add: `out` must be a contiguous tensor of the operands' shape and the output dtype")
-    _check(load().mf_add(C.c_void_p(a.data_ptr()), dt_code(a.dtype), C.c_void_p(b.data_ptr()), dt_code(b.dtype),
-                         C.c_void_p(out.data_ptr()), dt_code(out_dtype), C.c_int64(a.numel()), _stream()), "mf_add")
+    _launch("mf_add", a, dt_code(a.dtype), b, dt_code(b.dtype), out, dt_code(out_dtype), a.numel())
     return out
 
 
@@ -1073,7 +1061,7 @@ def cast_bf16(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tens
         out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     elif out.dtype != torch.bfloat16 or out.numel() != x.numel() or not out.is_contiguous():
         raise MfhipError("cast_bf16: `out` must be a contiguous bf16 tensor of the same size")
-    _check(load().mf_cast_bf16(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), C.c_int64(x.numel()), _stream()), "mf_cast_bf16")
+    _launch("mf_cast_bf16", x, out, x.numel())
     return out
 
 
@@ -1087,10 +1075,8 @@ def cast_bf16_colsum(x: torch.Tensor, n: int, *, segs: int = 1, seg_out: Optiona
     rps = x.numel() // n // segs
     out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     lib = load()
-    ws = scratch("cast_colsum", int(lib.mf_cast_bf16_colsum_ws_floats(segs, C.c_int64(rps), n)), x.device)
-    _check(lib.mf_cast_bf16_colsum(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), segs, C.c_int64(rps), n, C.c_void_p(_ptr(seg_out)),
-                                   C.c_int64(n if ldo is None else ldo), 1, C.c_void_p(_ptr(tot_out)), 1, C.c_void_p(ws.data_ptr()), _stream()),
-           "mf_cast_bf16_colsum")
+    ws = scratch("cast_colsum", lib.mf_cast_bf16_colsum_ws_floats(segs, rps, n), x.device)
+    _launch("mf_cast_bf16_colsum", x, out, segs, rps, n, seg_out, n if ldo is None else ldo, 1, tot_out, 1, ws)
     return out
 
 
@@ -1099,8 +1085,7 @@ def geglu(h: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
     c = h.shape[-1] // 2
     rows = h.numel() // (2 * c)
     out = torch.empty(*h.shape[:-1], c, dtype=out_dtype, device=h.device)
-    _check(load().mf_geglu(C.c_void_p(h.data_ptr()), dt_code(h.dtype), C.c_void_p(out.data_ptr()), dt_code(out_dtype),
-                           C.c_int64(rows), c, _stream()), "mf_geglu")
+    _launch("mf_geglu", h, dt_code(h.dtype), out, dt_code(out_dtype), rows, c)
     return out
 
 
@@ -1108,17 +1093,14 @@ def timestep_embedding(t: torch.Tensor, dim: int, flip_sin_to_cos: bool, freq_sh
     _req_cuda(t)
     t = t.float().contiguous()
     out = torch.empty(t.numel(), dim, dtype=torch.float32, device=t.device)
-    _check(load().mf_timestep_embedding(C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()), t.numel(), dim,
-                                        int(flip_sin_to_cos), C.c_float(freq_shift), _stream()),
-           "mf_timestep_embedding")
+    _launch("mf_timestep_embedding", t, out, t.numel(), dim, int(flip_sin_to_cos), freq_shift)
     return out
 
 
 def silu_f32(x: torch.Tensor) -> torch.Tensor:
     _req_cuda(x)
     out = torch.empty_like(x)
-    _check(load().mf_silu_f32(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), C.c_int64(x.numel()), _stream()),
-           "mf_silu_f32")
+    _launch("mf_silu_f32", x, out, x.numel())
     return out
 
 
@@ -1127,11 +1109,7 @@ def cfg_ddim_step(eps_u: torch.Tensor, eps_c: Optional[torch.Tensor], g: float, 
                   pred_type: int = 0, clip: float = 0.0) -> torch.Tensor:
     _req_cuda(eps_u, eps_c, x, eps_out)
     xp = torch.empty_like(x)
-    _check(load().mf_cfg_ddim_step(C.c_void_p(eps_u.data_ptr()), C.c_void_p(_ptr(eps_c)), C.c_float(g),
-                                   C.c_void_p(x.data_ptr()), C.c_void_p(xp.data_ptr()), C.c_float(sqrt_at),
-                                   C.c_float(sqrt_1m_at), C.c_float(sqrt_ap), C.c_float(dir_coef), pred_type,
-                                   C.c_float(clip), C.c_void_p(_ptr(eps_out)), C.c_int64(x.numel()), _stream()),
-           "mf_cfg_ddim_step")
+    _launch("mf_cfg_ddim_step", eps_u, eps_c, g, x, xp, sqrt_at, sqrt_1m_at, sqrt_ap, dir_coef, pred_type, clip, eps_out, x.numel())
     return xp
 
 
@@ -1140,18 +1118,14 @@ def cfg_ddim_step_dev(eps_u: torch.Tensor, eps_c: Optional[torch.Tensor], g: flo
     """DDIM update with device-resident coefficients (graph replay); `out` may be `x` itself (in place)."""
     _req_cuda(eps_u, eps_c, x, coef4, out)
     xp = out if out is not None else torch.empty_like(x)
-    _check(load().mf_cfg_ddim_step_dev(C.c_void_p(eps_u.data_ptr()), C.c_void_p(_ptr(eps_c)), C.c_float(g),
-                                       C.c_void_p(x.data_ptr()), C.c_void_p(xp.data_ptr()),
-                                       C.c_void_p(coef4.data_ptr()), pred_type, C.c_float(clip),
-                                       C.c_int64(x.numel()), _stream()), "mf_cfg_ddim_step_dev")
+    _launch("mf_cfg_ddim_step_dev", eps_u, eps_c, g, x, xp, coef4, pred_type, clip, x.numel())
     return xp
 
 
 def cfg_combine(eps_u: torch.Tensor, eps_c: torch.Tensor, g: float) -> torch.Tensor:
     _req_cuda(eps_u, eps_c)
     out = torch.empty_like(eps_u)
-    _check(load().mf_cfg_combine(C.c_void_p(eps_u.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_float(g),
-                                 C.c_void_p(out.data_ptr()), C.c_int64(eps_u.numel()), _stream()), "mf_cfg_combine")
+    _launch("mf_cfg_combine", eps_u, eps_c, g, out, eps_u.numel())
     return out
 
 
@@ -1163,7 +1137,7 @@ def axpby_n(xs, coefs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     cf = (C.c_float * n)(*[float(c) for c in coefs])
     if out is None:
         out = torch.empty_like(xs[0])
-    _check(load().mf_axpby_n(arr, cf, n, C.c_void_p(out.data_ptr()), C.c_int64(out.numel()), _stream()), "mf_axpby_n")
+    _launch("mf_axpby_n", arr, cf, n, out, out.numel())
     return out
 
 
@@ -1179,8 +1153,7 @@ def sched_step_dev(eps_u: torch.Tensor, eps_c: torch.Tensor, g: float, latents: 
     for t in (eps_u, eps_c, latents, state, row):
         if t is not None and (not t.is_contiguous() or (t.dtype != torch.float32 and t is not row)):
             raise MfhipError("sched_step_dev: contiguous fp32 tensors needed")
-    _check(load().mf_sched_step_dev(C.c_void_p(eps_u.data_ptr()), C.c_void_p(eps_c.data_ptr()), C.c_float(g), C.c_void_p(latents.data_ptr()),
-                                    C.c_void_p(_ptr(state)), C.c_void_p(row.data_ptr()), C.c_int64(n), _stream()), "mf_sched_step_dev")
+    _launch("mf_sched_step_dev", eps_u, eps_c, g, latents, state, row, n)
     return latents
 
 
@@ -1198,10 +1171,7 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor, weights: Optional[torch.T
         w = weights.to(pred.device, torch.float32).contiguous()
         if w.numel() != rows:
             raise ValueError("mse_loss: one weight per sample")
-    _check(load().mf_mse_loss(C.c_void_p(pred.data_ptr()), C.c_void_p(target.data_ptr()),
-                              C.c_void_p(w.data_ptr() if w is not None else None), C.c_void_p(per.data_ptr()),
-                              C.c_void_p(loss.data_ptr()), C.c_int32(rows), C.c_int64(pred.numel() // rows), _stream()),
-           "mf_mse_loss")
+    _launch("mf_mse_loss", pred, target, w, per, loss, rows, pred.numel() // rows)
     return loss, per
 
 
@@ -1211,9 +1181,7 @@ def vae_sample(moments: torch.Tensor, noise: torch.Tensor, c: int, scaling: floa
     b, h, w, ld = moments.shape
     z = torch.empty(b, c, h, w, dtype=torch.float32, device=moments.device)
     noise = noise.float().contiguous()
-    _check(load().mf_vae_sample(C.c_void_p(moments.data_ptr()), dt_code(moments.dtype), C.c_int64(ld),
-                                C.c_void_p(noise.data_ptr()), C.c_void_p(z.data_ptr()), c, b, h * w,
-                                C.c_float(scaling), _stream()), "mf_vae_sample")
+    _launch("mf_vae_sample", moments, dt_code(moments.dtype), ld, noise, z, c, b, h * w, scaling)
     return z
 
 
@@ -1223,8 +1191,7 @@ def nearest_resize(src: torch.Tensor, h_out: int, w_out: int) -> torch.Tensor:
     b, c, h, w = src.shape
     src = src.float().contiguous()
     out = torch.empty(b, c, h_out, w_out, dtype=torch.float32, device=src.device)
-    _check(load().mf_nearest_resize(C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()), b * c, h, w, h_out, w_out,
-                                    _stream()), "mf_nearest_resize")
+    _launch("mf_nearest_resize", src, out, b * c, h, w, h_out, w_out)
     return out
 
 
@@ -1255,7 +1222,7 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, code: int
     d.accumulate, d.splitm = int(accumulate), 0
     ws = scratch("wgrad", WGRAD_WS_FLOATS, x.device)
     d.ws, d.ws_floats = ws.data_ptr(), ws.numel()
-    _check(load().mf_conv_wgrad(C.byref(d), _stream()), "mf_conv_wgrad")
+    _launch("mf_conv_wgrad", C.byref(d))
 
 
 def zero_ranges(base: torch.Tensor, offs: torch.Tensor, lens: torch.Tensor) -> None:
@@ -1264,8 +1231,7 @@ def zero_ranges(base: torch.Tensor, offs: torch.Tensor, lens: torch.Tensor) -> N
     _req_cuda(offs, lens)
     if offs.dtype != torch.int64 or lens.dtype != torch.int64 or offs.numel() != lens.numel() or not (offs.is_contiguous() and lens.is_contiguous()):
         raise MfhipError("zero_ranges: two contiguous int64 device tensors of one length")
-    _check(load().mf_zero_ranges(C.c_void_p(base.data_ptr()), C.c_void_p(offs.data_ptr()), C.c_void_p(lens.data_ptr()), offs.numel(), _stream()),
-           "mf_zero_ranges")
+    _launch("mf_zero_ranges", base, offs, lens, offs.numel())
 
 
 def set_wgrad_dma(on: bool) -> None:
@@ -1286,20 +1252,17 @@ def transpose(x: torch.Tensor, rows: int, cols: int, *, nz: int = 1, ldx: Option
         _req_cuda(x, out)
         if out is None or out.dtype != torch.bfloat16 or y_offset:
             raise MfhipError("transpose: a bf16 input takes a bf16 `out`")
-        _check(load().mf_transpose_bf16_bf16(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), nz, rows, cols, C.c_int64(ldx), C.c_int64(ldy),
-                                             C.c_int64(zsx), C.c_int64(zsy), _stream()), "mf_transpose_bf16_bf16")
+        _launch("mf_transpose_bf16_bf16", x, out, nz, rows, cols, ldx, ldy, zsx, zsy)
         return out
     if out is not None and out.dtype == torch.bfloat16:
         _f32(x)
         _req_cuda(out)
-        _check(load().mf_transpose_bf16(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr() + 2 * y_offset), nz, rows, cols, C.c_int64(ldx),
-                                        C.c_int64(ldy), C.c_int64(zsx), C.c_int64(zsy), _stream()), "mf_transpose_bf16")
+        _launch("mf_transpose_bf16", x, out.data_ptr() + 2 * y_offset, nz, rows, cols, ldx, ldy, zsx, zsy)
         return out
     _f32(x, out)
     if out is None:
         out = torch.empty(nz, cols, ldy, dtype=torch.float32, device=x.device)
-    _check(load().mf_transpose(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr() + 4 * y_offset), nz, rows, cols, C.c_int64(ldx),
-                               C.c_int64(ldy), C.c_int64(zsx), C.c_int64(zsy), _stream()), "mf_transpose")
+    _launch("mf_transpose", x, out.data_ptr() + 4 * y_offset, nz, rows, cols, ldx, ldy, zsx, zsy)
     return out
 
 
@@ -1311,9 +1274,8 @@ def colsum(x: torch.Tensor, n: int, *, segs: int = 1, rows_per_seg: Optional[int
     if out is None:
         out = torch.empty(segs, n, dtype=torch.float32, device=x.device)
     lib = load()
-    ws = scratch("colsum", int(lib.mf_colsum_ws_floats(segs, C.c_int64(rows_per_seg), n)), x.device)
-    _check(lib.mf_colsum(C.c_void_p(x.data_ptr()), C.c_int64(ldx), C.c_void_p(out.data_ptr()), C.c_int64(n if ldo is None else ldo), segs,
-                         C.c_int64(rows_per_seg), n, int(accumulate), C.c_void_p(ws.data_ptr()), _stream()), "mf_colsum")
+    ws = scratch("colsum", lib.mf_colsum_ws_floats(segs, rows_per_seg, n), x.device)
+    _launch("mf_colsum", x, ldx, out, n if ldo is None else ldo, segs, rows_per_seg, n, int(accumulate), ws)
     return out
 
 
@@ -1353,8 +1315,8 @@ def groupnorm_bwd(x0: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, beta:
             raise MfhipError("groupnorm_bwd: stats is a contiguous [batch, groups, 2] tensor")
         d.stats_in = stats.data_ptr()
     if streaming:
-        d.ws = _ptr(scratch("gn_bwd", int(load().mf_groupnorm_bwd_ws_floats(b, hw, c0 + c1, groups)), x0.device))
-    _check(load().mf_groupnorm_bwd(C.byref(d), _stream()), "mf_groupnorm_bwd")
+        d.ws = _ptr(scratch("gn_bwd", load().mf_groupnorm_bwd_ws_floats(b, hw, c0 + c1, groups), x0.device))
+    _launch("mf_groupnorm_bwd", C.byref(d))
     return dx0, dx1, dg, db
 
 
@@ -1367,12 +1329,10 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, eps: f
     c = x.shape[-1]
     rows = x.numel() // c
     dx = torch.empty_like(x)
-    nb = int(load().mf_layernorm_bwd_parts(rows))
+    nb = load().mf_layernorm_bwd_parts(rows)
     dg = torch.empty(nb, c, dtype=torch.float32, device=x.device) if want_param_grads else None
     db = torch.empty_like(dg) if want_param_grads else None
-    _check(load().mf_layernorm_bwd(C.c_void_p(x.data_ptr()), C.c_void_p(dy.data_ptr()), C.c_void_p(gamma.data_ptr()),
-                                   C.c_void_p(dx.data_ptr()), C.c_void_p(_ptr(dg)), C.c_void_p(_ptr(db)), C.c_int64(rows), c,
-                                   C.c_float(eps), C.c_void_p(_ptr(add)), _stream()), "mf_layernorm_bwd")
+    _launch("mf_layernorm_bwd", x, dy, gamma, dx, dg, db, rows, c, eps, add)
     return dx, dg, db
 
 
@@ -1380,16 +1340,14 @@ def softmax_bwd(p: torch.Tensor, dp: torch.Tensor, cols: int, scale: float) -> t
     _f32(p, dp)
     ld = p.shape[-1]
     ds = torch.empty_like(p)
-    _check(load().mf_softmax_bwd(C.c_void_p(p.data_ptr()), C.c_void_p(dp.data_ptr()), C.c_void_p(ds.data_ptr()),
-                                 C.c_int64(p.numel() // ld), cols, ld, C.c_float(scale), _stream()), "mf_softmax_bwd")
+    _launch("mf_softmax_bwd", p, dp, ds, p.numel() // ld, cols, ld, scale)
     return ds
 
 
 def silu_bwd(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     _f32(x, dy)
     dx = torch.empty_like(x)
-    _check(load().mf_silu_bwd(C.c_void_p(x.data_ptr()), C.c_void_p(dy.data_ptr()), C.c_void_p(dx.data_ptr()), C.c_int64(x.numel()),
-                              _stream()), "mf_silu_bwd")
+    _launch("mf_silu_bwd", x, dy, dx, x.numel())
     return dx
 
 
@@ -1397,8 +1355,7 @@ def geglu_bwd(h: torch.Tensor, dout: torch.Tensor) -> torch.Tensor:
     _f32(h, dout)
     c = h.shape[-1] // 2
     dh = torch.empty_like(h)
-    _check(load().mf_geglu_bwd(C.c_void_p(h.data_ptr()), C.c_void_p(dout.data_ptr()), C.c_void_p(dh.data_ptr()),
-                               C.c_int64(h.numel() // (2 * c)), c, _stream()), "mf_geglu_bwd")
+    _launch("mf_geglu_bwd", h, dout, dh, h.numel() // (2 * c), c)
     return dh
 
 
@@ -1412,9 +1369,8 @@ def geglu_bwd_bf16(h16: torch.Tensor, dout: torch.Tensor, bias_grad: Optional[to
         raise MfhipError("geglu_bwd_bf16: contiguous bf16 [rows, 2c] pre-activation and fp32 [rows, c] gradient")
     dh = torch.empty_like(h16)
     lib = load()
-    ws = scratch("geglu_bwd", int(lib.mf_geglu_bwd_bf16_ws_floats(C.c_int64(rows), c)), h16.device) if bias_grad is not None else None
-    _check(lib.mf_geglu_bwd_bf16(C.c_void_p(h16.data_ptr()), C.c_void_p(dout.data_ptr()), C.c_void_p(dh.data_ptr()), C.c_int64(rows), c,
-                                 C.c_void_p(_ptr(bias_grad)), C.c_void_p(_ptr(ws)), _stream()), "mf_geglu_bwd_bf16")
+    ws = scratch("geglu_bwd", lib.mf_geglu_bwd_bf16_ws_floats(rows, c), h16.device) if bias_grad is not None else None
+    _launch("mf_geglu_bwd_bf16", h16, dout, dh, rows, c, bias_grad, ws)
     return dh
 
 
@@ -1422,7 +1378,7 @@ def zero_insert2x(x: torch.Tensor) -> torch.Tensor:
     _f32(x)
     b, h, w, c = x.shape
     y = torch.empty(b, 2 * h, 2 * w, c, dtype=torch.float32, device=x.device)
-    _check(load().mf_zero_insert2x(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), b, h, w, c, _stream()), "mf_zero_insert2x")
+    _launch("mf_zero_insert2x", x, y, b, h, w, c)
     return y
 
 
@@ -1430,7 +1386,7 @@ def sumpool2x2(x: torch.Tensor) -> torch.Tensor:
     _f32(x)
     b, h2, w2, c = x.shape
     y = torch.empty(b, h2 // 2, w2 // 2, c, dtype=torch.float32, device=x.device)
-    _check(load().mf_sumpool2x2(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), b, h2 // 2, w2 // 2, c, _stream()), "mf_sumpool2x2")
+    _launch("mf_sumpool2x2", x, y, b, h2 // 2, w2 // 2, c)
     return y
 
 
@@ -1438,8 +1394,7 @@ def mse_grad(pred: torch.Tensor, target: torch.Tensor, weights: Optional[torch.T
     _f32(pred, target, weights)
     rows = pred.shape[0]
     d = torch.empty_like(pred)
-    _check(load().mf_mse_grad(C.c_void_p(pred.data_ptr()), C.c_void_p(target.data_ptr()), C.c_void_p(_ptr(weights)),
-                              C.c_void_p(d.data_ptr()), rows, C.c_int64(pred.numel() // rows), _stream()), "mf_mse_grad")
+    _launch("mf_mse_grad", pred, target, weights, d, rows, pred.numel() // rows)
     return d
 
 
@@ -1450,38 +1405,33 @@ def sumsq(x: torch.Tensor, out: torch.Tensor, accumulate: bool = False) -> torch
     key = ("sumsq", torch.device(x.device).index, torch.cuda.current_stream(x.device).cuda_stream)
     ws = _scratch.get(key)
     if ws is None:
-        ws = torch.empty(int(lib.mf_sumsq_ws_doubles()), dtype=torch.float64, device=x.device)
+        ws = torch.empty(lib.mf_sumsq_ws_doubles(), dtype=torch.float64, device=x.device)
         _scratch[key] = ws
-    _check(lib.mf_sumsq(C.c_void_p(x.data_ptr()), C.c_int64(x.numel()), C.c_void_p(out.data_ptr()), int(accumulate),
-                        C.c_void_p(ws.data_ptr()), _stream()), "mf_sumsq")
+    _launch("mf_sumsq", x, x.numel(), out, int(accumulate), ws)
     return out
 
 
 def clip_coef(sumsq_t: torch.Tensor, max_norm: float, coef: torch.Tensor, norm_out: Optional[torch.Tensor] = None,
               unscale: float = 1.0) -> None:
-    _check(load().mf_clip_coef(C.c_void_p(sumsq_t.data_ptr()), C.c_float(max_norm), C.c_float(unscale), C.c_void_p(coef.data_ptr()),
-                               C.c_void_p(_ptr(norm_out)), _stream()), "mf_clip_coef")
+    _launch("mf_clip_coef", sumsq_t, max_norm, unscale, coef, norm_out)
 
 
 def adamw(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
           weight_decay: float = 1e-2, step: int, grad_scale: Optional[torch.Tensor] = None) -> None:
     _f32(w, g, m, v, grad_scale)
-    _check(load().mf_adamw(C.c_void_p(w.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()),
-                           C.c_int64(w.numel()), C.c_float(lr), C.c_float(betas[0]), C.c_float(betas[1]), C.c_float(eps),
-                           C.c_float(weight_decay), step, C.c_void_p(_ptr(grad_scale)), _stream()), "mf_adamw")
+    _launch("mf_adamw", w, g, m, v, w.numel(), lr, betas[0], betas[1], eps, weight_decay, step, grad_scale)
 
 
 # ---- image front-end (csrc/frontend.hip) ------------------------------------------------------------------------------
 def _mm_ws(device) -> torch.Tensor:
-    return scratch("minmax", int(load().mf_minmax_ws_floats()) + 2, device)
+    return scratch("minmax", load().mf_minmax_ws_floats() + 2, device)
 
 
 def minmax(x: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[min, max] of x (where mask > 0) as a 2-element DEVICE tensor."""
     _f32(x, mask)
     out = torch.empty(2, dtype=torch.float32, device=x.device)
-    _check(load().mf_minmax(C.c_void_p(x.data_ptr()), C.c_void_p(_ptr(mask)), C.c_int64(x.numel()), C.c_void_p(out.data_ptr()),
-                            C.c_void_p(_mm_ws(x.device).data_ptr()), _stream()), "mf_minmax")
+    _launch("mf_minmax", x, mask, x.numel(), out, _mm_ws(x.device))
     return out
 
 
@@ -1490,8 +1440,7 @@ def image_normalize(x: torch.Tensor) -> torch.Tensor:
     _f32(x)
     x = x.contiguous()
     y = torch.empty_like(x)
-    _check(load().mf_image_normalize(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_int64(x.numel()),
-                                     C.c_void_p(minmax(x).data_ptr()), _stream()), "mf_image_normalize")
+    _launch("mf_image_normalize", x, y, x.numel(), minmax(x))
     return y
 
 
@@ -1499,8 +1448,7 @@ def mask_keep(m: torch.Tensor) -> torch.Tensor:
     _f32(m)
     b, c, h, w = m.shape
     out = torch.empty(b, 1, h, w, dtype=torch.float32, device=m.device)
-    _check(load().mf_mask_keep(C.c_void_p(m.contiguous().data_ptr()), C.c_void_p(out.data_ptr()), b, c, C.c_int64(h * w), _stream()),
-           "mf_mask_keep")
+    _launch("mf_mask_keep", m.contiguous(), out, b, c, h * w)
     return out
 
 
@@ -1514,7 +1462,7 @@ def concat_channels(srcs, batch: int) -> torch.Tensor:
     arr = (C.c_void_p * n)(*[s.data_ptr() for s in srcs])
     ch = (C.c_int32 * n)(*[s.shape[1] for s in srcs])
     bs = (C.c_int32 * n)(*[s.shape[0] for s in srcs])
-    _check(load().mf_concat_channels(arr, ch, bs, n, C.c_void_p(out.data_ptr()), batch, C.c_int64(h * w), _stream()), "mf_concat_channels")
+    _launch("mf_concat_channels", arr, ch, bs, n, out, batch, h * w)
     return out
 
 
@@ -1524,14 +1472,12 @@ def postprocess(x: torch.Tensor, denormalize: bool = True, uint8: bool = False) 
     x = x.contiguous()
     b, c, h, w = x.shape
     out = torch.empty((b, h, w, c) if uint8 else (b, c, h, w), dtype=torch.uint8 if uint8 else torch.float32, device=x.device)
-    _check(load().mf_postprocess(C.c_void_p(x.data_ptr()), C.c_void_p(None if uint8 else out.data_ptr()),
-                                 C.c_void_p(out.data_ptr() if uint8 else None), b, c, C.c_int64(h * w), int(denormalize), _stream()),
-           "mf_postprocess")
+    _launch("mf_postprocess", x, None if uint8 else out, out if uint8 else None, b, c, h * w, int(denormalize))
     return out
 
 
 def _sel_ws(device) -> torch.Tensor:
-    return scratch("select", int(load().mf_select_ws_bytes()) // 4 + 8, device)
+    return scratch("select", load().mf_select_ws_bytes() // 4 + 8, device)
 
 
 def depth_percentile_normalize(depth: torch.Tensor, signed_range: bool = True) -> torch.Tensor:
@@ -1549,9 +1495,7 @@ def depth_percentile_normalize(depth: torch.Tensor, signed_range: bool = True) -
     rk = torch.tensor(ranks, dtype=torch.int64).to(depth.device)
     vals = torch.empty(4, dtype=torch.float32, device=depth.device)
     out = torch.empty_like(depth)
-    _check(load().mf_depth_percentile_normalize(C.c_void_p(depth.data_ptr()), C.c_void_p(out.data_ptr()), C.c_int64(n), C.c_void_p(rk.data_ptr()),
-                                                C.c_float(ts[0]), C.c_float(ts[1]), int(signed_range), C.c_void_p(vals.data_ptr()),
-                                                C.c_void_p(_sel_ws(depth.device).data_ptr()), _stream()), "mf_depth_percentile_normalize")
+    _launch("mf_depth_percentile_normalize", depth, out, n, rk, ts[0], ts[1], int(signed_range), vals, _sel_ws(depth.device))
     return out
 
 
@@ -1561,8 +1505,7 @@ def select_ranks(x: torch.Tensor, ranks) -> torch.Tensor:
     x = x.contiguous()
     rk = torch.tensor(list(ranks), dtype=torch.int64).to(x.device)
     vals = torch.empty(len(ranks), dtype=torch.float32, device=x.device)
-    _check(load().mf_select_ranks(C.c_void_p(x.data_ptr()), C.c_int64(x.numel()), C.c_void_p(rk.data_ptr()), len(ranks), C.c_void_p(vals.data_ptr()),
-                                  C.c_void_p(_sel_ws(x.device).data_ptr()), _stream()), "mf_select_ranks")
+    _launch("mf_select_ranks", x, x.numel(), rk, len(ranks), vals, _sel_ws(x.device))
     return vals
 
 
@@ -1574,9 +1517,8 @@ def bicubic_resize_crop(x: torch.Tensor, resized: tuple, crop: tuple, out_hw: tu
     x = x.contiguous()
     planes, h, w = x.shape
     out = torch.empty(planes, out_hw[0], out_hw[1], dtype=torch.float32, device=x.device)
-    fn, name = (load().mf_bicubic_aa_resize_crop, "mf_bicubic_aa_resize_crop") if antialias else (load().mf_bicubic_resize_crop, "mf_bicubic_resize_crop")
-    _check(fn(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), planes, h, w, int(resized[0]), int(resized[1]),
-              int(crop[0]), int(crop[1]), int(out_hw[0]), int(out_hw[1]), C.c_float(a), C.c_float(b), _stream()), name)
+    _launch("mf_bicubic_aa_resize_crop" if antialias else "mf_bicubic_resize_crop", x, out, planes, h, w, int(resized[0]), int(resized[1]),
+            int(crop[0]), int(crop[1]), int(out_hw[0]), int(out_hw[1]), a, b)
     return out
 
 
@@ -1591,8 +1533,7 @@ def hwc_to_chw_affine(x: torch.Tensor, a: float, b: float) -> torch.Tensor:
     x = x.contiguous()
     h, w, c = x.shape
     out = torch.empty(c, h, w, dtype=torch.float32, device=x.device)
-    _check(load().mf_hwc_to_chw_affine(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), C.c_int64(h * w), c, C.c_float(a), C.c_float(b),
-                                       _stream()), "mf_hwc_to_chw_affine")
+    _launch("mf_hwc_to_chw_affine", x, out, h * w, c, a, b)
     return out
 
 
@@ -1601,7 +1542,6 @@ def depth_normalize(depth: torch.Tensor, mask: Optional[torch.Tensor] = None, ma
     _f32(depth, mask)
     depth = depth.contiguous()
     out = torch.empty_like(depth)
-    _check(load().mf_depth_normalize(C.c_void_p(depth.data_ptr()), C.c_void_p(_ptr(mask.contiguous()) if mask is not None else None),
-                                     C.c_void_p(out.data_ptr()), C.c_int64(depth.numel()), C.c_float(max_scene_depth), C.c_float(delta),
-                                     int(signed_range), C.c_void_p(_mm_ws(depth.device).data_ptr()), _stream()), "mf_depth_normalize")
+    _launch("mf_depth_normalize", depth, mask.contiguous() if mask is not None else None, out, depth.numel(), max_scene_depth, delta,
+            int(signed_range), _mm_ws(depth.device))
     return out

@@ -13,7 +13,7 @@ device buffers they touch:
   * workspace       — the caching allocator's segments of a private pool the pass allocated from: one region per segment,
                       so the recorded addresses (including the allocator's reuse of freed blocks) stay valid as offsets.
 
-`mf_program_load` / `mf_program_bind` / `mf_program_run` (csrc/program.cpp, include/mfhip.h) replay the file through the same
+`mf_program_load` / `mf_program_bind` / `mf_program_run` (csrc/program.hip, include/mfhip.h) replay the file through the same
 entry points, on any stream, capturable into a hipGraph by the host.  A program is specialised like a hipGraph: shapes, precision,
 tiles and scalar arguments (guidance scale, conditioning scale) are the recorded ones.  Anything the recorder cannot express (a
 torch kernel other than a copy / fill, an entry without a replay thunk) raises at record time — there is no partial export.
@@ -31,22 +31,15 @@ MAGIC = b"MFPROG1\0"
 KIND_CONST, KIND_WORKSPACE, KIND_IO = 0, 1, 2
 A_I32, A_I64, A_F32, A_PTR, A_DESC = 0, 1, 2, 3, 4
 
-# replayable entries: one character per argument before the trailing stream — p device pointer, i int32, l int64, f float,
-# d descriptor struct (csrc/program.cpp holds the matching thunk for each; tests/test_program_gpu.py replays every one of them)
-SIGNATURES = {
-    "mf_gemm_conv": "d", "mf_groupnorm": "d",
-    "mf_layernorm": "pipipplif", "mf_softmax_rows": "ppilii",
-    "mf_attention_bf16": "plplplpliiiiif", "mf_attention_f16": "plplplpliiiiif",
-    "mf_attention_f16x3": "pplpplpplpliiiiif", "mf_attention_f16x3_lse": "pplpplpplplpiiiiif", "mf_split_halves": "pppl",
-    "mf_quantize_rows_fp8": "pipplippf",
-    "mf_pack_nhwc": "pipipiiii", "mf_unpack_nchw": "pilpiii",
-    "mf_add": "pipipil", "mf_cast_bf16": "ppl", "mf_geglu": "pipili",
-    "mf_timestep_embedding": "ppiiif", "mf_silu_f32": "ppl",
-    "mf_cfg_ddim_step_dev": "ppfpppifl", "mf_cfg_combine": "ppfpl", "mf_sched_step_dev": "ppfpppl",
-    "mf_vae_sample": "pilppiiif", "mf_nearest_resize": "ppiiiii",
-    "mf_transpose": "ppiiillll", "mf_transpose_bf16": "ppiiillll", "mf_transpose_bf16_bf16": "ppiiillll",
-    "mf_memcpy2d": "plplll", "mf_memset": "pil",
-}
+# replayable entries (csrc/program.hip holds a thunk for each; tests/test_program_gpu.py replays every one of them).  SIGNATURES: one
+# character per argument before the trailing stream, taken from hip.SIGNATURES — p device pointer, i int32, l int64, f float, d descriptor
+# struct (the two descriptors with a thunk)
+_REPLAYABLE = (
+    "mf_gemm_conv", "mf_groupnorm", "mf_layernorm", "mf_softmax_rows", "mf_attention_bf16", "mf_attention_f16", "mf_attention_f16x3",
+    "mf_attention_f16x3_lse", "mf_split_halves", "mf_quantize_rows_fp8", "mf_pack_nhwc", "mf_unpack_nchw", "mf_add", "mf_cast_bf16", "mf_geglu",
+    "mf_timestep_embedding", "mf_silu_f32", "mf_cfg_ddim_step_dev", "mf_cfg_combine", "mf_sched_step_dev", "mf_vae_sample", "mf_nearest_resize",
+    "mf_transpose", "mf_transpose_bf16", "mf_transpose_bf16_bf16", "mf_memcpy2d", "mf_memset")
+SIGNATURES = {name: hip.SIGNATURES[name][2:-1].replace("G", "d").replace("N", "d") for name in _REPLAYABLE}
 # queries / developer switches: forwarded, never recorded
 _PASS_THROUGH = ("mf_last_error", "mf_abi_version", "mf_gemm_num_tiles", "mf_gemm_tile_shape", "mf_gemm_tile_table_version",
                  "mf_groupnorm_ws_floats", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc", "mf_sizeof_sched_row")
@@ -111,7 +104,7 @@ class _Proxy:
             return fn
         if name not in SIGNATURES:
             def refuse(*a, **k):
-                raise ProgramError(f"{name} has no replay thunk (program.SIGNATURES / csrc/program.cpp): it cannot be part of an exported program")
+                raise ProgramError(f"{name} has no replay thunk (program.SIGNATURES / csrc/program.hip): it cannot be part of an exported program")
             return refuse
         rec = self._rec
 
@@ -553,10 +546,8 @@ class Program:
             f.seek(0)
             blob = f.read(head_len)
             lib = hip.load()
-            lib.mf_program_num_buffers.restype = C.c_int32
-            lib.mf_program_find_buffer.restype = C.c_int32
             self._h = C.c_void_p()
-            hip._check(lib.mf_program_load(blob, C.c_int64(len(blob)), C.byref(self._h)), "mf_program_load")
+            hip._check(lib.mf_program_load(blob, len(blob), C.byref(self._h)), "mf_program_load")
             self.tensors: Dict[int, torch.Tensor] = {}
             self.names: Dict[str, int] = {}
             with torch.cuda.device(self.device):
@@ -569,7 +560,7 @@ class Program:
                         if t.numel() < nbytes.value:
                             raise ProgramError(f"shared buffer {nm!r}: {t.numel()} bytes there, {nbytes.value} here")
                         self.tensors[i], self.names[nm] = t, i
-                        hip._check(lib.mf_program_bind(self._h, i, C.c_void_p(t.data_ptr())), "mf_program_bind")
+                        hip._check(lib.mf_program_bind(self._h, i, t.data_ptr()), "mf_program_bind")
                         continue
                     t = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=self.device)
                     if off.value >= 0:
@@ -577,20 +568,18 @@ class Program:
                         t.copy_(torch.frombuffer(bytearray(f.read(nbytes.value)), dtype=torch.uint8))
                     self.tensors[i] = t
                     self.names[name.value.decode()] = i
-                    hip._check(lib.mf_program_bind(self._h, i, C.c_void_p(t.data_ptr())), "mf_program_bind")
+                    hip._check(lib.mf_program_bind(self._h, i, t.data_ptr()), "mf_program_bind")
 
     def buffer(self, name: str, dtype=torch.uint8) -> torch.Tensor:
         return self.tensors[self.names[name]].view(dtype)
 
     @property
     def meta(self) -> str:
-        lib = hip.load()
-        lib.mf_program_meta.restype = C.c_char_p
-        return lib.mf_program_meta(self._h).decode()
+        return hip.load().mf_program_meta(self._h).decode()
 
     @property
     def num_calls(self) -> int:
-        return int(hip.load().mf_program_num_calls(self._h))
+        return hip.load().mf_program_num_calls(self._h)
 
     def run(self) -> None:
         hip._check(hip.load().mf_program_run(self._h, hip._stream()), "mf_program_run")

@@ -1,17 +1,27 @@
-"""The C-ABI library loads (no GPU needed) and exports every symbol include/mfhip.h declares."""
+"""The C-ABI library loads (no GPU needed), exports every symbol include/mfhip.h declares, and the binding's one signature table
+(hip.SIGNATURES, which load() hands to ctypes) says what the header's prototypes say."""
 import ctypes
 import os
-import re
 
+import pytest
+
+import abi_header
 from reflecting_reality_amd import _build, hip
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the host descriptor structs of the header and their ctypes mirrors
+DESCRIPTORS = {"mf_gemm_desc": hip.GemmDesc, "mf_groupnorm_desc": hip.GroupNormDesc, "mf_attn_bwd_desc": hip.AttnBwdDesc,
+               "mf_wgrad_desc": hip.WgradDesc, "mf_groupnorm_bwd_desc": hip.GroupNormBwdDesc}
+CTYPES = {"p": ctypes.c_void_p, "i": ctypes.c_int32, "l": ctypes.c_int64, "f": ctypes.c_float, "s": ctypes.c_char_p, "v": None}
 
 
-def header_functions():
-    src = open(os.path.join(ROOT, "include", "mfhip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(mf_[a-z0-9_]+)\s*\(", src)))
+def _table():
+    """hip.SIGNATURES in the parser's form: name -> (return kind, [parameter kinds]), a descriptor letter as the struct it stands for."""
+    out = {}
+    for name, sig in hip.SIGNATURES.items():
+        ret, sep, params = sig.partition(":")
+        assert sep and len(ret) == 1, f"hip.SIGNATURES[{name!r}] = {sig!r} is not '<return kind>:<parameter kinds>'"
+        out[name] = (ret, [hip.DESC_KINDS.get(k, k) for k in params])
+    return out
 
 
 def test_library_builds_and_loads():
@@ -23,17 +33,50 @@ def test_library_builds_and_loads():
 
 def test_every_declared_symbol_is_exported():
     lib = hip.load()
-    declared = header_functions()
+    declared = abi_header.declared_names()
     assert declared, "no functions parsed from mfhip.h"
     assert sorted(hip.EXPORTS) == declared, "hip.EXPORTS is out of sync with include/mfhip.h"
+    protos = abi_header.prototypes()
+    assert sorted(protos) == declared, "abi_header.prototypes() misses a function the header declares"
+    want = {name: (ret, [DESCRIPTORS.get(k, k) for k in params]) for name, (ret, params) in protos.items()}
+    table = _table()
     for name in declared:
+        assert table[name] == want[name], f"{name}: hip.SIGNATURES says {table[name]}, the header's prototype reads {want[name]}"
         assert hasattr(lib, name), f"{name} declared in mfhip.h but not exported by libmfhip.so"
+    assert hip.EXPORTS == list(hip.SIGNATURES)
+
+
+def test_load_types_every_entry_from_the_table():
+    lib = hip.load()
+    for name, (ret, params) in _table().items():
+        fn = getattr(lib, name)
+        assert fn.restype is CTYPES[ret], f"{name}: restype {fn.restype}"
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), f"{name}: argtypes {fn.argtypes}"
+        for got, k in zip(fn.argtypes, params):
+            assert got is (CTYPES[k] if isinstance(k, str) else ctypes.POINTER(k)), f"{name}: argtypes {fn.argtypes} for {params}"
+
+
+def test_the_host_refuses_misuse_before_the_library_is_entered():
+    lib = hip.load()
+    with pytest.raises(ctypes.ArgumentError):          # cols is an int32_t
+        lib.mf_softmax_rows(None, None, hip.MF_F32, 1, 8.0, 8, None)
+    with pytest.raises(ctypes.ArgumentError):          # another struct's descriptor
+        lib.mf_gemm_conv(ctypes.byref(hip.GroupNormDesc()), None)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.mf_groupnorm(ctypes.byref(hip.GemmDesc()), None)
+
+
+def test_a_bare_64_bit_int_is_not_truncated():
+    # csrc/train.hip: 64 chunks x 8 columns for a segment of 2^32 + 1 rows; an argument cut to its low 32 bits (1 row) would give 8
+    assert hip.load().mf_colsum_ws_floats(1, (1 << 32) + 1, 8) == 512
 
 
 def test_descriptor_layouts_match():
     lib = hip.load()
     assert lib.mf_sizeof_gemm_desc() == ctypes.sizeof(hip.GemmDesc)
     assert lib.mf_sizeof_groupnorm_desc() == ctypes.sizeof(hip.GroupNormDesc)
+    for struct, sizeof in hip._LAYOUTS:
+        assert getattr(lib, sizeof)() == ctypes.sizeof(struct), sizeof
     n = lib.mf_gemm_num_tiles()
     assert n >= 1
     bm, bn = ctypes.c_int(), ctypes.c_int()
@@ -54,7 +97,6 @@ def test_argument_errors_are_reported_without_a_gpu():
 
 
 def test_ops_refuse_host_tensors():
-    import pytest
     import torch
     with pytest.raises(hip.MfhipError):
         hip.silu_f32(torch.zeros(4))

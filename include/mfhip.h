@@ -250,7 +250,18 @@ int mf_softmax_rows_causal(const float* scores, void* out, int32_t out_dtype, in
 
 /* Fused flash-style attention (bf16): out[b][s][h*d + :] = softmax(q k^T * scale) v.
  * q: [B][Sq][ldq], k: [B][Skv][ldk], vt: V^T as [B][heads*d][ldvt] (keys contiguous),
- * replaces F.scaled_dot_product_attention (attention_processor.py:1266-1268). */
+ * replaces F.scaled_dot_product_attention (attention_processor.py:1266-1268).
+ *
+ * Memory past skv.  Keys are processed in tiles of 64, and the last tile is loaded whole:
+ *   - k: rows skv .. 64 * ceil(skv / 64) - 1 of batch b are the first rows of batch b + 1; behind the last batch, rows past the
+ *     B * Skv * ldk elements of the tensor are never read (they count as zeros).  Their scores are overwritten with -inf before the
+ *     softmax, so these rows may hold ANY bit pattern, NaN and inf included: they never reach the result.
+ *   - vt: columns skv .. 64 * ceil(skv / 64) - 1 of every row — the pad columns up to ldvt and, where ldvt is shorter than the
+ *     tile, the start of the next row — are multiplied by probabilities that are exactly zero.  They must be FINITE (0 * inf and
+ *     0 * NaN are NaN, in every output channel of the query); any finite value, however large, leaves the result unchanged.  Behind
+ *     the last row nothing past the B * heads * d * ldvt elements is read.
+ * The same holds for every mf_attention_* entry below (the split flavours: for both planes); gap columns of q, k and out rows
+ * (ldq, ldk, ldo wider than heads * d) are neither read nor written.  tests/test_attention_gpu.py::test_decoys_past_skv. */
 int mf_attention_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                       void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
                       int32_t head_dim, float scale, void* stream);

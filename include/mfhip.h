@@ -15,6 +15,10 @@
  * bit-identical to the [batch][tokens][channels] layout of the transformer blocks, so no
  * transposes exist between conv and attention.  Weights are [N][K] with K contiguous
  * (conv: [Cout][ky][kx][Cin]).  dtype codes: MF_F32 = 0, MF_BF16 = 1.
+ *
+ * ABI 23 adds the reference's 'ip_adapter' normals mode (examples/brushnet/train_brushnet_mirror.py:752-756, 858-888): decoupled
+ * cross-attention in one launch (mf_attention_ip_bf16 / _f16 / _f16x3), the frequency encoder of the mirror normal (mf_freq_encode)
+ * and the mean normal over the mirror mask (mf_masked_mean_normal).  These entries are not part of step programs.
  */
 #ifndef MFHIP_H
 #define MFHIP_H
@@ -59,7 +63,7 @@ extern "C" {
 #define MF_ACT_GEGLU4 2
 
 /* ABI version, bumped on any struct change; checked by the Python host at load time. */
-#define MF_ABI_VERSION 22
+#define MF_ABI_VERSION 23
 int mf_abi_version(void);
 const char* mf_last_error(void);
 /* sizeof() of the descriptor structs, so a foreign-language binding can verify its layout */
@@ -296,6 +300,30 @@ int mf_attention_f16x3_lse(const void* q_hi, const void* q_lo, int64_t ldq, cons
                            const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, float* lse, int32_t batch,
                            int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream);
 
+/* Decoupled cross-attention (ABI 23): the reference's IPAttnProcessor2_0 (ip_adapter/attention_processor.py:282-410), which every
+ * attn2 of a UNet trained with --normals_conditioning_mode ip_adapter carries, in ONE launch:
+ *   out = softmax(q k^T * scale) v + ip_scale * softmax(q k_ip^T * scale) v_ip,        each softmax over its own keys only.
+ * k_ip: [B][skv_ip][ldk_ip], vt_ip: V_ip^T as [B][heads*d][ldvt_ip] (keys contiguous, ldvt_ip a multiple of 8 and >= skv_ip);
+ * 1 <= skv_ip <= 64 (one key tile; else MF_EINVAL).  The ip keys are one more tile on the text keys' Q fragments, LDS buffers and epilogue,
+ * with a fresh softmax; the two results are added in the fp32 accumulator and rounded to storage once.  Everything said of k / vt above
+ * holds for k_ip / vt_ip, with this difference: key rows past skv_ip are never read, and of vt_ip only the columns up to
+ * 8 * ceil(skv_ip / 8) are (the pad columns among them must be finite).  Head dims as the plain entries (the split flavour: no 160). */
+int mf_attention_ip_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, const void* k_ip,
+                         int64_t ldk_ip, const void* vt_ip, int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads,
+                         int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale, float ip_scale, void* stream);
+int mf_attention_ip_f16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, const void* k_ip,
+                        int64_t ldk_ip, const void* vt_ip, int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads,
+                        int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale, float ip_scale, void* stream);
+int mf_attention_ip_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                          const void* vt_hi, const void* vt_lo, int64_t ldvt, const void* k_ip_hi, const void* k_ip_lo,
+                          int64_t ldk_ip, const void* vt_ip_hi, const void* vt_ip_lo, int64_t ldvt_ip, float* out, int64_t ldo,
+                          int32_t batch, int32_t heads, int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale,
+                          float ip_scale, void* stream);
+/* Frequency encoding of the mirror normal (ip_adapter/ip_adapter.py:50-94 FreqEncoder, log sampling, (sin, cos), no input copy):
+ * x fp32 [rows][in_dim] -> out fp32 [rows][2 * n_freqs * in_dim], out[r][(2 i + s) * in_dim + j] = (s ? cos : sin)(x[r][j] * f_i),
+ * f_i = 2^(i * max_freq_log2 / (n_freqs - 1)). */
+int mf_freq_encode(const float* x, float* out, int32_t rows, int32_t in_dim, int32_t n_freqs, float max_freq_log2, void* stream);
+
 /* Flash-style attention BACKWARD in split precision (the training step's backward through
  * F.scaled_dot_product_attention, attention_processor.py:1266-1268 under train_brushnet_mirror.py:1459): dQ, dK, dV from Q, K, V,
  * dO, the forward's lse and dd[b][head][i] = sum_c dO[b][i][head*d + c] * O[b][i][head*d + c] (mf_rowdot_heads).  P is recomputed
@@ -466,6 +494,9 @@ int mf_minmax(const float* x, const float* mask, int64_t n, float* out2, float* 
 int mf_image_normalize(const float* x, float* y, int64_t n, const float* minmax, void* stream);
 /* out[b][0][p] = (sum_c mask[b][c][p] < 0) ? 1 : 0: 1 = keep, 0 = hole (pipeline_brushnet.py:1139) */
 int mf_mask_keep(const float* mask, float* out, int32_t batch, int32_t channels, int64_t hw, void* stream);
+/* The 'ip_adapter' normals transform (dataset.py:173-180): out3 = the mean of normals[p][0..2] (HWC fp32, `pixels` = H * W) over the
+ * pixels with mask[p] > 0, divided by its L2 norm (ABI 23). */
+int mf_masked_mean_normal(const float* normals, const float* mask, float* out3, int64_t pixels, void* stream);
 /* torch.cat along channels of up to 8 NCHW sources into out [batch][sum channels][hw]; source i has batches[i] images and
  * is repeated (image b % batches[i]) when that is smaller than batch */
 int mf_concat_channels(const float* const* srcs, const int32_t* channels, const int32_t* batches, int32_t nsrc, float* out,

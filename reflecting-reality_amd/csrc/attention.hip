@@ -34,6 +34,12 @@ struct AttnArgs {
     int heads, sq, skv, batch;
     float c;   // softmax scale * log2(e)
     int no_xcd_order;   // A/B switch (MFHIP_ATTN_NOXCD=1): keep the hardware's round-robin block order
+    // IP (decoupled cross-attention): a second key / value segment of 1 .. 64 keys with a softmax of its own
+    const char* k_ip; int64_t ldk_ip;      // [batch][skv_ip][ldk_ip]
+    const char* vt_ip; int64_t ldvt_ip;    // [batch][heads*d][ldvt_ip]
+    const char* k_ip2; const char* vt_ip2; // SP: the low-half planes
+    int skv_ip;
+    float ip_scale;
 };
 
 __device__ unsigned g_split_ovf_attn;     // raised when an fp16-split operand of this file exceeded the fp16 range (mf_common.h)
@@ -50,9 +56,17 @@ __device__ __forceinline__ f32x16_t mfma16(const uint4& a, const uint4& b, const
 // CAUSAL (the CLIP text encoders' self-attention, sq == skv): key > query is masked to -inf next to the tail mask, and a block stops
 // after the key tile that holds its last query.  Tiles are walked in ascending order and key 0 is visible to every query, so the
 // running max is finite after the first tile and a wholly masked later tile gives exp2(-inf - m) = 0, never (-inf) - (-inf).
-template <int HD, bool DB, bool SP = false, bool F16 = false, bool CAUSAL = false>
+// IP (decoupled cross-attention, the reference's IPAttnProcessor2_0): out = softmax(q k^T c) v + ip_scale softmax(q k_ip^T c) v_ip.
+// The ip keys (1 .. 64: one tile) are walked as one more tile AFTER the text tiles, on the same Q fragments, LDS buffers and epilogue,
+// but as the first tile of a new softmax: the running offset starts afresh (m, l, and on the MJ head dims the pad slots of Q~).  No
+// second accumulator and no parked copy of the text result: the ip segment is ONE tile, so its row sum l_ip is known before its
+// second product.  With f = ip_scale / l_ip = g 2^n (1 <= |g| < 2), O^T is normalised in place to (o_text / l_text) 2^-n, the ip
+// probabilities enter the second product as P g (the factor g does not shrink P, so it rounds to the operand type exactly as well
+// as P does), and the epilogue multiplies by 2^n: the two results meet in the fp32 accumulator and are rounded to storage once.
+template <int HD, bool DB, bool SP = false, bool F16 = false, bool CAUSAL = false, bool IP = false>
 __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2)) void attn_fwd_kernel(const AttnArgs p) {
     static_assert(!(SP && F16), "F16 is the single-plane form");
+    static_assert(!(IP && CAUSAL), "the ip segment belongs to cross-attention");
     constexpr unsigned ONE2 = F16 ? 0x3C003C00u : 0x3F803F80u;   // (1.0, 1.0)
     constexpr int NP = SP ? 2 : 1;            // operand planes (hi, lo)
     constexpr int OES = SP ? 4 : 2;           // output element size
@@ -203,6 +217,40 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
 #pragma unroll
         for (int e = 0; e < 16; ++e) o[d][e] = 0.0f;
     float m = MJ ? 0.0f : -INFINITY, l = 0.0f;
+    float l_text = 0.0f, ip_unit = 1.0f;      // IP: the text segment's row sum; the power of two the accumulator is held in
+    (void)l_text; (void)ip_unit;
+    // IP: the one tile of k_ip / vt_ip, staged like any other (permuted K rows, zeros in pad chunks) into the buffer the loop would
+    // prefetch next.  Key rows past skv_ip and V^T chunks wholly past skv_ip are never read (out-of-range lanes write zeros).
+    auto issue_ip_tile = [&](int buf) {
+        const int64_t kb = ((int64_t)b * p.skv_ip * p.ldk_ip + head * HD) * 2;
+        const int64_t kl = ((int64_t)(p.batch - b) * p.skv_ip * p.ldk_ip - head * HD) * 2;
+        const int64_t vb = ((int64_t)(b * p.heads + head) * HD) * p.ldvt_ip * 2;
+        const int64_t vl = ((int64_t)((p.batch - b) * p.heads - head) * HD * p.ldvt_ip) * 2;
+        const unsigned lk = lds0 + buf * BUF_BYTES;
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) {
+            const srd_t sk = make_srd((pl ? p.k_ip2 : p.k_ip) + kb, (unsigned)(kl < 0x7fffffff ? kl : 0x7fffffff));
+            const srd_t sv = make_srd((pl ? p.vt_ip2 : p.vt_ip) + vb, (unsigned)(vl < 0x7fffffff ? vl : 0x7fffffff));
+#pragma unroll
+            for (int i = 0; i < KPW; ++i) {
+                const int g = (wv + 4 * i) * 64 + lane;
+                const int R = g / KCPR, c = g - R * KCPR;
+                const int kr = (R & ~12) | ((R & 4) << 1) | ((R & 8) >> 1);
+                const int64_t off = ((int64_t)kr * p.ldk_ip + c * 8) * 2;
+                const unsigned ko = (c < HD / 8 && kr < p.skv_ip && off < 0x7fffffff) ? (unsigned)off : 0x80000000u;
+                if (wv + 4 * i < KI) dma16_buf(ko, sk, lk + pl * K_BYTES + (wv + 4 * i) * 1024);
+            }
+#pragma unroll
+            for (int i = 0; i < VPW; ++i) {
+                const int g = (wv + 4 * i) * 64 + lane;
+                const int row = g / VCPR, c = g - row * VCPR;
+                const int64_t off = ((int64_t)row * p.ldvt_ip + c * 8) * 2;
+                const unsigned vo = (row < HD && c * 8 < p.skv_ip && off < 0x7fffffff) ? (unsigned)off : 0x80000000u;
+                if (wv + 4 * i < VI) dma16_buf(vo, sv, lk + V0 + pl * V_BYTES + (wv + 4 * i) * 1024);
+            }
+        }
+    };
+    (void)issue_ip_tile;
     // MJ: bf16 ones in k slots HD, HD+1, HD+2 of the last K fragment, for the half-wave that reads the pad chunk
     const unsigned ones_x = (MJ && h) ? ONE2 : 0u, ones_y = (MJ && h) ? (ONE2 & 0xffffu) : 0u;
     (void)ones_x; (void)ones_y;
@@ -216,12 +264,26 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
     issue_tile(0);
     wait_vmcnt<0>();
     __syncthreads();
-    for (int t = 0; t < ntiles; ++t) {
-        const int kv0 = t * 64;
+    for (int t = 0; t < ntiles + (IP ? 1 : 0); ++t) {
+        const bool ipt = IP && t == ntiles;                // the ip tile: block-uniform
+        const bool first = t == 0 || ipt;                  // the first tile of a softmax
+        const int kv0 = ipt ? 0 : t * 64;
+        const int kv_end = ipt ? p.skv_ip : p.skv;
         const char* Ks = smem + (t & 1) * BUF_BYTES;
         const char* Vs = Ks + V0;
         // the other buffer was last read in iteration t-1, which every wave finished before the barrier that ended it
         if (t + 1 < ntiles) issue_tile((t + 1) & 1);       // the DMA flies under this tile's MFMAs and softmax
+        if constexpr (IP) {
+            if (t + 1 == ntiles) issue_ip_tile((t + 1) & 1);
+            if (ipt) {         // a new softmax: keep the text row sum, forget the offset (MJ: the Q~ pad slots go back to zero)
+                if (!ONES) l_text = l + __shfl_xor(l, 32, 64);
+                l = 0.0f;
+                m = MJ ? 0.0f : -INFINITY;
+                if constexpr (MJ) {
+                    if (h) { qf[0][KS - 1].x = 0u; qf[0][KS - 1].y = 0u; }
+                }
+            }
+        }
 
         // ---- S^T = K . Q^T : two 32-key tiles ----
         f32x16_t st[2];
@@ -245,13 +307,13 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
                 }
             }
         }
-        if (kv0 + 64 > p.skv) {
+        if (kv0 + 64 > kv_end) {
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int key = kv0 + 32 * tt + (e & 3) + 4 * (e >> 2 & 1) + 16 * (e >> 3) + 8 * h;   // row with bits 2, 3 swapped
-                    if (key >= p.skv) st[tt][e] = -INFINITY;
+                    if (key >= kv_end) st[tt][e] = -INFINITY;
                 }
         }
         if constexpr (CAUSAL) {
@@ -274,8 +336,8 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
         if constexpr (MJ) {
             // st already is score - m.  Move the offset only when some lane's scores run more than MJ_T above it (and on
             // the first tile, where the offset is still 0): wave-uniform, rare after the first few tiles
-            if (t == 0 || __builtin_amdgcn_ballot_w64(mx > MJ_T) != 0) {
-                const float want = m + (t == 0 ? mx : fmaxf(mx, 0.0f));
+            if (first || __builtin_amdgcn_ballot_w64(mx > MJ_T) != 0) {
+                const float want = m + (first ? mx : fmaxf(mx, 0.0f));
                 // the offset the matrix pipe can subtract exactly: three 16-bit pieces (bf16: 24 bits; fp16: 33, the last piece
                 // may be an fp16 subnormal — the matrix pipe keeps those)
                 float f0, f1, f2, dummy;
@@ -298,7 +360,7 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
                 for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) st[tt][e] -= dlt;
-                if (t != 0) {
+                if (!first) {
                     const float alpha = __builtin_amdgcn_exp2f(-dlt);
                     l *= alpha;
 #pragma unroll
@@ -313,7 +375,7 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
                 for (int e = 0; e < 16; ++e) {
                     const float pv = __builtin_amdgcn_exp2f(st[tt][e]);
                     st[tt][e] = pv;
-                    if (!ONES) rs += pv;
+                    if (!ONES || ipt) rs += pv;
                 }
         } else {
             const float m_new = fmaxf(m, mx * p.c);
@@ -328,10 +390,11 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
                 for (int e = 0; e < 16; ++e) {
                     const float pv = __builtin_amdgcn_exp2f(fmaf(st[tt][e], p.c, -m_sub));
                     st[tt][e] = pv;
-                    if (!ONES) rs += pv;
+                    if (!ONES || ipt) rs += pv;
                 }
             // the running max settles after the first few tiles: skip the O^T rescale when no lane's max moved
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
+            // (the ip tile starts from m = -inf: alpha = 0 there, and O^T holds the text result, which is not its to rescale)
+            if (!ipt && __builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
                 l *= alpha;
 #pragma unroll
                 for (int d = 0; d < DT; ++d)
@@ -340,6 +403,28 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
             }
         }
         if (!ONES) l += rs;
+        if constexpr (IP) {
+            if (ipt) {
+                // the text result is complete in o[] (ONES: its row sum still sits in accumulator row ONES_ROW) and the ip row sum is known
+                const float l_ip = rs + __shfl_xor(rs, 32, 64);
+                if (ONES) l_text = __shfl(o[L_D][L_E], (lane & 31) + 32 * L_H, 64);
+                const float f = p.ip_scale / l_ip;
+                const unsigned fb = __builtin_bit_cast(unsigned, f), ex = (fb >> 23) & 0xffu;
+                // f = g * 2^(ex - 127) with 1 <= |g| < 2; outside 2^+-30 (ip_scale = 0 among them) the accumulator keeps unit 1
+                const bool ok = ex >= 97u && ex <= 157u;
+                const float g = ok ? __builtin_bit_cast(float, (fb & 0x807fffffu) | 0x3f800000u) : f;
+                ip_unit = ok ? __builtin_bit_cast(float, ex << 23) : 1.0f;
+                const float a = (1.0f / l_text) * (ok ? __builtin_bit_cast(float, (254u - ex) << 23) : 1.0f);
+#pragma unroll
+                for (int d = 0; d < DT; ++d)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) o[d][e] *= a;
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) st[tt][e] *= g;
+            }
+        }
         // ---- P^T fragments: accumulator registers 8s..8s+7 of tile tt are k-step 2*tt+s ----
         uint4 pf[NP][4];
 #pragma unroll
@@ -388,7 +473,7 @@ __global__ __launch_bounds__(256, (HD <= 80 && !SP) ? 3 : (SP && HD > 64 ? 1 : 2
     // ---- epilogue: normalise, transpose through LDS, row-contiguous stores ----
     if (ONES) l = __shfl(o[L_D][L_E], (lane & 31) + 32 * L_H, 64);      // the half-wave that holds accumulator row ONES_ROW
     else l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
+    const float inv = IP ? ip_unit : 1.0f / l;        // IP: o[] is normalised already, in units of 2^-n
     if (p.lse && h == 0 && qi < p.sq) p.lse[((int64_t)b * p.heads + head) * p.sq + qi] = m + __builtin_amdgcn_logf(l) - (SP ? (float)SP_SHIFT : 0.0f);   // v_log_f32 = log2
     char* Os = smem + wave * 32 * RBO;   // safe: the loop ended on a barrier
 #pragma unroll
@@ -838,10 +923,10 @@ __global__ __launch_bounds__(256) void rowdot_heads_kernel(const float* a, const
     }
 }
 
-template <int HD, bool SP = false, bool F16 = false, bool CAUSAL = false>
+template <int HD, bool SP = false, bool F16 = false, bool CAUSAL = false, bool IP = false>
 void launch_attn(const AttnArgs& a, int batch, hipStream_t s) {
     dim3 grid((unsigned)(((a.sq + 127) / 128) * a.heads * batch));
-    hipLaunchKernelGGL((attn_fwd_kernel<HD, true, SP, F16, CAUSAL>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, true, SP, F16, CAUSAL, IP>), grid, dim3(256), 0, s, a);
 }
 
 // fp32 [rows][ld] (first `cols` columns) -> two fp16 planes of the same layout: hi toward zero, lo = x - hi
@@ -1040,6 +1125,85 @@ static int attention_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, cons
     }
     MF_CHECK_LAUNCH("mf_attention_f16x3");
     return MF_OK;
+}
+
+// ---- decoupled cross-attention (IP): a second key / value segment with its own softmax, one launch ----
+static int attention_ip(int flavour /* 0 bf16, 1 fp16, 2 split */, const void* const q[2], int64_t ldq, const void* const k[2], int64_t ldk,
+                        const void* const vt[2], int64_t ldvt, const void* const k_ip[2], int64_t ldk_ip, const void* const vt_ip[2],
+                        int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv, int32_t skv_ip,
+                        int32_t head_dim, float scale, float ip_scale, void* stream) {
+    const int np = flavour == 2 ? 2 : 1;
+    for (int pl = 0; pl < np; ++pl) {
+        MF_CHECK_ARG(q[pl] && k[pl] && vt[pl] && k_ip[pl] && vt_ip[pl] && out, "mf_attention_ip: null pointer");
+        if (!mf_aligned16(q[pl]) || !mf_aligned16(k[pl]) || !mf_aligned16(vt[pl]) || !mf_aligned16(k_ip[pl]) || !mf_aligned16(vt_ip[pl]) ||
+            !mf_aligned16(out)) {
+            mf_set_error("mf_attention_ip: pointers must be 16-byte aligned");
+            return MF_EALIGN;
+        }
+    }
+    MF_CHECK_ARG(batch >= 1 && heads >= 1 && sq >= 1 && skv >= 1, "mf_attention_ip: bad sizes");
+    MF_CHECK_ARG(skv_ip >= 1 && skv_ip <= 64, "mf_attention_ip: skv_ip = %d, the ip segment is one key tile (1 .. 64)", skv_ip);
+    MF_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldk_ip % 8 == 0 && ldvt_ip % 8 == 0 && ldo % (flavour == 2 ? 4 : 8) == 0 &&
+                     ldvt >= skv && ldvt_ip >= skv_ip,
+                 "mf_attention_ip: leading dims must be multiples of 8 (fp32 ldo: 4), ldvt >= skv and ldvt_ip >= skv_ip");
+    AttnArgs a{};
+    a.q = (const char*)q[0]; a.q2 = (const char*)q[1]; a.ldq = ldq;
+    a.k = (const char*)k[0]; a.k2 = (const char*)k[1]; a.ldk = ldk;
+    a.vt = (const char*)vt[0]; a.vt2 = (const char*)vt[1]; a.ldvt = ldvt;
+    a.k_ip = (const char*)k_ip[0]; a.k_ip2 = (const char*)k_ip[1]; a.ldk_ip = ldk_ip;
+    a.vt_ip = (const char*)vt_ip[0]; a.vt_ip2 = (const char*)vt_ip[1]; a.ldvt_ip = ldvt_ip;
+    a.out = (char*)out; a.ldo = ldo; a.heads = heads; a.sq = sq; a.skv = skv; a.batch = batch;
+    a.skv_ip = skv_ip; a.ip_scale = ip_scale;
+    a.c = scale * 1.44269504088896340736f;
+    { static const bool off = getenv("MFHIP_ATTN_NOXCD") != nullptr; a.no_xcd_order = off; }
+    hipStream_t s = (hipStream_t)stream;
+    switch (flavour * 1000 + head_dim) {
+        case 8: launch_attn<8, false, false, false, true>(a, batch, s); break;
+        case 40: launch_attn<40, false, false, false, true>(a, batch, s); break;
+        case 64: launch_attn<64, false, false, false, true>(a, batch, s); break;
+        case 80: launch_attn<80, false, false, false, true>(a, batch, s); break;
+        case 160: launch_attn<160, false, false, false, true>(a, batch, s); break;
+        case 1008: launch_attn<8, false, true, false, true>(a, batch, s); break;
+        case 1040: launch_attn<40, false, true, false, true>(a, batch, s); break;
+        case 1064: launch_attn<64, false, true, false, true>(a, batch, s); break;
+        case 1080: launch_attn<80, false, true, false, true>(a, batch, s); break;
+        case 1160: launch_attn<160, false, true, false, true>(a, batch, s); break;
+        case 2008: launch_attn<8, true, false, false, true>(a, batch, s); break;
+        case 2040: launch_attn<40, true, false, false, true>(a, batch, s); break;
+        case 2064: launch_attn<64, true, false, false, true>(a, batch, s); break;
+        case 2080: launch_attn<80, true, false, false, true>(a, batch, s); break;
+        default:
+            mf_set_error("mf_attention_ip: unsupported head_dim %d (have 8, 40, 64, 80, and 160 for the 16-bit flavours)", head_dim);
+            return MF_EINVAL;
+    }
+    MF_CHECK_LAUNCH("mf_attention_ip");
+    return MF_OK;
+}
+
+extern "C" int mf_attention_ip_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, const void* k_ip,
+                                    int64_t ldk_ip, const void* vt_ip, int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads,
+                                    int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale, float ip_scale, void* stream) {
+    const void *qq[2] = {q, nullptr}, *kk[2] = {k, nullptr}, *vv[2] = {vt, nullptr}, *ki[2] = {k_ip, nullptr}, *vi[2] = {vt_ip, nullptr};
+    return attention_ip(0, qq, ldq, kk, ldk, vv, ldvt, ki, ldk_ip, vi, ldvt_ip, out, ldo, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale,
+                        stream);
+}
+
+extern "C" int mf_attention_ip_f16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, const void* k_ip,
+                                   int64_t ldk_ip, const void* vt_ip, int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads,
+                                   int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale, float ip_scale, void* stream) {
+    const void *qq[2] = {q, nullptr}, *kk[2] = {k, nullptr}, *vv[2] = {vt, nullptr}, *ki[2] = {k_ip, nullptr}, *vi[2] = {vt_ip, nullptr};
+    return attention_ip(1, qq, ldq, kk, ldk, vv, ldvt, ki, ldk_ip, vi, ldvt_ip, out, ldo, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale,
+                        stream);
+}
+
+extern "C" int mf_attention_ip_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                                     const void* vt_hi, const void* vt_lo, int64_t ldvt, const void* k_ip_hi, const void* k_ip_lo,
+                                     int64_t ldk_ip, const void* vt_ip_hi, const void* vt_ip_lo, int64_t ldvt_ip, float* out, int64_t ldo,
+                                     int32_t batch, int32_t heads, int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale,
+                                     float ip_scale, void* stream) {
+    const void *qq[2] = {q_hi, q_lo}, *kk[2] = {k_hi, k_lo}, *vv[2] = {vt_hi, vt_lo}, *ki[2] = {k_ip_hi, k_ip_lo}, *vi[2] = {vt_ip_hi, vt_ip_lo};
+    return attention_ip(2, qq, ldq, kk, ldk, vv, ldvt, ki, ldk_ip, vi, ldvt_ip, out, ldo, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale,
+                        stream);
 }
 
 template <int HD, bool B16 = false>

@@ -147,6 +147,23 @@ __global__ void timestep_embedding_kernel(const float* t, float* out, int n, int
     }
 }
 
+// Frequency encoding of the mirror normal (the reference's ip_adapter/ip_adapter.py:50-94 FreqEncoder with log sampling, no input copy,
+// (sin, cos)): out[r][(2 i + s) * in_dim + j] = (s ? cos : sin)(x[r][j] * f_i), f_i = 2^(i * max_freq_log2 / (n_freqs - 1)), all in fp32.
+// The exponents are formed the way torch.linspace(0, max_freq_log2, n_freqs) forms them in fp32 (from the start below the middle, back
+// from the end above it), so that f_i differs from the reference's 2.0 ** linspace by the rounding of the power alone.
+__global__ void freq_encode_kernel(const float* x, float* out, int rows, int in_dim, int n_freqs, float step, float max_log2) {
+    const int total = rows * in_dim * n_freqs;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+        const int j = idx % in_dim, i = (idx / in_dim) % n_freqs, r = idx / (in_dim * n_freqs);
+        // (separately rounded product and difference, as ATen's linspace computes them: no contraction into an fma)
+        const float ex = i < n_freqs / 2 ? __fmul_rn(step, (float)i) : __fsub_rn(max_log2, __fmul_rn(step, (float)(n_freqs - i - 1)));
+        const float arg = x[(int64_t)r * in_dim + j] * exp2f(ex);
+        float* o = out + (int64_t)r * (2 * in_dim * n_freqs) + (int64_t)(2 * i) * in_dim + j;
+        o[0] = sinf(arg);
+        o[in_dim] = cosf(arg);
+    }
+}
+
 // ---- CLIP text encoder: token + position embedding gather, and the MLP activations -------------------------------------------
 // 8 consecutive elements of a row as fp32: two 16-byte loads of an fp32 tensor, one of a 16-bit tensor
 __device__ __forceinline__ void load8_as_f32(const char* p, int dt, int64_t i, float* v) {
@@ -459,6 +476,16 @@ extern "C" int mf_timestep_embedding(const float* t, float* out, int32_t n, int3
     hipLaunchKernelGGL(timestep_embedding_kernel, dim3(grid_for((int64_t)n * (dim / 2))), dim3(256), 0,
                        (hipStream_t)stream, t, out, n, dim, flip_sin_to_cos, freq_shift);
     MF_CHECK_LAUNCH("mf_timestep_embedding");
+    return MF_OK;
+}
+
+extern "C" int mf_freq_encode(const float* x, float* out, int32_t rows, int32_t in_dim, int32_t n_freqs, float max_freq_log2, void* stream) {
+    MF_CHECK_ARG(x && out && rows >= 1 && in_dim >= 1 && n_freqs >= 1, "mf_freq_encode: bad arguments");
+    MF_CHECK_ARG((int64_t)rows * in_dim * n_freqs < (1 << 30), "mf_freq_encode: rows * in_dim * n_freqs must stay below 2^30");
+    const float step = n_freqs > 1 ? max_freq_log2 / (float)(n_freqs - 1) : 0.0f;
+    hipLaunchKernelGGL(freq_encode_kernel, dim3(grid_for((int64_t)rows * in_dim * n_freqs)), dim3(256), 0, (hipStream_t)stream, x, out, rows,
+                       in_dim, n_freqs, step, max_freq_log2);
+    MF_CHECK_LAUNCH("mf_freq_encode");
     return MF_OK;
 }
 

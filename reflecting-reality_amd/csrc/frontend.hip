@@ -312,6 +312,34 @@ extern "C" int mf_image_normalize(const float* x, float* y, int64_t n, const flo
     return MF_OK;
 }
 
+// dataset.py:173-180 ('ip_adapter' normals): the mean of normals[p][0..2] over the pixels with mask[p] > 0, L2-normalised.  mean / |mean| =
+// sum / |sum|, so the count never enters.  One block, double accumulation, a fixed reduction tree: deterministic.  An empty mask gives
+// NaN, as the reference's 0 / 0 does.
+__global__ __launch_bounds__(256) void masked_mean_normal_kernel(const float* normals, const float* mask, float* out3, int64_t pixels) {
+    __shared__ double red[3][256];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int64_t i = threadIdx.x; i < pixels; i += 256)
+        if (mask[i] > 0.0f) { s0 += normals[3 * i]; s1 += normals[3 * i + 1]; s2 += normals[3 * i + 2]; }
+    red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = s2;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) {
+        const double nrm = sqrt(red[0][0] * red[0][0] + red[1][0] * red[1][0] + red[2][0] * red[2][0]);
+        out3[threadIdx.x] = (float)(red[threadIdx.x][0] / nrm);
+    }
+}
+
+extern "C" int mf_masked_mean_normal(const float* normals, const float* mask, float* out3, int64_t pixels, void* stream) {
+    MF_CHECK_ARG(normals && mask && out3 && pixels >= 1, "mf_masked_mean_normal: bad arguments");
+    hipLaunchKernelGGL(masked_mean_normal_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, normals, mask, out3, pixels);
+    MF_CHECK_LAUNCH("mf_masked_mean_normal");
+    return MF_OK;
+}
+
 extern "C" int mf_mask_keep(const float* mask, float* out, int32_t batch, int32_t channels, int64_t hw, void* stream) {
     MF_CHECK_ARG(mask && out && batch >= 1 && channels >= 1 && hw >= 1, "mf_mask_keep: bad arguments");
     hipLaunchKernelGGL(mask_keep_kernel, dim3(fgrid((int64_t)batch * hw)), dim3(256), 0, (hipStream_t)stream, mask, out, batch, channels, hw);

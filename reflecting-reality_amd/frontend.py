@@ -75,9 +75,10 @@ def apply_transforms_depth(depth_map, mask=None, normalization_method: str = "ma
 def apply_transforms_normals(normals_map, resolution: int = 512, mask=None, normals_conditioning_mode: str = "concat", device="cuda",
                              antialias: Optional[bool] = None, **kwargs) -> torch.Tensor:
     """dataset.py:168-192 for the map-valued modes: [H, W, 3] -> [3, resolution, resolution], (x - 0.5) / 0.5.  The
-    'ip_adapter' mode (one mean normal vector for the image encoder) belongs to the IP-Adapter path, which is out of scope."""
+    'ip_adapter' mode returns one mean normal vector instead of a map: that is mean_normal_over_mask below."""
     if normals_conditioning_mode == "ip_adapter":
-        raise NotImplementedError("normals_conditioning_mode='ip_adapter' (SURVEY.md §2 #14: IP-Adapter is outside the hot path)")
+        raise NotImplementedError("normals_conditioning_mode='ip_adapter' yields one [1, 3] vector, not a map: use "
+                                  "frontend.mean_normal_over_mask(normals_map, mask) and frontend.NormalEmbedder")
     x = torch.as_tensor(np.ascontiguousarray(normals_map) if isinstance(normals_map, np.ndarray) else normals_map).to(device, torch.float32)
     if x.dim() != 3 or x.shape[-1] != 3:
         raise ValueError("apply_transforms_normals takes an [H, W, 3] normals map")
@@ -85,3 +86,62 @@ def apply_transforms_normals(normals_map, resolution: int = 512, mask=None, norm
     if (h, w) == (resolution, resolution):
         return hip.hwc_to_chw_affine(x, 2.0, -1.0)                                                   # Normalize([0.5], [0.5])
     return _resize_crop(hip.hwc_to_chw_affine(x, 1.0, 0.0), resolution, antialias, 2.0, -1.0)
+
+
+def mean_normal_over_mask(normals_map, mask, device="cuda") -> torch.Tensor:
+    """dataset.py:173-180 (`apply_transforms_normals(..., "ip_adapter")`): the mean of normals_map [H, W, 3] over the pixels where
+    mask [H, W] > 0, L2-normalised, as a [1, 3] fp32 device tensor — one reduction on the device (mf_masked_mean_normal)."""
+    as_dev = lambda a: torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a).to(device, torch.float32)
+    x, m = as_dev(normals_map), as_dev(mask)
+    if x.dim() != 3 or x.shape[-1] != 3:
+        raise ValueError("mean_normal_over_mask takes an [H, W, 3] normals map")
+    if m.dim() == 3 and m.shape[-1] == 1:
+        m = m[:, :, 0]
+    if tuple(m.shape) != tuple(x.shape[:2]):
+        raise ValueError(f"mean_normal_over_mask: the mask must be [H, W] = {tuple(x.shape[:2])}, got {tuple(m.shape)}")
+    return hip.masked_mean_normal(x.contiguous(), m.contiguous())
+
+
+class NormalEmbedder:
+    """The 'ip_adapter' normals branch of MirrorFusionModel.forward (train_brushnet_mirror.py:868-871, 1085-1098): FreqEncoder(input_dim=3,
+    max_freq_log2=5, N_freqs=32, log sampling, no input copy, (sin, cos)) -> [.., 192], then NormalProjModel = Linear(192,
+    cross_attention_dim) + erf-GELU (ip_adapter/ip_adapter.py:50-112; checkpoint keys "proj.0.weight" / "proj.0.bias", the "image_proj"
+    dict of an ip-adapter.bin).  normal [B, 1, 3] -> one prompt token [B, 1, cross_attention_dim] in the model's storage dtype."""
+
+    N_FREQS, MAX_FREQ_LOG2, INPUT_DIM = 32, 5.0, 3
+
+    def __init__(self, cross_attention_dim: int, device="cuda", precision="bf16"):
+        from . import ops
+        self.cross_attention_dim, self.device = cross_attention_dim, torch.device(device)
+        self.prec = ops.Precision.get(precision) if isinstance(precision, str) else precision
+        self.proj = None
+
+    @property
+    def embed_dim(self) -> int:
+        return 2 * self.N_FREQS * self.INPUT_DIM
+
+    def load_state_dict(self, image_proj) -> "NormalEmbedder":
+        from . import ops
+        w, b = image_proj["proj.0.weight"], image_proj["proj.0.bias"]
+        if tuple(w.shape) != (self.cross_attention_dim, self.embed_dim) or tuple(b.shape) != (self.cross_attention_dim,):
+            raise ValueError(f"image_proj: proj.0.weight must be [{self.cross_attention_dim}, {self.embed_dim}], got {tuple(w.shape)}")
+        self._src = {"proj.0.weight": w.detach().float().cpu().clone(), "proj.0.bias": b.detach().float().cpu().clone()}
+        # the token is computed once per image from an fp32 encoding: the projection stays fp32 (f16x3 in that mode) whatever the storage dtype
+        self._pprec = ops.Precision.get("f16x3" if self.prec.name == "f16x3" else "fp32")
+        self.proj = ops.ConvWeight(self._src["proj.0.weight"], self._src["proj.0.bias"], self._pprec, self.device)
+        return self
+
+    def state_dict(self):
+        return dict(self._src)
+
+    def __call__(self, normal: torch.Tensor) -> torch.Tensor:
+        from . import ops
+        if self.proj is None:
+            raise RuntimeError("NormalEmbedder has no parameters loaded (load_state_dict(image_proj))")
+        if normal.shape[-1] != self.INPUT_DIM:
+            raise ValueError(f"a normal is [..., {self.INPUT_DIM}], got {tuple(normal.shape)}")
+        x = normal.to(self.device, torch.float32).contiguous()
+        enc = hip.freq_encode(x, self.N_FREQS, self.MAX_FREQ_LOG2)
+        y = ops.linear(enc, self.proj, out_dtype=torch.float32)
+        y = hip.act(y, hip.ACT_GELU_ERF, out=y)
+        return y if self.prec.act == torch.float32 else y.to(self.prec.act)

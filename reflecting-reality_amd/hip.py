@@ -18,7 +18,7 @@ MF_F32, MF_BF16, MF_F16X3, MF_BF16X3, MF_FP8, MF_BF16X1, MF_F16 = 0, 1, 2, 3, 4,
 FP8 = torch.float8_e4m3fn          # OCP e4m3 (gfx950's fp8), 1 byte per element
 ACT_NONE, ACT_SILU, ACT_GEGLU4 = 0, 1, 2
 ACT_QUICK_GELU, ACT_GELU_ERF = 3, 4      # mf_act only (the CLIP text encoders' MLP): mf_gemm_conv has no such epilogue
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class MfhipError(RuntimeError):
@@ -166,6 +166,10 @@ SIGNATURES = {
     "mf_cfg_ddim_step": "i:ppfppffffifplp", "mf_cfg_ddim_step_dev": "i:ppfpppiflp", "mf_cfg_combine": "i:ppfplp", "mf_axpby_n": "i:ppiplp",
     "mf_sizeof_sched_row": "i:", "mf_sched_step_dev": "i:ppfppplp", "mf_mse_loss": "i:pppppilp", "mf_vae_sample": "i:pilppiiifp",
     "mf_nearest_resize": "i:ppiiiiip",
+    # decoupled cross-attention (ABI 23)
+    "mf_attention_ip_bf16": "i:plplplplplpliiiiiiffp", "mf_attention_ip_f16": "i:plplplplplpliiiiiiffp",
+    "mf_attention_ip_f16x3": "i:pplpplpplpplpplpliiiiiiffp", "mf_freq_encode": "i:ppiiifp",
+    "mf_masked_mean_normal": "i:ppplp",
     # image front-end (csrc/frontend.hip)
     "mf_minmax_ws_floats": "l:", "mf_minmax": "i:pplppp", "mf_image_normalize": "i:pplpp", "mf_mask_keep": "i:ppiilp",
     "mf_concat_channels": "i:pppipilp", "mf_postprocess": "i:pppiilip",
@@ -879,6 +883,52 @@ def attention_bf16(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torc
     return out
 
 
+def attention_ip_bf16(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, k_ip: torch.Tensor, vt_ip: torch.Tensor, out: torch.Tensor, *,
+                      ldq: int, ldk: int, ldvt: int, ldk_ip: int, ldvt_ip: int, ldo: int, batch: int, heads: int, sq: int, skv: int,
+                      skv_ip: int, head_dim: int, scale: float, ip_scale: float) -> torch.Tensor:
+    """Decoupled cross-attention in one launch (mf_attention_ip_bf16 / _f16 by q.dtype):
+    out = softmax(q k^T scale) v + ip_scale softmax(q k_ip^T scale) v_ip, 1 <= skv_ip <= 64.  Inference only."""
+    _req_cuda(q, k, vt, k_ip, vt_ip, out)
+    if q.dtype not in (torch.bfloat16, torch.float16) or not (q.dtype == k.dtype == vt.dtype == k_ip.dtype == vt_ip.dtype == out.dtype):
+        raise MfhipError("attention_ip_bf16: bf16 or fp16 q / k / vt / k_ip / vt_ip / out of one dtype")
+    if PROFILE is not None:
+        global PROFILE_ATTN_FLOPS
+        PROFILE_ATTN_FLOPS += 4.0 * batch * heads * sq * (skv + skv_ip) * head_dim
+    _launch("mf_attention_ip_f16" if q.dtype == torch.float16 else "mf_attention_ip_bf16", q, ldq, k, ldk, vt, ldvt, k_ip, ldk_ip, vt_ip,
+            ldvt_ip, out, ldo, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale)
+    return out
+
+
+def attention_ip_f16x3(q, k, vt, k_ip, vt_ip, out: torch.Tensor, *, ldq: int, ldk: int, ldvt: int, ldk_ip: int, ldvt_ip: int, ldo: int,
+                       batch: int, heads: int, sq: int, skv: int, skv_ip: int, head_dim: int, scale: float, ip_scale: float) -> torch.Tensor:
+    """attention_ip_bf16 in split precision: q / k / vt / k_ip / vt_ip are (hi, lo) pairs from split_halves; out fp32."""
+    _req_cuda(*q, *k, *vt, *k_ip, *vt_ip, out)
+    _f32(out)
+    if PROFILE is not None:
+        global PROFILE_ATTN_FLOPS
+        PROFILE_ATTN_FLOPS += 4.0 * batch * heads * sq * (skv + skv_ip) * head_dim
+    _launch("mf_attention_ip_f16x3", q[0], q[1], ldq, k[0], k[1], ldk, vt[0], vt[1], ldvt, k_ip[0], k_ip[1], ldk_ip, vt_ip[0], vt_ip[1],
+            ldvt_ip, out, ldo, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale)
+    return out
+
+
+def freq_encode(x: torch.Tensor, n_freqs: int, max_freq_log2: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [..., in_dim] -> fp32 [..., 2 * n_freqs * in_dim]: cat([sin(x f_0), cos(x f_0), sin(x f_1), ...], -1) with
+    f_i = 2^(i max_freq_log2 / (n_freqs - 1)) (mf_freq_encode: the reference's FreqEncoder, log sampling, no input copy)."""
+    _req_cuda(x, out)
+    _f32(x)
+    if not x.is_contiguous():
+        raise MfhipError("freq_encode: contiguous input")
+    in_dim = x.shape[-1]
+    rows = x.numel() // in_dim
+    if out is None:
+        out = torch.empty(*x.shape[:-1], 2 * n_freqs * in_dim, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.numel() != rows * 2 * n_freqs * in_dim or not out.is_contiguous():
+        raise MfhipError("freq_encode: out is a contiguous fp32 [..., 2 * n_freqs * in_dim] tensor")
+    _launch("mf_freq_encode", x, out, rows, in_dim, n_freqs, float(max_freq_log2))
+    return out
+
+
 def quantize_rows_fp8(x: torch.Tensor, norm=None, eps: float = 1e-5):
     """Per-row dynamic fp8 quantisation of [..., C] (optionally LayerNorm(x; gamma, beta) first): returns
     (q fp8 [..., C], scale fp32 [rows]) with x ~ q * scale[row]."""
@@ -1449,6 +1499,16 @@ def mask_keep(m: torch.Tensor) -> torch.Tensor:
     b, c, h, w = m.shape
     out = torch.empty(b, 1, h, w, dtype=torch.float32, device=m.device)
     _launch("mf_mask_keep", m.contiguous(), out, b, c, h * w)
+    return out
+
+
+def masked_mean_normal(normals: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """[H, W, 3] fp32 normals, [H, W] fp32 mask -> [1, 3]: the mean normal over mask > 0, L2-normalised (mf_masked_mean_normal)."""
+    _f32(normals, mask)
+    if normals.dim() != 3 or normals.shape[-1] != 3 or tuple(mask.shape) != tuple(normals.shape[:2]):
+        raise MfhipError("masked_mean_normal: [H, W, 3] normals and an [H, W] mask")
+    out = torch.empty(1, 3, dtype=torch.float32, device=normals.device)
+    _launch("mf_masked_mean_normal", normals.contiguous(), mask.contiguous(), out, mask.numel())
     return out
 
 

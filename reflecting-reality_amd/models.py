@@ -177,6 +177,8 @@ class HipModel:
         if self.prec.act != F32:
             raise NotImplementedError("training runs with fp32 master weights and activations: build the model with "
                                       "precision='fp32', 'f16x3' or 'bf16x1' (bf16 products, fp32 storage)")
+        if self.__dict__.get("_ip_procs"):
+            raise NotImplementedError("IP-Adapter processors are inference only: the backward pass of the ip branch is not built")
         if requires_grad is not None:
             self._requires_grad = bool(requires_grad)
         src = self.state_dict() if (self.training or self._src is not None) else None
@@ -354,6 +356,8 @@ class HipModel:
         """nn.Module.train(): the MirrorFusion nets have no dropout / batch-norm state (dropout 0.0, resnet.py:393), so the
         only effect is switching the parameters to the training layout the first time."""
         if mode and not self.training:
+            if self.__dict__.get("_ip_procs"):
+                raise NotImplementedError("IP-Adapter processors are inference only: the backward pass of the ip branch is not built")
             self.prepare_training()
         return self
 
@@ -751,6 +755,9 @@ class _UNetCore(HipModel):
             if join is not None:
                 join()
         else:
+            ipw = self._ip_for(b)
+            if ipw is not None:
+                return self._attention_ip(b, x, ctx, heads, residual, fold, ipw)
             skv = ctx.shape[1]
             q = ops.linear(x, P[b + ("to_q_ln" if fold else "to_q")])
             kv = self._cross_kv.get(b)
@@ -763,6 +770,68 @@ class _UNetCore(HipModel):
             else:
                 k, vt = kv[0], kv[1]
         o = ops.attention(q, k, vt, heads, skv, 1.0 / (d ** 0.5), self.prec, c=c)
+        return ops.linear(o, P[b + "to_out.0"], res0=residual)
+
+    def _ip_for(self, b: str):
+        """(to_k_ip, to_v_ip ConvWeights, scale, num_tokens) of the IP processor installed on cross-attention layer `b`, None when the
+        model runs the plain processors.  The device copies of the weights are made on first use, on the device the model is on NOW
+        (a model may be built on the CPU and moved, or moved between devices, after the processors were installed), and again when the
+        processor's weights were written in place; `scale` and `num_tokens` are read from the live processor at every call
+        (`proc.scale = s`, the reference's set_scale idiom).  With IP processors installed every cross-attention layer has one:
+        a layer without is an error, never a silent plain attention."""
+        procs = self.__dict__.get("_ip_procs")
+        if not procs:
+            return None
+        proc = procs.get(b + "processor")
+        if proc is None:
+            raise RuntimeError(f"IP-Adapter processors are installed, but {b}processor has none: the decoupled attention would be dropped")
+        cache = self.__dict__.setdefault("_ip", {})
+        wk, wv = proc.to_k_ip.weight, proc.to_v_ip.weight
+        stamp = (self.device, wk._version, wv._version, wk.data_ptr(), wv.data_ptr())
+        ent = cache.get(b)
+        if ent is None or ent[2] != stamp:
+            ent = cache[b] = (ConvWeight(wk.detach().float(), None, self.prec, self.device),
+                              ConvWeight(wv.detach().float(), None, self.prec, self.device, raw=True),     # V^T: the A operand of ops.linear_t
+                              stamp)
+            self._cross_kv.pop(b, None)
+        return ent[0], ent[1], float(proc.scale), int(proc.num_tokens)
+
+    def ip_signature(self):
+        """What a captured denoise graph bakes in of the IP processors: (scale, num_tokens) per layer, and the install generation."""
+        procs = self.__dict__.get("_ip_procs") or {}
+        return (self.__dict__.get("_proc_gen", 0),) + tuple((float(p.scale), int(p.num_tokens)) for p in procs.values())
+
+    def _ip_project(self, b: str, ctx: torch.Tensor, ipw, bufs=None):
+        """The four prompt-side tensors of an attn2 with an IP processor (ip_adapter/attention_processor.py:350-383): text K / V^T from
+        ctx[:, :S - n] through to_k / to_v, ip K / V^T from ctx[:, S - n:] through to_k_ip / to_v_ip (V^T padded to 8 columns per 8
+        tokens).  `bufs`: the persistent tensors to write into (a captured graph keeps reading their addresses)."""
+        wk, wv, _, n = ipw
+        s = ctx.shape[1]
+        if s - n < 1:
+            raise ValueError(f"encoder_hidden_states has {s} tokens: an IP processor with num_tokens = {n} needs at least {n + 1}")
+        text, ipt = ctx[:, : s - n].contiguous(), ctx[:, s - n:].contiguous()
+        o = bufs if bufs is not None else (None,) * 4
+        k = ops.linear(text, self.P[b + "to_k"], out=o[0])
+        vt = ops.linear_t(text, self.P[b + "to_v"], (s - n + 7) // 8 * 8, out=o[1])
+        k_ip = ops.linear(ipt, wk, out=o[2])
+        vt_ip = ops.linear_t(ipt, wv, (n + 7) // 8 * 8, out=o[3])
+        return k, vt, k_ip, vt_ip
+
+    def _attention_ip(self, b: str, x, ctx: torch.Tensor, heads: int, residual: torch.Tensor, fold: bool, ipw) -> torch.Tensor:
+        """attn2 under an IP processor: out = to_out(sdpa(q, k, v) + scale * sdpa(q, k_ip, v_ip)) in one attention launch.  All four
+        prompt-side tensors live in _cross_kv under the prompt's generation counter, like K / V^T of the plain layer."""
+        P = self.P
+        c = (x[0] if isinstance(x, tuple) else x).shape[-1]
+        d = c // heads
+        n = ipw[3]
+        q = ops.linear(x, P[b + ("to_q_ln" if fold else "to_q")])
+        kv = self._cross_kv.get(b)
+        if kv is None or len(kv) != 5 or kv[-1] != self._ehs_gen or kv[0].shape[1] != ctx.shape[1] - n:
+            reuse = kv is not None and len(kv) == 5 and kv[0].shape[0] == ctx.shape[0] and kv[0].shape[1] == ctx.shape[1] - n
+            kv = self._ip_project(b, ctx, ipw, kv[:4] if reuse else None) + (self._ehs_gen,)
+            self._cross_kv[b] = kv
+        k, vt, k_ip, vt_ip = kv[:4]
+        o = ops.attention(q, k, vt, heads, ctx.shape[1] - n, 1.0 / (d ** 0.5), self.prec, c=c, ip=(k_ip, vt_ip, n, ipw[2]))
         return ops.linear(o, P[b + "to_out.0"], res0=residual)
 
     def _vt_buffer(self, x: torch.Tensor, c: int, skv: int) -> Optional[torch.Tensor]:
@@ -798,7 +867,17 @@ class _UNetCore(HipModel):
             return False
         ctx = self._bind_prompt(encoder_hidden_states)
         for b, kv in list(self._cross_kv.items()):
-            if kv[2] == self._ehs_gen:
+            if kv[-1] == self._ehs_gen:
+                continue
+            ipw = self._ip_for(b)
+            if b not in self._cross_kv:               # the layer's weights were rebuilt: an eager forward makes the buffers again
+                return False
+            if (ipw is None) != (len(kv) == 3):       # processors changed since the buffers were made
+                return False
+            if ipw is not None:
+                if kv[0].shape[0] != ctx.shape[0] or kv[0].shape[1] != ctx.shape[1] - ipw[3]:
+                    return False
+                self._cross_kv[b] = self._ip_project(b, ctx, ipw, kv[:4]) + (self._ehs_gen,)
                 continue
             if kv[0].shape[:2] != ctx.shape[:2]:
                 return False
@@ -905,7 +984,19 @@ class _UNetCore(HipModel):
         """One entry per attention layer, keyed like the reference ("...attn1.processor"); every layer runs the HIP
         attention of this library."""
         from .attn_processor import MfhipAttnProcessor
-        return {k[: -len("to_q")] + "processor": MfhipAttnProcessor() for k in self.P if k.endswith(".to_q")}
+        installed = self.__dict__.get("_ip_procs") or {}
+        return {name: installed.get(name) or MfhipAttnProcessor() for name in self._processor_names()}
+
+    def _processor_names(self) -> List[str]:
+        """The reference's attn_processors keys in the reference's order (unet_2d_condition.py:716-748 walks named_children:
+        down_blocks, up_blocks, mid_block): index i of this list is the "<i>." of an ip-adapter.bin's "ip_adapter" keys."""
+        names = [k[: -len("to_q")] + "processor" for k in self.P if k.endswith(".to_q")]
+        rank = {"down_blocks": 0, "up_blocks": 1, "mid_block": 2}
+
+        def order(name):
+            parts = name.split(".")
+            return (rank[parts[0]],) + tuple(int(x) for x in parts if x.isdigit()) + (parts[-2],)
+        return sorted(names, key=order)
 
     def set_attn_processor(self, processor) -> None:
         """The reference lets a caller swap the attention arithmetic per layer.  Here attention is fused into the HIP graph
@@ -913,8 +1004,8 @@ class _UNetCore(HipModel):
         `MfhipAttnProcessor` (the same kernel, exposed on the reference's processor ABI for use inside the reference's own
         modules).  Passing it — or a dict of it with exactly the reference's keys — is accepted; anything else is refused
         instead of being silently ignored."""
-        from .attn_processor import MfhipAttnProcessor
-        keys = set(self.attn_processors)
+        from .attn_processor import MfhipAttnProcessor, MfhipIPAttnProcessor
+        keys = set(self._processor_names())
         if isinstance(processor, dict):
             if len(processor) != len(keys):
                 raise ValueError(f"A dict of processors was passed, but the number of processors {len(processor)} does not match the"
@@ -922,9 +1013,86 @@ class _UNetCore(HipModel):
             procs = list(processor.values())
         else:
             procs = [processor]
+        if isinstance(processor, dict) and any(isinstance(p, MfhipIPAttnProcessor) for p in procs):
+            return self._install_ip(processor, keys)
         if not all(isinstance(p, MfhipAttnProcessor) for p in procs):
             raise NotImplementedError("the HIP models run their own fused attention: only MfhipAttnProcessor is accepted "
                                       "(use it with the reference's modules to run this kernel there)")
+        if self.__dict__.get("_ip_procs"):           # back to the plain processors everywhere
+            self._ip, self._ip_procs, self._cross_kv = {}, {}, {}
+            self._proc_gen = self.__dict__.get("_proc_gen", 0) + 1
+
+    def _install_ip(self, processor: Dict[str, Any], keys) -> None:
+        """The 'ip_adapter' normals mode (train_brushnet_mirror.py:1002-1024): every attn2 carries an IP processor (decoupled
+        cross-attention over the last num_tokens prompt rows), every attn1 the plain one.  SD1.5 UNet, inference only."""
+        from .attn_processor import MfhipAttnProcessor, MfhipIPAttnProcessor
+        if self._class_name != "UNet2DConditionModel" or self.config.get("addition_embed_type") or self.config.get("use_linear_projection"):
+            raise NotImplementedError("IP-Adapter processors are built for the SD1.5 UNet only (BrushNet never sees the ip tokens; SDXL is out of scope)")
+        if self.training:
+            raise NotImplementedError("IP-Adapter processors are inference only: the backward pass of the ip branch is not built")
+        if set(processor) != set(keys):
+            raise ValueError(f"the processor dict must carry exactly the keys of attn_processors; unknown: {sorted(set(processor) - set(keys))[:3]}")
+        cross = self.config["cross_attention_dim"]
+        held = {}
+        for name, proc in processor.items():
+            b = name[: -len("processor")]
+            if ".attn1." in name:
+                if type(proc) is not MfhipAttnProcessor:
+                    raise NotImplementedError(f"{name}: self-attention takes MfhipAttnProcessor")
+                continue
+            if not isinstance(proc, MfhipIPAttnProcessor):
+                raise NotImplementedError(f"{name}: with IP processors installed every attn2 takes an MfhipIPAttnProcessor")
+            hidden = self.P[b + "to_q"].n
+            wk, wv = proc.to_k_ip.weight.detach(), proc.to_v_ip.weight.detach()
+            if tuple(wk.shape) != (hidden, cross) or tuple(wv.shape) != (hidden, cross):
+                raise ValueError(f"{name}: to_k_ip / to_v_ip must be [{hidden}, {cross}], got {tuple(wk.shape)} / {tuple(wv.shape)}")
+            if not 1 <= proc.num_tokens <= 64:
+                raise ValueError(f"{name}: num_tokens = {proc.num_tokens} (the ip segment is one key tile: 1 .. 64)")
+            held[name] = proc
+        self._ip, self._ip_procs, self._cross_kv = {}, held, {}              # (_ip: the device weights, made by _ip_for on first use)
+        self._proc_gen = self.__dict__.get("_proc_gen", 0) + 1
+
+    def load_ip_adapter(self, state_or_path, scale: float = 1.0, num_tokens: int = 4) -> Dict[str, torch.Tensor]:
+        """Bind an `ip_adapter/ip-adapter.bin` of the reference (train_brushnet_mirror.py:1026-1049: torch.save({"image_proj":
+        normal_proj.state_dict(), "ip_adapter": ModuleList(unet.attn_processors.values()).state_dict()})): key "<i>.to_k_ip.weight"
+        belongs to processor i in the reference's attn_processors order (odd i: the attn2 layers).  Installs an
+        MfhipIPAttnProcessor(scale, num_tokens) on every attn2 and returns the "image_proj" dict (frontend.NormalEmbedder loads it)."""
+        from .attn_processor import MfhipAttnProcessor, MfhipIPAttnProcessor
+        state = torch.load(state_or_path, map_location="cpu") if isinstance(state_or_path, (str, bytes, os.PathLike)) else state_or_path
+        if "ip_adapter" not in state or "image_proj" not in state:
+            raise ValueError('an ip-adapter checkpoint is {"image_proj": ..., "ip_adapter": ...}')
+        sd = state["ip_adapter"]
+        names = self._processor_names()
+        want = {f"{i}.{w}.weight" for i, n in enumerate(names) if ".attn2." in n for w in ("to_k_ip", "to_v_ip")}
+        if set(sd) != want:
+            raise ValueError(f"ip_adapter keys do not match this UNet's attn2 layers: missing {sorted(want - set(sd))[:3]}, "
+                             f"unexpected {sorted(set(sd) - want)[:3]}")
+        cross = self.config["cross_attention_dim"]
+        procs = {}
+        for i, n in enumerate(names):
+            if ".attn1." in n:
+                procs[n] = MfhipAttnProcessor()
+                continue
+            wk = sd[f"{i}.to_k_ip.weight"]
+            proc = MfhipIPAttnProcessor(wk.shape[0], cross, scale=scale, num_tokens=num_tokens)
+            with torch.no_grad():
+                proc.to_k_ip.weight.copy_(wk.float())
+                proc.to_v_ip.weight.copy_(sd[f"{i}.to_v_ip.weight"].float())
+            procs[n] = proc
+        self.set_attn_processor(procs)
+        return dict(state["image_proj"])
+
+    def ip_adapter_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The "ip_adapter" dict of an ip-adapter.bin from the installed processors (the layout load_ip_adapter reads)."""
+        held = self.__dict__.get("_ip_procs") or {}
+        if not held:
+            raise ValueError("no IP processors are installed")
+        out = OrderedDict()
+        for i, n in enumerate(self._processor_names()):
+            if n in held:
+                out[f"{i}.to_k_ip.weight"] = held[n].to_k_ip.weight.detach().clone()
+                out[f"{i}.to_v_ip.weight"] = held[n].to_v_ip.weight.detach().clone()
+        return out
 
     def set_default_attn_processor(self) -> None:
         return None

@@ -593,13 +593,51 @@ FLASH_SPLIT_HEAD_DIMS = (8, 40, 64, 80)          # 160 (two split K / V^T planes
 FLASH_CAUSAL_HEAD_DIMS = (8, 64)                 # mf_attention_causal_*: both CLIP text encoders and the tiny test configs
 
 
+def _attention_ip(q, k, vt, heads, skv, scale, prec, c, ip):
+    """attention(ip=...): out = softmax(q k^T scale) v + ip_scale softmax(q k_ip^T scale) v_ip, each softmax over its own keys."""
+    k_ip, vt_ip, skv_ip, ip_scale = ip
+    b, sq, _ = q.shape
+    d = c // heads
+    if not 1 <= skv_ip <= 64 or k_ip.shape[1] < skv_ip or vt_ip.shape[-1] < skv_ip or vt_ip.shape[-1] % 8:
+        raise hip.MfhipError(f"attention(ip=): 1 <= skv_ip <= 64 keys in k_ip [B, >= skv_ip, C] and vt_ip [B, C, ld % 8 == 0] (got {skv_ip}, "
+                             f"{tuple(k_ip.shape)}, {tuple(vt_ip.shape)})")
+    if k_ip.shape[1] != skv_ip:
+        k_ip = k_ip[:, :skv_ip]
+    if prec.half and d in FLASH_HEAD_DIMS:
+        if k_ip.stride(0) != skv_ip * k_ip.stride(1):
+            k_ip = k_ip.contiguous()
+        out = torch.empty(b, sq, c, dtype=prec.compute, device=q.device)
+        return hip.attention_ip_bf16(q, k, vt, k_ip, vt_ip, out, ldq=q.stride(1), ldk=k.stride(1), ldvt=vt.shape[-1], ldk_ip=k_ip.stride(1),
+                                     ldvt_ip=vt_ip.shape[-1], ldo=c, batch=b, heads=heads, sq=sq, skv=skv, skv_ip=skv_ip, head_dim=d,
+                                     scale=scale, ip_scale=ip_scale)
+    if prec.code == hip.MF_F16X3 and d in FLASH_SPLIT_HEAD_DIMS and vt.shape[-1] % 8 == 0:
+        qs, ks, vs = hip.split_halves(q.contiguous()), hip.split_halves(k.contiguous()), hip.split_halves(vt)
+        kis, vis = hip.split_halves(k_ip.contiguous()), hip.split_halves(vt_ip)
+        out = torch.empty(b, sq, c, dtype=torch.float32, device=q.device)
+        return hip.attention_ip_f16x3(qs, ks, vs, kis, vis, out, ldq=c, ldk=c, ldvt=vt.shape[-1], ldk_ip=c, ldvt_ip=vt_ip.shape[-1], ldo=c,
+                                      batch=b, heads=heads, sq=sq, skv=skv, skv_ip=skv_ip, head_dim=d, scale=scale, ip_scale=ip_scale)
+    # fp32, and f16x3 at head dim 160: two unfused attentions and one fp32 combine
+    q, k, k_ip = q.contiguous(), k.contiguous(), k_ip.contiguous()
+    o_text = attention_unfused(q, k, vt, heads, skv, scale, prec)
+    o_ip = attention_unfused(q, k_ip, vt_ip, heads, skv_ip, scale, prec)
+    if o_text.dtype != torch.float32:      # a 16-bit mode at a head dim without a flash kernel (no model of this library has one in attn2)
+        return hip.axpby_n([o_text.float(), o_ip.float()], [1.0, float(ip_scale)]).to(o_text.dtype)
+    return hip.axpby_n([o_text, o_ip], [1.0, float(ip_scale)])
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, skv: int, scale: float,
-              prec: Precision, c: Optional[int] = None, causal: bool = False) -> torch.Tensor:
+              prec: Precision, c: Optional[int] = None, causal: bool = False, ip=None) -> torch.Tensor:
     """q: [B, Sq, ldq] and k: [B, Skv, ldk] may be column slices of a fused projection (`c` = model width).
-    causal: query i attends keys 0 .. i (the CLIP text encoders; sq == skv, inference only)."""
+    causal: query i attends keys 0 .. i (the CLIP text encoders; sq == skv, inference only).
+    ip = (k_ip [B, skv_ip, C], vt_ip [B, C, ld], skv_ip, ip_scale): decoupled cross-attention, the second key / value segment of the
+    reference's IPAttnProcessor2_0 with a softmax of its own (inference only, no causal mask)."""
     b, sq, ldq = q.shape
     c = c or ldq
     d = c // heads
+    if ip is not None:
+        if TAPE is not None or causal:
+            raise hip.MfhipError("attention(ip=): inference only and no causal mask")
+        return _attention_ip(q, k, vt, heads, skv, scale, prec, c, ip)
     if causal:
         if TAPE is not None or sq != skv:
             raise hip.MfhipError(f"attention(causal=True): inference only and sq == skv (got {sq}, {skv})")

@@ -130,8 +130,15 @@ class StableDiffusionBrushNetPipeline:
             raise NotImplementedError("the safety checker (a CLIP vision model) is outside the accelerated path; "
                                       "pass safety_checker=None as examples/brushnet/test_brushnet.py:150 does")
         for nm, mode in (("depth", depth_conditioning_mode), ("normals", normals_conditioning_mode)):
+            if nm == "normals" and mode == "ip_adapter":
+                # train_brushnet_mirror.py:752-756, 868-871: the mirror normal enters as ONE extra prompt token of the UNet (decoupled
+                # cross-attention, MfhipIPAttnProcessor on every attn2); no normals map joins the BrushNet conditioning
+                if type(self).__name__ != "StableDiffusionBrushNetPipeline":
+                    raise NotImplementedError("normals_conditioning_mode='ip_adapter' is built for the SD1.5 pipeline")
+                continue
             if mode not in (None, "concat", "latents"):
-                raise ValueError(f"{nm}_conditioning_mode must be None, 'concat' or 'latents', got {mode!r}")
+                raise ValueError(f"{nm}_conditioning_mode must be None, 'concat' or 'latents'" + (" or 'ip_adapter'" if nm == "normals" else "")
+                                 + f", got {mode!r}")
         self.vae, self.text_encoder, self.tokenizer = vae, text_encoder, tokenizer
         self.unet, self.brushnet, self.scheduler = unet, brushnet, scheduler
         self.safety_checker, self.feature_extractor, self.image_encoder = safety_checker, feature_extractor, image_encoder
@@ -163,6 +170,8 @@ class StableDiffusionBrushNetPipeline:
         self.fold_zero_convs = os.environ.get("MFHIP_ZC_FOLD") == "1"
         self._added_cond = None          # SDXL: added_cond_kwargs of the (CFG-duplicated) batch, set by the XL subclass
         self._graph_state = None
+        self.normal_embedder = None      # 'ip_adapter' normals mode: a frontend.NormalEmbedder turns `normals=` [B, 1, 3] into the ip token
+        self._pe_unet = None             # ... and the UNet's prompt embeddings with that token appended (BrushNet keeps the text's 77)
 
     # ---- loading / saving (pipelines/pipeline_utils.py:148-296 save_pretrained, :465-919 from_pretrained) ---------
     _scheduler_classes = ("DDIMScheduler", "PNDMScheduler", "UniPCMultistepScheduler")
@@ -345,7 +354,7 @@ class StableDiffusionBrushNetPipeline:
                 raise TypeError(f"`{nm}` must be passed (PIL image, numpy array, torch tensor or a list of those)")
         if self.depth_conditioning_mode is not None and depth is None:
             raise ValueError(f"depth_conditioning_mode={self.depth_conditioning_mode!r} needs a `depth` input")
-        if self.normals_conditioning_mode is not None and normals is None:
+        if self.normals_conditioning_mode not in (None, "ip_adapter") and normals is None:
             raise ValueError(f"normals_conditioning_mode={self.normals_conditioning_mode!r} needs a `normals` input")
         if not isinstance(brushnet_conditioning_scale, float):
             raise TypeError("For single brushnet: `brushnet_conditioning_scale` must be type `float`.")
@@ -464,7 +473,7 @@ class StableDiffusionBrushNetPipeline:
             else:
                 for ps, h in zip(parts, encode_sample(d.repeat(1, 3, 1, 1), noises[1])):           # :1203-1206
                     ps.append(h)
-        if self.normals_conditioning_mode is not None:
+        if self.normals_conditioning_mode not in (None, "ip_adapter"):
             nrm = self.prepare_image(normals, width, height, batch, num_images_per_prompt)
             if self.normals_conditioning_mode == "concat":
                 nl = hip.nearest_resize(hip.h2d(nrm, self.device), hl, wl)                         # :1208-1212
@@ -493,8 +502,14 @@ class StableDiffusionBrushNetPipeline:
                  conditioning_noise: Optional[torch.Tensor] = None, _timing: Optional[dict] = None, **kwargs):
         callback = kwargs.pop("callback", None)
         callback_steps = kwargs.pop("callback_steps", None)
-        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-            raise NotImplementedError("IP-Adapter inputs are outside the BASELINE configs (SURVEY.md §2 #14)")
+        ip_mode = self.normals_conditioning_mode == "ip_adapter"
+        if ip_adapter_image is not None:
+            raise NotImplementedError("ip_adapter_image (the CLIP vision tower of an image-prompt IP-Adapter) is not built")
+        if ip_adapter_image_embeds is not None and not ip_mode:
+            raise NotImplementedError("ip_adapter_image_embeds are taken in normals_conditioning_mode='ip_adapter' only (the mirror normal's token)")
+        if ip_mode and not getattr(self.unet, "_ip_procs", None):
+            raise ValueError("normals_conditioning_mode='ip_adapter' needs IP-Adapter processors on the UNet: unet.load_ip_adapter(...) or "
+                             "unet.set_attn_processor({...attn2.processor: MfhipIPAttnProcessor(...)})")
         if cross_attention_kwargs:
             raise NotImplementedError("cross_attention_kwargs (LoRA scale) are not built")
         if timesteps is not None:
@@ -527,6 +542,10 @@ class StableDiffusionBrushNetPipeline:
         pe = torch.cat([negative_prompt_embeds, prompt_embeds]) if do_cfg else prompt_embeds         # :1103
         pe = pe.to(self.device)
         nb = batch_size * num_images_per_prompt
+        self._pe_unet = (self._append_normal_token(pe, batch_size, num_images_per_prompt, do_cfg, normals, ip_adapter_image_embeds)
+                         if ip_mode else None)
+        if ip_mode:
+            normals = None                    # a [B, 1, 3] vector, consumed above: no normals map enters the conditioning
 
         first = image[0] if isinstance(image, list) else image
         if height is None or width is None:
@@ -586,7 +605,8 @@ class StableDiffusionBrushNetPipeline:
                     down = [torch.cat([torch.zeros_like(d), d]) for d in down]
                     mid = torch.cat([torch.zeros_like(mid), mid])
                     up = [torch.cat([torch.zeros_like(u), u]) for u in up]
-                eps = self.unet(x_in, t, encoder_hidden_states=pe, down_block_add_samples=down,
+                eps = self.unet(x_in, t, encoder_hidden_states=pe if self._pe_unet is None else self._pe_unet,
+                                down_block_add_samples=down,
                                 mid_block_add_sample=mid, up_block_add_samples=up, added_cond_kwargs=self._added_cond,
                                 return_dict=False)[0]                                                # :1296
                 if do_cfg:
@@ -635,6 +655,34 @@ class StableDiffusionBrushNetPipeline:
         if not return_dict:
             return (img, None)
         return StableDiffusionPipelineOutput(images=img, nsfw_content_detected=None)
+
+    def _append_normal_token(self, pe: torch.Tensor, batch: int, per_prompt: int, do_cfg: bool, normals, embeds) -> torch.Tensor:
+        """MirrorFusionModel.forward (train_brushnet_mirror.py:868-871): encoder_hidden_states = cat([text, ip_tokens], dim=1) for the UNet
+        only.  `embeds`: [t] with t [2B or B, 1, C], what the reference's get_normal_embeds returns (:75-88: the same token in both
+        classifier-free-guidance halves); or `normals` [B, 1, 3] through self.normal_embedder.  B is the number of prompts.  `pe` is [negative | positive], each half prompt-major (p0, p0, p1, p1 for two images per prompt:
+        encode_prompt's repeat + view), so the token of prompt i is repeated in place for its images, never tiled across prompts."""
+        if embeds is not None:
+            tok = embeds[0] if isinstance(embeds, (list, tuple)) else embeds
+        else:
+            if normals is None or self.normal_embedder is None:
+                raise ValueError("normals_conditioning_mode='ip_adapter' takes ip_adapter_image_embeds=[token], or normals=[B, 1, 3] with "
+                                 "pipe.normal_embedder set (frontend.NormalEmbedder)")
+            nv = torch.as_tensor(normals, dtype=torch.float32)
+            if nv.dim() == 2:
+                nv = nv[:, None, :]
+            tok = self.normal_embedder(nv)
+        tok = tok.to(pe.device, pe.dtype)
+        if tok.dim() != 3 or tok.shape[1] != 1 or tok.shape[2] != pe.shape[2]:
+            raise ValueError(f"the normal token must be [B, 1, {pe.shape[2]}], got {tuple(tok.shape)}")
+        rows = tok.shape[0]
+        if rows == batch:                             # one token per prompt: the same in every guidance half
+            parts = [tok] * (2 if do_cfg else 1)
+        elif do_cfg and rows == 2 * batch:            # get_normal_embeds' [unconditional | conditional] stack
+            parts = [tok[:batch], tok[batch:]]
+        else:
+            raise ValueError(f"the normal token's batch is {rows}: expected one token per prompt ({batch})"
+                             + (f" or the two guidance halves stacked ({2 * batch})" if do_cfg else ""))
+        return torch.cat([pe, torch.cat([t.repeat_interleave(per_prompt, dim=0) for t in parts])], 1).contiguous()
 
     def _brushnet_shareable(self, cond: torch.Tensor, nb: int, do_cfg: bool) -> bool:
         """Under classifier-free guidance the reference feeds BrushNet the duplicated batch (pipeline_brushnet.py:1256-1277:
@@ -702,7 +750,8 @@ class StableDiffusionBrushNetPipeline:
         added = self._added_cond
         key = (tuple(latents.shape), tuple(pe.shape), tuple(cond.shape), float(guidance_scale), cond_scale, ptype, clip,
                str(dev), id(self.unet), self.unet._weights_gen, id(self.brushnet), self.brushnet._weights_gen, self._brushnet_once,
-               tuple((k, tuple(v.shape)) for k, v in sorted(added.items())) if added else None)
+               tuple((k, tuple(v.shape)) for k, v in sorted(added.items())) if added else None,
+               tuple(self._pe_unet.shape) if self._pe_unet is not None else None, self.unet.ip_signature() if hasattr(self.unet, "ip_signature") else None)
         st = self._graph_state if self._graph_state is not None and self._graph_state["key"] == key else None
         if st is None:
             st = dict(key=key, graph=None, lat=torch.empty_like(latents), pe=torch.empty_like(pe),
@@ -710,6 +759,8 @@ class StableDiffusionBrushNetPipeline:
                       coef_cur=torch.empty(4, dtype=torch.float32, device=dev))
             if added:
                 st["added"] = {k: torch.empty(v.shape, dtype=torch.float32, device=dev) for k, v in added.items()}
+            if self._pe_unet is not None:
+                st["pe_unet"] = torch.empty_like(self._pe_unet)
             if plan is not None:                                 # the step's mf_sched_row, and the scheduler's history (persists between steps)
                 st["row_cur"] = torch.empty(plan.rows.shape[1], dtype=torch.int32, device=dev)
                 st["state"] = torch.empty((max(plan.nslots, 1),) + tuple(latents.shape), dtype=torch.float32, device=dev)
@@ -725,6 +776,10 @@ class StableDiffusionBrushNetPipeline:
         st["pe"].copy_(pe)
         st["cond"].copy_(cond)
         pe, cond = st["pe"], st["cond"]
+        pe_u = pe                                             # what the UNet reads: the 'ip_adapter' normals mode appends its token
+        if self._pe_unet is not None:
+            st["pe_unet"].copy_(self._pe_unet)
+            pe_u = st["pe_unet"]
         # every timestep is known here: both nets' time embeddings and the fused time_emb_proj GEMM run ONCE for
         # the whole schedule (4 batched launches per net) instead of 8 dependent launches at the head of every step; the
         # graph reads one row block per step from a static buffer.  Kept across calls with the same schedule.
@@ -750,7 +805,7 @@ class StableDiffusionBrushNetPipeline:
                                           brushnet_cond=cond[:nb] if once else cond,
                                           conditioning_scale=cond_scale, added_cond_kwargs=added, return_dict=False, _temb=temb_b,
                                           _lazy=lazy)
-            eps = self.unet(x_in, t_cur, encoder_hidden_states=pe, down_block_add_samples=down,
+            eps = self.unet(x_in, t_cur, encoder_hidden_states=pe_u, down_block_add_samples=down,
                             mid_block_add_sample=mid, up_block_add_samples=up, added_cond_kwargs=added,
                             return_dict=False, _temb=temb_u)[0]
             if fused_ddim:
@@ -766,7 +821,7 @@ class StableDiffusionBrushNetPipeline:
         if export is not None:
             st["graph"] = None                                    # (a graph kept from an earlier call is captured again)
         replay_all = (export is None and st["graph"] is not None and os.environ.get("MFHIP_EAGER_FIRST") != "1"      # A/B switch
-                      and self.unet.bind_prompt(pe))
+                      and self.unet.bind_prompt(pe_u))
         for i in range(len(ts)):
             t_cur.copy_(tvals[i:i + 1])
             if fused_ddim:
@@ -867,6 +922,8 @@ class StableDiffusionBrushNetPipeline:
             raise ValueError(f"export_denoise_step: scheduler must be 'host' or 'device', not {scheduler!r}")
         if scheduler == "device" and not isinstance(self.scheduler, (DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler)):
             raise NotImplementedError(f"{type(self.scheduler).__name__} has no device update")
+        from . import program
+        program.refuse_ip_processors(self.unet)      # before anything is captured (the recorder would refuse in the middle of a two-stream capture)
         self._export_step_to, self._export_sched, self._export_info = path, scheduler, None
         try:
             call_kwargs.setdefault("output_type", "latent")

@@ -678,6 +678,15 @@ def export_vae_encode(vae, path: str, image: torch.Tensor) -> dict:
     return info
 
 
+def refuse_ip_processors(unet) -> None:
+    """A UNet with IP-Adapter processors launches mf_attention_ip_* (not in _REPLAYABLE: the recorder's proxy would raise this very
+    error at the launch) and keeps four prompt-side tensors per layer that export_bind_prompt does not know: refused up front."""
+    if getattr(unet, "_ip_procs", None):
+        name = {"f16x3": "mf_attention_ip_f16x3", "fp16": "mf_attention_ip_f16"}.get(unet.prec.name, "mf_attention_ip_bf16")
+        raise ProgramError(f"{name} has no replay thunk (program.SIGNATURES / csrc/program.hip): it cannot be part of an exported program "
+                           "(the UNet carries IP-Adapter processors)")
+
+
 def export_bind_prompt(unet, path: str) -> dict:
     """What depends on the prompt alone — K and V^T of every cross-attention layer (attention_processor.py:1246-1252: to_k / to_v of
     the prompt embeddings) — as a program: io buffer "prompt_embeds" ([2B, 77, C] in the model's storage dtype, [negative | positive]
@@ -688,6 +697,7 @@ def export_bind_prompt(unet, path: str) -> dict:
     from . import ops
     if not unet._cross_kv or getattr(unet, "_ehs_val", None) is None:
         raise ProgramError("export_bind_prompt: run the UNet (or the pipeline) once first: the K / V^T buffers do not exist yet")
+    refuse_ip_processors(unet)
     ctx = unet._ehs_val
     skv = ctx.shape[1]
 

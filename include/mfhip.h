@@ -19,6 +19,11 @@
  * ABI 23 adds the reference's 'ip_adapter' normals mode (examples/brushnet/train_brushnet_mirror.py:752-756, 858-888): decoupled
  * cross-attention in one launch (mf_attention_ip_bf16 / _f16 / _f16x3), the frequency encoder of the mirror normal (mf_freq_encode)
  * and the mean normal over the mirror mask (mf_masked_mean_normal).  These entries are not part of step programs.
+ *
+ * Appended since (no struct changed, so the version stays 23): mf_u8_to_planes (uint8 NHWC pixels -> fp32 NCHW planes in [0, 1], the
+ * ingest of a host that decoded an image file) and the step-level entries mf_encode_prompt / mf_build_conditioning / mf_decode_image,
+ * which with mf_denoise_step_fused run a whole inpainting call from step programs: token ids, pixels, mask and depth in, a uint8
+ * image out (examples/c_host/inpaint_host.c).
  */
 #ifndef MFHIP_H
 #define MFHIP_H
@@ -535,6 +540,13 @@ int mf_bicubic_aa_resize_crop(const float* src, float* dst, int32_t planes, int3
                               int32_t crop_top, int32_t crop_left, int32_t h_out, int32_t w_out, float a, float b, void* stream);
 /* y[c][p] = a * x[p][c] + b: HWC -> CHW with Normalize([0.5], [0.5]) (apply_transforms_normals, dataset.py:184-192) */
 int mf_hwc_to_chw_affine(const float* x, float* y, int64_t hw, int32_t channels, float a, float b, void* stream);
+/* uint8 NHWC pixels (what a host holds after decoding an image file) -> fp32 NCHW planes in [0, 1]:
+ * dst[b][c][p] = (float)src[b][p][c % channels_in] / 255.0f, a true fp32 division — bit for bit what
+ * numpy.asarray(img).astype(np.float32) / 255.0 gives (VaeImageProcessor.preprocess for a PIL image, image_processor.py:471-480).
+ * channels_out == channels_in, or channels_in == 1 with channels_out > 1: the grey plane is replicated (a mask the reference turns
+ * into three equal channels with .convert("RGB")). */
+int mf_u8_to_planes(const void* src_u8_nhwc, float* dst_nchw, int32_t batch, int32_t channels_in, int32_t channels_out, int64_t hw,
+                    void* stream);
 
 /* ============================================================================================
  * Training: the backward pass and the optimizer of examples/brushnet/train_brushnet_mirror.py:1459-1466
@@ -734,6 +746,24 @@ int mf_vae_decode(mf_program* vae_decoder, const void* z, void* image_out, void*
 /* AutoencoderKL.encode up to the posterior's moments (autoencoder_kl.py:256-291, vae.py:137-167 + quant_conv): io buffers "image"
  * (NCHW fp32) and "moments" (NHWC fp32 [b][h/8][w/8][2 * latent_channels]: mean | logvar, what mf_vae_sample reads; written). */
 int mf_vae_encode_moments(mf_program* vae_encoder, const void* image, void* moments_out, void* stream);
+/* The two ends of a call around the denoise loop, so that a host runs pipeline_brushnet.py:848-1363 from programs alone
+ * (pipe.export_call writes the five files and a manifest; examples/c_host/inpaint_host.c runs them).  Each of the three entries below
+ * refuses a program whose meta names another entry, binds the io buffers it is given (NULL keeps a binding) and runs the program.
+ *
+ * mf_encode_prompt: CLIPTextModel under encode_prompt (pipeline_brushnet.py:271-450, clip_skip included): io buffers "input_ids"
+ * (int32 [2B][77]: the negative prompts' rows, then the positive ones') and "prompt_embeds" ([2B][77][C] in the model's storage dtype,
+ * written — the very buffer the prompt-binding program reads: bind one allocation to both).  Token ids are CLAMPED into the vocabulary
+ * (mf_embed_tokens's rule); checking them is the host's job. */
+int mf_encode_prompt(mf_program* text_encoder, const int32_t* input_ids, void* prompt_embeds, void* stream);
+/* pipeline_brushnet.py:1116-1215: io buffers "image_u8" / "mask_u8" (uint8 [B][H][W][3]), "depth" (fp32 [B][1][H][W] in [-1, 1]; only
+ * a program exported with depth conditioning has it: pass NULL otherwise), "cond_noise" (the VAE posterior noise, fp32 NCHW at latent
+ * resolution: B images when both guidance halves share one draw, else 2B — the program's meta says which) and "cond" (the denoise
+ * step's conditioning buffer, written). */
+int mf_build_conditioning(mf_program* conditioning, const void* image_u8, const void* mask_u8, const float* depth, const float* cond_noise,
+                          void* cond, void* stream);
+/* pipeline_brushnet.py:1342 and VaeImageProcessor.postprocess: latents / scaling_factor, AutoencoderKL.decode, mf_postprocess: io
+ * buffers "latents" (NCHW fp32, the denoise step's) and "image_u8" (uint8 [B][H][W][3], written). */
+int mf_decode_image(mf_program* decoder, const void* latents, void* image_u8, void* stream);
 /* the device copies / fills a recorded pass contains (torch made them between the launches): hipMemcpy2DAsync / hipMemsetAsync */
 int mf_memcpy2d(void* dst, int64_t dpitch, const void* src, int64_t spitch, int64_t width_bytes, int64_t height, void* stream);
 int mf_memset(void* dst, int32_t value, int64_t bytes, void* stream);

@@ -290,7 +290,62 @@ __global__ __launch_bounds__(256) void hwc_to_chw_affine_kernel(const float* x, 
     }
 }
 
+// uint8 NHWC -> fp32 NCHW planes in [0, 1] (what numpy's astype(float32) / 255.0 gives: a correctly rounded fp32 division, never a
+// multiplication by 1/255, which differs in the last bit for some of the 256 values).  Four pixels per thread: 4 * CI bytes come in
+// as CI dword loads when the address allows it, each plane gets one 16-byte store when ITS address allows it (hw odd: bytes / scalars).
+template <int CI>
+__global__ __launch_bounds__(256) void u8_to_planes_kernel(const unsigned char* src, float* dst, int batch, int co, int64_t hw) {
+    const int64_t groups = (hw + 3) / 4, total = (int64_t)batch * groups;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / groups, p = (i - b * groups) * 4;
+        const int np = hw - p < 4 ? (int)(hw - p) : 4;
+        const unsigned char* sp = src + (b * hw + p) * CI;
+        unsigned char px[4 * CI];
+        if (np == 4 && ((uintptr_t)sp & 3) == 0) {
+#pragma unroll
+            for (int w = 0; w < CI; ++w) {
+                const unsigned v = reinterpret_cast<const unsigned*>(sp)[w];
+                px[4 * w] = v & 0xff; px[4 * w + 1] = (v >> 8) & 0xff; px[4 * w + 2] = (v >> 16) & 0xff; px[4 * w + 3] = v >> 24;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4 * CI; ++k) px[k] = k < np * CI ? sp[k] : 0;
+        }
+#pragma unroll
+        for (int sc = 0; sc < CI; ++sc) {
+            float4 v;
+            v.x = __fdiv_rn((float)px[sc], 255.0f); v.y = __fdiv_rn((float)px[CI + sc], 255.0f);
+            v.z = __fdiv_rn((float)px[2 * CI + sc], 255.0f); v.w = __fdiv_rn((float)px[3 * CI + sc], 255.0f);
+            const int c_end = CI == 1 ? co : sc + 1;          // a single grey plane is replicated into every output channel
+            for (int c = sc; c < c_end; ++c) {
+                float* d = dst + (b * co + c) * hw + p;
+                if (np == 4 && ((uintptr_t)d & 15) == 0) *reinterpret_cast<float4*>(d) = v;
+                else {
+                    d[0] = v.x;
+                    if (np > 1) d[1] = v.y;
+                    if (np > 2) d[2] = v.z;
+                    if (np > 3) d[3] = v.w;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int mf_u8_to_planes(const void* src_u8_nhwc, float* dst_nchw, int32_t batch, int32_t channels_in, int32_t channels_out, int64_t hw,
+                               void* stream) {
+    MF_CHECK_ARG(src_u8_nhwc && dst_nchw && batch >= 1 && hw >= 1, "mf_u8_to_planes: bad arguments");
+    MF_CHECK_ARG(channels_in >= 1 && channels_in <= 4 && channels_out >= 1 && (channels_out == channels_in || channels_in == 1),
+                 "mf_u8_to_planes: %d -> %d channels (1 .. 4 in; as many out, or one grey plane replicated)", channels_in, channels_out);
+    MF_CHECK_ARG(((uintptr_t)dst_nchw & 3) == 0, "mf_u8_to_planes: dst must be 4-byte aligned");
+    auto* kern = channels_in == 1 ? u8_to_planes_kernel<1> : channels_in == 2 ? u8_to_planes_kernel<2> : channels_in == 3 ? u8_to_planes_kernel<3>
+                                                                                                                          : u8_to_planes_kernel<4>;
+    hipLaunchKernelGGL(kern, dim3(fgrid((int64_t)batch * ((hw + 3) / 4))), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8_nhwc,
+                       dst_nchw, batch, channels_out, hw);
+    MF_CHECK_LAUNCH("mf_u8_to_planes");
+    return MF_OK;
+}
 
 extern "C" int64_t mf_minmax_ws_floats(void) { return 2 * MM_BLOCKS; }
 

@@ -1,6 +1,7 @@
 // Step programs (include/mfhip.h, "step programs"): a recorded sequence of this library's own entry points, replayed without Python.
-// Host code only: the file parser, the buffer table, one thunk per replayable entry, and the three model-level entries of
-// SURVEY.md section 8(b) (mf_denoise_step_fused, mf_unet_forward, mf_brushnet_forward) on top of them.
+// Host code only: the file parser, the buffer table, one thunk per replayable entry, the three model-level entries of
+// SURVEY.md section 8(b) (mf_denoise_step_fused, mf_unet_forward, mf_brushnet_forward) on top of them, and the two ends of a call
+// around the loop (mf_encode_prompt, mf_build_conditioning, mf_decode_image).
 // The writer is reflecting_reality_amd/program.py (Recorder.save); both sides are pinned by tests/test_program_gpu.py.
 #include <string.h>
 
@@ -42,6 +43,22 @@ const struct { const char* name; const char* sig; } kFns[F_COUNT] = {
     {"mf_transpose", "ppiiillll"}, {"mf_transpose_bf16", "ppiiillll"}, {"mf_transpose_bf16_bf16", "ppiiillll"},
     {"mf_memcpy2d", "plplll"}, {"mf_memset", "pil"},
 };
+
+// The entries of the two ends of a call (prompt encoding, conditioning, decode + postprocess): program._REPLAYABLE_CALL holds the same
+// table.  Kept apart from kFns, whose contents tests/test_program_cpu.py pins as the entries of a denoise step; ids go on from F_COUNT.
+// mf_axpby_n takes two HOST arrays: the recorder writes them out flat (six pointers, six coefficients; unused ones null / 0).
+enum CallFn {
+    G_EMBED_TOKENS = F_COUNT, G_ACT, G_ATTN_CAUSAL_BF16, G_ATTN_CAUSAL_F16, G_ATTN_CAUSAL_F16X3, G_SOFTMAX_ROWS_CAUSAL, G_MINMAX, G_IMAGE_NORMALIZE,
+    G_MASK_KEEP, G_POSTPROCESS, G_U8_TO_PLANES, G_AXPBY_N, G_END
+};
+const struct { int fn; const char* name; const char* sig; } kCallFns[G_END - F_COUNT] = {
+    {G_EMBED_TOKENS, "mf_embed_tokens", "pppipiiiii"}, {G_ACT, "mf_act", "ppiil"},
+    {G_ATTN_CAUSAL_BF16, "mf_attention_causal_bf16", "plplplpliiiiif"}, {G_ATTN_CAUSAL_F16, "mf_attention_causal_f16", "plplplpliiiiif"},
+    {G_ATTN_CAUSAL_F16X3, "mf_attention_causal_f16x3", "pplpplpplpliiiiif"}, {G_SOFTMAX_ROWS_CAUSAL, "mf_softmax_rows_causal", "ppiliii"},
+    {G_MINMAX, "mf_minmax", "pplpp"}, {G_IMAGE_NORMALIZE, "mf_image_normalize", "pplp"}, {G_MASK_KEEP, "mf_mask_keep", "ppiil"},
+    {G_POSTPROCESS, "mf_postprocess", "pppiili"}, {G_U8_TO_PLANES, "mf_u8_to_planes", "ppiiil"}, {G_AXPBY_N, "mf_axpby_n", "ppppppffffffipl"},
+};
+inline const char* sig_of(int fn) { return fn < F_COUNT ? kFns[fn].sig : kCallFns[fn - F_COUNT].sig; }
 
 struct Reader {
     const uint8_t* p; const uint8_t* end; bool ok = true;
@@ -135,6 +152,8 @@ extern "C" int mf_program_load(const void* blob, int64_t bytes, mf_program** out
         call.fn = -1;
         for (int f = 0; f < F_COUNT; ++f)
             if (call.name == kFns[f].name) call.fn = f;
+        for (const auto& g : kCallFns)
+            if (call.name == g.name) call.fn = g.fn;
         if (call.stream >= nstreams) {
             mf_set_error("mf_program_load: call %u (%s) on stream %u of %u", c, call.name.c_str(), call.stream, nstreams);
             delete p;
@@ -155,7 +174,7 @@ extern "C" int mf_program_load(const void* blob, int64_t bytes, mf_program** out
             p->calls.push_back(std::move(call));
             continue;
         }
-        if (call.fn < 0 || strlen(kFns[call.fn].sig) != nargs) {
+        if (call.fn < 0 || strlen(sig_of(call.fn)) != nargs) {
             mf_set_error("mf_program_load: call %u: entry %s with %u arguments has no replay thunk in this library", c, call.name.c_str(), nargs);
             delete p;
             return MF_EINVAL;
@@ -167,7 +186,7 @@ extern "C" int mf_program_load(const void* blob, int64_t bytes, mf_program** out
             arg.buf = r.get<int32_t>();
             if (arg.kind == A_F32) { arg.f = r.get<float>(); (void)r.get<int32_t>(); }
             else arg.i = r.get<int64_t>();
-            const char want = kFns[call.fn].sig[a];
+            const char want = sig_of(call.fn)[a];
             const bool match = (want == 'p' && arg.kind == A_PTR) || (want == 'i' && arg.kind == A_I32) || (want == 'l' && arg.kind == A_I64) ||
                                (want == 'f' && arg.kind == A_F32) || (want == 'd' && arg.kind == A_DESC);
             if (!match || (arg.kind == A_PTR && (arg.buf < -1 || arg.buf >= (int32_t)nbuf))) {
@@ -310,6 +329,23 @@ int run_call(const mf_program* prog, const Call& c, void* s) {
     case F_TRANSPOSE_BF16_BF16: return mf_transpose_bf16_bf16(P(0), P(1), I(2), I(3), I(4), L(5), L(6), L(7), L(8), s);
     case F_MEMCPY2D: return mf_memcpy2d(P(0), L(1), P(2), L(3), L(4), L(5), s);
     case F_MEMSET: return mf_memset(P(0), I(1), L(2), s);
+    case G_EMBED_TOKENS: return mf_embed_tokens((const int32_t*)P(0), P(1), P(2), I(3), P(4), I(5), I(6), I(7), I(8), I(9), s);
+    case G_ACT: return mf_act(P(0), P(1), I(2), I(3), L(4), s);
+    case G_ATTN_CAUSAL_BF16: return mf_attention_causal_bf16(P(0), L(1), P(2), L(3), P(4), L(5), P(6), L(7), I(8), I(9), I(10), I(11), I(12), F(13), s);
+    case G_ATTN_CAUSAL_F16: return mf_attention_causal_f16(P(0), L(1), P(2), L(3), P(4), L(5), P(6), L(7), I(8), I(9), I(10), I(11), I(12), F(13), s);
+    case G_ATTN_CAUSAL_F16X3:
+        return mf_attention_causal_f16x3(P(0), P(1), L(2), P(3), P(4), L(5), P(6), P(7), L(8), (float*)P(9), L(10), I(11), I(12), I(13), I(14), I(15), F(16), s);
+    case G_SOFTMAX_ROWS_CAUSAL: return mf_softmax_rows_causal(FP(0), P(1), I(2), L(3), I(4), I(5), I(6), s);
+    case G_MINMAX: return mf_minmax(FP(0), FP(1), L(2), (float*)P(3), (float*)P(4), s);
+    case G_IMAGE_NORMALIZE: return mf_image_normalize(FP(0), (float*)P(1), L(2), FP(3), s);
+    case G_MASK_KEEP: return mf_mask_keep(FP(0), (float*)P(1), I(2), I(3), L(4), s);
+    case G_POSTPROCESS: return mf_postprocess(FP(0), (float*)P(1), P(2), I(3), I(4), L(5), I(6), s);
+    case G_U8_TO_PLANES: return mf_u8_to_planes(P(0), (float*)P(1), I(2), I(3), I(4), L(5), s);
+    case G_AXPBY_N: {
+        const float* xs[6] = {FP(0), FP(1), FP(2), FP(3), FP(4), FP(5)};
+        const float cs[6] = {F(6), F(7), F(8), F(9), F(10), F(11)};
+        return mf_axpby_n(xs, cs, I(12), (float*)P(13), L(14), s);      // (the entry copies both arrays into the launch's arguments)
+    }
     default: break;
     }
 #undef P
@@ -327,6 +363,14 @@ int bind_io(mf_program* p, const char* entry, const char* name, const void* ptr)
     const int32_t i = mf_program_find_buffer(p, name);
     MF_CHECK_ARG(i >= 0 && p->buffers[i].kind == MF_PROGRAM_IO, "%s: the program has no io buffer \"%s\" (was it exported for this entry?)", entry, name);
     return mf_program_bind(p, i, const_cast<void*>(ptr));
+}
+
+// the three entries of a call's two ends name the program they take: its meta (JSON written by the exporter) carries "entry": "<name>"
+int check_entry(const mf_program* p, const char* entry) {
+    MF_CHECK_ARG(p, "%s: null program", entry);
+    const std::string want = std::string("\"entry\": \"") + entry + "\"";
+    MF_CHECK_ARG(p->meta.find(want) != std::string::npos, "%s: the program was not exported for this entry (its meta does not say %s)", entry, want.c_str());
+    return MF_OK;
 }
 
 }  // namespace
@@ -414,4 +458,32 @@ extern "C" int mf_vae_encode_moments(mf_program* vae_encoder, const void* image,
     if ((rc = bind_io(vae_encoder, "mf_vae_encode_moments", "image", image)) != MF_OK) return rc;
     if ((rc = bind_io(vae_encoder, "mf_vae_encode_moments", "moments", moments_out)) != MF_OK) return rc;
     return mf_program_run(vae_encoder, stream);
+}
+
+extern "C" int mf_encode_prompt(mf_program* text_encoder, const int32_t* input_ids, void* prompt_embeds, void* stream) {
+    int rc;
+    if ((rc = check_entry(text_encoder, "mf_encode_prompt")) != MF_OK) return rc;
+    if ((rc = bind_io(text_encoder, "mf_encode_prompt", "input_ids", input_ids)) != MF_OK) return rc;
+    if ((rc = bind_io(text_encoder, "mf_encode_prompt", "prompt_embeds", prompt_embeds)) != MF_OK) return rc;
+    return mf_program_run(text_encoder, stream);
+}
+
+extern "C" int mf_build_conditioning(mf_program* conditioning, const void* image_u8, const void* mask_u8, const float* depth, const float* cond_noise,
+                                     void* cond, void* stream) {
+    int rc;
+    if ((rc = check_entry(conditioning, "mf_build_conditioning")) != MF_OK) return rc;
+    if ((rc = bind_io(conditioning, "mf_build_conditioning", "image_u8", image_u8)) != MF_OK) return rc;
+    if ((rc = bind_io(conditioning, "mf_build_conditioning", "mask_u8", mask_u8)) != MF_OK) return rc;
+    if ((rc = bind_io(conditioning, "mf_build_conditioning", "depth", depth)) != MF_OK) return rc;
+    if ((rc = bind_io(conditioning, "mf_build_conditioning", "cond_noise", cond_noise)) != MF_OK) return rc;
+    if ((rc = bind_io(conditioning, "mf_build_conditioning", "cond", cond)) != MF_OK) return rc;
+    return mf_program_run(conditioning, stream);
+}
+
+extern "C" int mf_decode_image(mf_program* decoder, const void* latents, void* image_u8, void* stream) {
+    int rc;
+    if ((rc = check_entry(decoder, "mf_decode_image")) != MF_OK) return rc;
+    if ((rc = bind_io(decoder, "mf_decode_image", "latents", latents)) != MF_OK) return rc;
+    if ((rc = bind_io(decoder, "mf_decode_image", "image_u8", image_u8)) != MF_OK) return rc;
+    return mf_program_run(decoder, stream);
 }

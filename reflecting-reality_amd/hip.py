@@ -175,6 +175,7 @@ SIGNATURES = {
     "mf_concat_channels": "i:pppipilp", "mf_postprocess": "i:pppiilip",
     "mf_depth_normalize": "i:ppplffipp", "mf_select_ws_bytes": "l:", "mf_select_ranks": "i:plpippp", "mf_depth_percentile_normalize": "i:pplpffippp",
     "mf_bicubic_resize_crop": "i:ppiiiiiiiiiffp", "mf_bicubic_aa_resize_crop": "i:ppiiiiiiiiiffp", "mf_hwc_to_chw_affine": "i:ppliffp",
+    "mf_u8_to_planes": "i:ppiiilp",
     # training (csrc/train.hip)
     "mf_sizeof_wgrad_desc": "i:", "mf_conv_wgrad_ws_floats": "l:W", "mf_conv_wgrad": "i:Wp", "mf_split_pack": "i:plpliip",
     "mf_transpose": "i:ppiiillllp", "mf_transpose_bf16": "i:ppiiillllp", "mf_colsum_ws_floats": "l:ili", "mf_colsum": "i:plpliliipp",
@@ -187,6 +188,8 @@ SIGNATURES = {
     "mf_program_buffer_info": "i:pipppp", "mf_program_find_buffer": "i:pp", "mf_program_bind": "i:pip", "mf_program_num_calls": "i:p",
     "mf_program_meta": "s:p", "mf_program_run": "i:pp", "mf_denoise_step_fused": "i:pppppp", "mf_unet_forward": "i:ppppipp",
     "mf_brushnet_forward": "i:pppppip", "mf_vae_decode": "i:pppp", "mf_vae_encode_moments": "i:pppp",
+    # the two ends of a call as step programs (program.export_encode_prompt / pipeline.export_conditioning / export_vae_decode(postprocess=True))
+    "mf_encode_prompt": "i:pppp", "mf_build_conditioning": "i:ppppppp", "mf_decode_image": "i:pppp",
 }
 EXPORTS = list(SIGNATURES)
 # (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
@@ -1516,6 +1519,10 @@ def concat_channels(srcs, batch: int) -> torch.Tensor:
     """torch.cat(srcs, 1) for NCHW fp32 tensors whose batch divides `batch` (smaller ones are repeated)."""
     _f32(*srcs)
     srcs = [s.contiguous() for s in srcs]
+    if _RECORDER is not None and all(s.shape[0] == batch for s in srcs):
+        # a step program cannot hold this entry's host arrays: while one is recorded the concatenation is the copies it amounts to
+        # (torch.cat: program.Recorder writes them down as mf_memcpy2d), bit for bit the same tensor
+        return torch.cat(srcs, 1)
     h, w = srcs[0].shape[-2:]
     n = len(srcs)
     out = torch.empty(batch, sum(s.shape[1] for s in srcs), h, w, dtype=torch.float32, device=srcs[0].device)
@@ -1523,6 +1530,21 @@ def concat_channels(srcs, batch: int) -> torch.Tensor:
     ch = (C.c_int32 * n)(*[s.shape[1] for s in srcs])
     bs = (C.c_int32 * n)(*[s.shape[0] for s in srcs])
     _launch("mf_concat_channels", arr, ch, bs, n, out, batch, h * w)
+    return out
+
+
+def u8_to_planes(src: torch.Tensor, channels_out: Optional[int] = None) -> torch.Tensor:
+    """uint8 NHWC pixels [B, H, W, C] (what a host holds after decoding an image file) -> fp32 NCHW planes in [0, 1], bit for bit
+    numpy's `arr.astype(np.float32) / 255.0` transposed (mf_u8_to_planes).  `channels_out` > 1 with C == 1 replicates the grey plane
+    (a mask the reference converts with .convert("RGB"))."""
+    _req_cuda(src)
+    if src.dtype != torch.uint8 or src.dim() != 4:
+        raise MfhipError("u8_to_planes: a uint8 [batch, height, width, channels] tensor")
+    src = src.contiguous()
+    b, h, w, ci = src.shape
+    co = ci if channels_out is None else int(channels_out)
+    out = torch.empty(b, co, h, w, dtype=torch.float32, device=src.device)
+    _launch("mf_u8_to_planes", src, out, b, ci, co, h * w)
     return out
 
 

@@ -407,7 +407,7 @@ class StableDiffusionBrushNetPipeline:
         """pipeline_brushnet.py:741-774 — WITHOUT the CFG duplication (done after the VAE, see module docstring)."""
         image = self.image_processor.preprocess(image, height=height, width=width).to(dtype=torch.float32)
         repeat_by = batch_size if image.shape[0] == 1 else num_images_per_prompt
-        return image.repeat_interleave(repeat_by, dim=0)
+        return image if repeat_by == 1 else image.repeat_interleave(repeat_by, dim=0)
 
     def prepare_latents(self, batch_size, num_channels_latents, height, width, generator, latents=None):
         shape = (batch_size, num_channels_latents, height // self.vae_scale_factor, width // self.vae_scale_factor)
@@ -454,7 +454,9 @@ class StableDiffusionBrushNetPipeline:
             if dup == 2 and self._cond_halves_identical:
                 # whether both CFG halves get the same sample is decided HERE, from how the noise was made (a host compare of a
                 # host tensor; a device tensor costs one read-back) — not by comparing the built conditioning on the device
-                self._cond_halves_identical = bool(torch.equal(noise[:batch], noise[batch:]))
+                # (export_conditioning decides before it records: the compare is a torch kernel a program cannot hold)
+                decided = getattr(self, "_cond_shared_decided", None)
+                self._cond_halves_identical = bool(torch.equal(noise[:batch], noise[batch:])) if decided is None else bool(decided)
             noise = noise.to(self.device, torch.float32)
             return [hip.vae_sample(moments, noise[i * batch:(i + 1) * batch].contiguous(), lat_c, sf) for i in range(dup)]
 
@@ -935,6 +937,127 @@ class StableDiffusionBrushNetPipeline:
                                  "use_graph left on)")
         self._export_info["result"] = out
         return self._export_info
+
+    # ---- the two ends of a call as step programs (program.py; include/mfhip.h "step programs") --------------------------------
+    def _u8_pixels(self, x, name: str) -> torch.Tensor:
+        from . import program
+        t = torch.as_tensor(np.asarray(x)) if not torch.is_tensor(x) else x
+        if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3:
+            raise program.ProgramError(f"`{name}` is uint8 pixels [B, H, W, 3] (what a host holds after decoding an image file), "
+                                       f"got {t.dtype} {tuple(t.shape)}")
+        return (t[None] if t.dim() == 3 else t).to(self.device).contiguous()
+
+    def export_conditioning(self, path: str, image=None, mask=None, depth=None, conditioning_noise=None, height: Optional[int] = None,
+                            width: Optional[int] = None, num_images_per_prompt: int = 1) -> dict:
+        """build_conditioning (pipeline_brushnet.py:1116-1215) under classifier-free guidance as a program for mf_build_conditioning,
+        preceded by the uint8 ingest (mf_u8_to_planes): io buffers "image_u8" / "mask_u8" (uint8 [B, H, W, 3]), "depth" (fp32
+        [B, 1, H, W] in [-1, 1], as `pipe(depth=)` takes it; only with depth_conditioning_mode='concat'), "cond_noise" (the VAE posterior
+        noise) and "cond" (the denoise step's conditioning buffer).  `conditioning_noise` of batch B, or of 2B with bit-identical halves,
+        exports the SHARED form (one draw for both guidance halves: "cond_noise" holds B images and the step runs BrushNet once);
+        otherwise "cond_noise" holds 2B.  The meta records which, and the `brushnet_once` a step exported from the same call carries.
+        Whatever the recorder cannot express (another depth / normals mode, several images per prompt: torch kernels between the
+        launches) raises ProgramError here, and no file is written."""
+        import json
+        from . import program
+        if self.device.type != "cuda":
+            raise hip.MfhipError("export_conditioning needs the device: a program is a recording of real launches")
+        if type(self) is not StableDiffusionBrushNetPipeline:
+            raise NotImplementedError("export_conditioning is built for the SD1.5 pipeline")
+        if conditioning_noise is None or isinstance(conditioning_noise, (list, tuple)):
+            raise program.ProgramError("export_conditioning takes ONE conditioning_noise tensor: random numbers stay the caller's")
+        image_u8, mask_u8 = self._u8_pixels(image, "image"), self._u8_pixels(mask, "mask")
+        if image_u8.shape != mask_u8.shape:
+            raise program.ProgramError(f"image {tuple(image_u8.shape)} and mask {tuple(mask_u8.shape)} differ in shape")
+        nb = image_u8.shape[0] * int(num_images_per_prompt)
+        height, width = height or int(image_u8.shape[1]), width or int(image_u8.shape[2])
+        noise = conditioning_noise.to(self.device, torch.float32).contiguous()
+        if noise.shape[0] not in (nb, 2 * nb):
+            raise ValueError(f"conditioning_noise must have batch {nb} (one draw shared by both guidance halves) or {2 * nb}")
+        shared = noise.shape[0] == nb or bool(torch.equal(noise[:nb], noise[nb:]))
+        noise = noise[:nb].contiguous() if shared else noise
+        named = dict(image_u8=image_u8, mask_u8=mask_u8, cond_noise=noise)
+        if self.depth_conditioning_mode is not None:
+            if depth is None:
+                raise ValueError(f"depth_conditioning_mode={self.depth_conditioning_mode!r} needs a `depth` input")
+            depth = torch.as_tensor(depth).to(self.device, torch.float32).contiguous()
+            named["depth"] = depth
+
+        def run():
+            img, msk = hip.u8_to_planes(image_u8), hip.u8_to_planes(mask_u8)
+            return self.build_conditioning(img, msk, depth, height, width, nb, num_images_per_prompt, True,
+                                           torch.cat([noise, noise]) if shared else noise, None)
+        self._cond_shared_decided = shared
+        try:
+            run()                                 # warm: tiles tuned, scratch sized
+            with program.Recorder(named) as rec:
+                cond = run()
+                rec.output("cond", cond)
+        finally:
+            self._cond_shared_decided = None
+        once = self._brushnet_shareable(cond, nb, True)
+        meta = dict(entry="mf_build_conditioning", reference="pipelines/brushnet/pipeline_brushnet.py:1116-1215", precision=self.vae.prec.name,
+                    depth_conditioning_mode=self.depth_conditioning_mode, cond_noise_batch=int(noise.shape[0]), batch=nb,
+                    shared_conditioning_sample=bool(shared), brushnet_once=bool(once), layouts=rec.layouts)
+        info = rec.save(path, meta=json.dumps(meta))
+        info["meta"] = meta
+        return info
+
+    def export_call(self, directory: str, **call_kwargs) -> dict:
+        """Run the pipeline once and write the whole call as five programs plus manifest.json / manifest.txt into `directory`:
+        encode_prompt.mfprog (mf_encode_prompt), bind_prompt.mfprog, conditioning.mfprog (mf_build_conditioning), step.mfprog
+        (mf_denoise_step_fused, scheduler="device": DDIM, PNDM and UniPC are one loop for the host) and decode.mfprog (mf_decode_image).
+        `call_kwargs`: what __call__ takes, with `prompt` (and optionally `negative_prompt`) as text for the pipeline's tokenizer,
+        `image` / `mask` as uint8 pixels [B, H, W, 3], `depth` as the normalised fp32 map and `conditioning_noise` given (tokenisation,
+        file decoding and random numbers stay the caller's).  examples/c_host/inpaint_host.c runs the directory without Python."""
+        import os
+        from . import program
+        from .text_encoder import CLIPTextModel
+        program.refuse_ip_processors(self.unet)
+        if type(self) is not StableDiffusionBrushNetPipeline:
+            raise NotImplementedError("export_call is built for the SD1.5 pipeline (SDXL's pooled text embedding feeds export-time tables)")
+        if self.normals_conditioning_mode is not None or call_kwargs.get("guess_mode"):
+            raise program.ProgramError("export_call: normals conditioning and guess_mode are outside the exported call")
+        kw = dict(call_kwargs)
+        if float(kw.get("guidance_scale", 7.5)) <= 1:
+            raise program.ProgramError("export_call: the exported call runs under classifier-free guidance (guidance_scale > 1)")
+        if not isinstance(self.text_encoder, CLIPTextModel) or self.tokenizer is None or kw.get("prompt") is None:
+            raise program.ProgramError("export_call needs the HIP text encoder (text_encoder.CLIPTextModel), a tokenizer and `prompt`")
+        prompt, nipp = kw.pop("prompt"), int(kw.get("num_images_per_prompt", 1) or 1)
+        plist = [prompt] if isinstance(prompt, str) else list(prompt)
+        neg = kw.pop("negative_prompt", None)
+        neg = [""] * len(plist) if neg is None else [neg] * len(plist) if isinstance(neg, str) else list(neg)
+        ids = self.tokenizer(neg + plist, padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True,
+                             return_tensors="pt").input_ids.to(self.device, torch.int32).contiguous()
+        image_u8, mask_u8 = self._u8_pixels(kw.pop("image", None), "image"), self._u8_pixels(kw.pop("mask", None), "mask")
+        noise, depth, clip_skip = kw.get("conditioning_noise"), kw.get("depth"), kw.get("clip_skip")
+        os.makedirs(directory, exist_ok=True)
+        files = dict(encode_prompt="encode_prompt.mfprog", bind_prompt="bind_prompt.mfprog", conditioning="conditioning.mfprog",
+                     step="step.mfprog", decode="decode.mfprog")
+        path = {k: os.path.join(directory, v) for k, v in files.items()}
+        self._graph_state = None
+        step = self.export_denoise_step(path["step"], scheduler="device", prompt=plist, negative_prompt=neg,
+                                        image=hip.u8_to_planes(image_u8), mask=hip.u8_to_planes(mask_u8), **kw)
+        latents = step["result"].images
+        infos = dict(step=step, bind_prompt=program.export_bind_prompt(self.unet, path["bind_prompt"]),
+                     encode_prompt=program.export_encode_prompt(self.text_encoder, path["encode_prompt"], ids, clip_skip=clip_skip),
+                     conditioning=self.export_conditioning(path["conditioning"], image=image_u8, mask=mask_u8, depth=depth,
+                                                           conditioning_noise=noise, height=kw.get("height"), width=kw.get("width"),
+                                                           num_images_per_prompt=nipp),
+                     decode=program.export_vae_decode(self.vae, path["decode"], latents, postprocess=True))
+        cm, sm = infos["conditioning"]["meta"], step["meta"]
+        if cm["brushnet_once"] != sm["brushnet_once"]:
+            raise program.ProgramError("export_call: the conditioning program and the step disagree on brushnet_once")
+        manifest = dict(abi_version=hip.ABI_VERSION, precision=self.unet.prec.name, scheduler=type(self.scheduler).__name__,
+                        steps=int(sm["steps"]), batch=int(cm["batch"]), brushnet_once=bool(sm["brushnet_once"]),
+                        cond_noise_batch=int(cm["cond_noise_batch"]), depth=self.depth_conditioning_mode is not None,
+                        init_noise_sigma=float(self.scheduler.init_noise_sigma), files=files,
+                        io={k: {n: dict(shape=l["shape"], dtype=l["dtype"]) for n, l in v["meta"]["layouts"].items()} for k, v in infos.items()
+                            if "layouts" in v["meta"]},
+                        shared_buffers=dict(prompt_embeds=["encode_prompt", "bind_prompt"], cond=["conditioning", "step"],
+                                            latents=["step", "decode"]))
+        manifest["io"]["step"] = dict(latents=dict(shape=list(sm["latents"]), dtype="float32"))
+        program.write_manifest(directory, manifest)
+        return dict(directory=directory, manifest=manifest, programs=infos, result=step["result"])
 
     def _sched_step(self, noise_pred, t, latents, eta, generator):
         import inspect

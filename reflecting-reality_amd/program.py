@@ -40,9 +40,21 @@ _REPLAYABLE = (
     "mf_timestep_embedding", "mf_silu_f32", "mf_cfg_ddim_step_dev", "mf_cfg_combine", "mf_sched_step_dev", "mf_vae_sample", "mf_nearest_resize",
     "mf_transpose", "mf_transpose_bf16", "mf_transpose_bf16_bf16", "mf_memcpy2d", "mf_memset")
 SIGNATURES = {name: hip.SIGNATURES[name][2:-1].replace("G", "d").replace("N", "d") for name in _REPLAYABLE}
+# The entries of the two ends of a call — prompt encoding, the conditioning build, decode + postprocess (export_encode_prompt,
+# pipeline.export_conditioning, export_vae_decode(postprocess=True)) — with their thunks in csrc/program.hip's kCallFns.  A table of its
+# own: _REPLAYABLE / SIGNATURES above are the entries of a denoise step, and tests/test_program_cpu.py pins them as such.
+_REPLAYABLE_CALL = (
+    "mf_embed_tokens", "mf_act", "mf_attention_causal_bf16", "mf_attention_causal_f16", "mf_attention_causal_f16x3", "mf_softmax_rows_causal",
+    "mf_minmax", "mf_image_normalize", "mf_mask_keep", "mf_postprocess", "mf_u8_to_planes")
+SIGNATURES_CALL = {name: hip.SIGNATURES[name][2:-1] for name in _REPLAYABLE_CALL}
+# mf_axpby_n (the latents / scaling_factor ahead of the decoder) takes two HOST arrays, which a program cannot hold: the recorder reads
+# them when the call is made and writes them out flat — six pointers, six coefficients (unused: null / 0), then nin, y, n
+_AXPBY_MAX = 6
+SIGNATURES_CALL["mf_axpby_n"] = "p" * _AXPBY_MAX + "f" * _AXPBY_MAX + "ipl"
+_ALL_SIGNATURES = {**SIGNATURES, **SIGNATURES_CALL}
 # queries / developer switches: forwarded, never recorded
 _PASS_THROUGH = ("mf_last_error", "mf_abi_version", "mf_gemm_num_tiles", "mf_gemm_tile_shape", "mf_gemm_tile_table_version",
-                 "mf_groupnorm_ws_floats", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc", "mf_sizeof_sched_row")
+                 "mf_groupnorm_ws_floats", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc", "mf_sizeof_sched_row", "mf_minmax_ws_floats")
 # descriptor fields that are HOST out-pointers (the library reports a choice through them): null in a program
 _HOST_FIELDS = {"gn_part_rows", "gn_grouped", "deferred_splits"}
 
@@ -102,16 +114,26 @@ class _Proxy:
         fn = getattr(self._lib, name)
         if name in _PASS_THROUGH:
             return fn
-        if name not in SIGNATURES:
+        if name not in _ALL_SIGNATURES:
             def refuse(*a, **k):
                 raise ProgramError(f"{name} has no replay thunk (program.SIGNATURES / csrc/program.hip): it cannot be part of an exported program")
             return refuse
         rec = self._rec
 
         def call(*args):
-            rec._record(name, args)
+            rec._record(name, _flat_axpby(args) if name == "mf_axpby_n" else args)
             return fn(*args)
         return call
+
+
+def _flat_axpby(args: tuple) -> tuple:
+    """mf_axpby_n(xs, coefs, nin, y, n, stream) with its two host arrays (ctypes) read out: SIGNATURES_CALL's flat form."""
+    xs, coefs, nin, y, n, stream = args
+    nin = int(nin.value if hasattr(nin, "value") else nin)
+    if not 1 <= nin <= _AXPBY_MAX:
+        raise ProgramError(f"mf_axpby_n with {nin} inputs")
+    return (tuple(xs[i] for i in range(nin)) + (None,) * (_AXPBY_MAX - nin) + tuple(float(coefs[i]) for i in range(nin))
+            + (0.0,) * (_AXPBY_MAX - nin) + (nin, y, n, stream))
 
 
 class _TorchOps(TorchDispatchMode):
@@ -293,7 +315,7 @@ class Recorder:
         self._ctx = [ops_ctx, pool_ctx]
 
     def _record(self, name: str, args: tuple) -> None:
-        sig = SIGNATURES[name]
+        sig = _ALL_SIGNATURES[name]
         if len(args) != len(sig) + 1:
             raise ProgramError(f"{name}: {len(args)} arguments for signature {sig!r} + stream")
         st = args[-1]
@@ -358,6 +380,10 @@ class Recorder:
         d2, s2 = rows(hd, pd, rd), rows(hs, ps, rs)
         if d2 is None or s2 is None or d2[0] != s2[0]:
             raise ProgramError(f"a torch copy {tuple(src.shape)}/{tuple(src.stride())} -> {tuple(dst.shape)}/{tuple(dst.stride())} is not a 2-D copy")
+        if d2[0] > 1 and (d2[1] < run or s2[1] < run):
+            # (rows that overlap: an expanded source, e.g. repeat_interleave's expand + clone; mf_memcpy2d takes no pitch below the row)
+            raise ProgramError(f"a broadcasting torch copy {tuple(src.shape)}/{tuple(src.stride())} -> {tuple(dst.shape)}/{tuple(dst.stride())} "
+                               "inside the recorded pass is not a 2-D copy")
         self._mem("mf_memcpy2d", dst.data_ptr(), d2[1] * es, src.data_ptr(), s2[1] * es, run * es, d2[0])
 
     def _cat(self, out: torch.Tensor, parts: List[torch.Tensor], dim: int) -> None:
@@ -533,10 +559,11 @@ def _hiprt():
 class Program:
     """A loaded program with torch-owned memory behind every buffer (tests, and Python hosts that want the replay without the models)."""
 
-    def __init__(self, path: str, device="cuda:0", share: Optional["Program"] = None):
+    def __init__(self, path: str, device="cuda:0", share: Optional["Program"] = None, only=None):
         """`share`: another loaded program; buffers of the same name (constants exported by the same process carry the address they
         had there: the weights, the prompt's K / V^T) are bound to ITS memory instead of a second copy — how a prompt-binding program
-        (export_bind_prompt) writes the constants a denoise-step program reads."""
+        (export_bind_prompt) writes the constants a denoise-step program reads.  `only`: share just the buffers of these names (the io
+        buffers two programs of a call hand each other: "cond", "latents", "prompt_embeds"); everything else gets memory of its own."""
         self.device = torch.device(device)
         with open(path, "rb") as f:
             head = f.read(8 + 16 + 16)
@@ -555,7 +582,7 @@ class Program:
                     kind, nbytes, off, name = C.c_int32(), C.c_int64(), C.c_int64(), C.c_char_p()
                     hip._check(lib.mf_program_buffer_info(self._h, i, C.byref(kind), C.byref(nbytes), C.byref(off), C.byref(name)), "mf_program_buffer_info")
                     nm = name.value.decode()
-                    if share is not None and kind.value != KIND_WORKSPACE and nm in share.names:
+                    if share is not None and kind.value != KIND_WORKSPACE and nm in share.names and (only is None or nm in only):
                         t = share.tensors[share.names[nm]]
                         if t.numel() < nbytes.value:
                             raise ProgramError(f"shared buffer {nm!r}: {t.numel()} bytes there, {nbytes.value} here")
@@ -572,6 +599,18 @@ class Program:
 
     def buffer(self, name: str, dtype=torch.uint8) -> torch.Tensor:
         return self.tensors[self.names[name]].view(dtype)
+
+    def write(self, name: str, t: torch.Tensor) -> None:
+        """Copy a tensor into the io buffer `name`; one whose bytes differ from the buffer's is refused (a program is specialised on its
+        shapes: e.g. "cond_noise" of B images for a conditioning program exported for 2B)."""
+        if name not in self.names:
+            raise ProgramError(f"the program has no buffer {name!r} (its buffers: {sorted(n for n in self.names if '.' not in n)})")
+        buf = self.tensors[self.names[name]]
+        src = t.to(self.device).contiguous()
+        nbytes = src.numel() * src.element_size()
+        if nbytes != buf.numel():
+            raise ProgramError(f"buffer {name!r}: {nbytes} bytes given ({tuple(t.shape)} {t.dtype}), the program was exported for {buf.numel()}")
+        buf.copy_(src.view(-1).view(torch.uint8))
 
     @property
     def meta(self) -> str:
@@ -648,11 +687,28 @@ def export_unet(model, path: str, sample: torch.Tensor, temb: torch.Tensor, enco
     return info
 
 
-def export_vae_decode(vae, path: str, z: torch.Tensor) -> dict:
+def export_vae_decode(vae, path: str, z: torch.Tensor, postprocess: bool = False) -> dict:
     """AutoencoderKL.decode (autoencoder_kl.py:294-318) as a program for mf_vae_decode: io buffers "z" (NCHW fp32, latents already divided by
-    the scaling factor as pipeline_brushnet.py:1342 does) and "image" (NCHW fp32)."""
+    the scaling factor as pipeline_brushnet.py:1342 does) and "image" (NCHW fp32).
+    `postprocess=True`: the end of a pipeline call as a program for mf_decode_image — `z` then holds the denoise loop's LATENTS (io buffer
+    "latents"); the program divides them by the scaling factor (:1342), decodes, and appends VaeImageProcessor.postprocess
+    (mf_postprocess: denormalise, clamp, round to uint8 NHWC) into the io buffer "image_u8" [B][H][W][3]."""
     import json
     z = z.to(vae.device).float().contiguous()
+    if postprocess:
+        sf = float(vae.config["scaling_factor"])
+
+        def run():
+            img = vae.decode(hip.axpby_n([z], [1.0 / sf]), return_dict=False)[0]
+            return hip.postprocess(img, denormalize=True, uint8=True)
+        run()
+        with Recorder(dict(latents=z)) as rec:
+            rec.output("image_u8", run())
+        meta = dict(entry="mf_decode_image", reference="pipelines/brushnet/pipeline_brushnet.py:1342-1350", precision=vae.prec.name,
+                    scaling_factor=sf, layouts=rec.layouts)
+        info = rec.save(path, meta=json.dumps(meta))
+        info["meta"] = meta
+        return info
     vae.decode(z, return_dict=False)
     with Recorder(dict(z=z)) as rec:
         img = vae.decode(z, return_dict=False)[0]
@@ -713,3 +769,71 @@ def export_bind_prompt(unet, path: str) -> dict:
     info = rec.save(path, meta=json.dumps(meta))
     info["meta"] = meta
     return info
+
+
+def export_encode_prompt(text_encoder, path: str, input_ids: torch.Tensor, clip_skip: Optional[int] = None) -> dict:
+    """CLIPTextModel as encode_prompt runs it (pipeline_brushnet.py:271-450; clip_skip :352-370: the hidden state clip_skip layers before
+    the last, through the final LayerNorm) as a program for mf_encode_prompt: io buffers "input_ids" (device int32 [2B, 77]: the negative
+    prompts' rows, then the positive ones' — the order the pipeline concatenates) and "prompt_embeds" ([2B, 77, C] in the encoder's
+    storage dtype: named and typed like the input of export_bind_prompt's program, so a host binds one allocation to both; the pipeline's
+    detour storage dtype -> fp32 -> storage dtype is exact and left out).  The two halves are encoded one after the other, as the
+    pipeline encodes the prompts and then the negative prompts: the launches — and the GEMM tiles tuned for their row count — are the
+    pipeline's own, which is what makes the result bit-identical at every size.  What `_encode` does on the host stays the host's: the
+    vocabulary check (mf_embed_tokens clamps), the pooled row.  Export with a text encoder of the UNet's precision."""
+    import json
+    te = text_encoder
+    if not (isinstance(input_ids, torch.Tensor) and input_ids.is_cuda and input_ids.dtype == torch.int32 and input_ids.dim() == 2
+            and input_ids.is_contiguous() and input_ids.shape[0] >= 2 and input_ids.shape[0] % 2 == 0):
+        raise ProgramError("export_encode_prompt: input_ids is a contiguous device int32 tensor [2B, seq] (negative rows, then positive)")
+    if input_ids.shape[1] > te.config["max_position_embeddings"]:
+        raise ValueError(f"sequence length {input_ids.shape[1]} exceeds max_position_embeddings {te.config['max_position_embeddings']}")
+    layers = te.config["num_hidden_layers"]
+    if clip_skip is not None and not 0 <= int(clip_skip) <= layers:
+        raise ValueError(f"clip_skip = {clip_skip} with {layers} layers")
+
+    half = input_ids.shape[0] // 2
+
+    def one(ids):
+        if clip_skip is None:
+            return te._stack(ids)[0]
+        hidden = te._stack(ids, output_hidden_states=True)[1]
+        return hip.layernorm(hidden[-(int(clip_skip) + 1)], *te.P["final_layer_norm"], te.eps, te.prec.act)
+
+    def run():
+        return torch.cat([one(input_ids[half:]), one(input_ids[:half])][::-1])      # (positive first, like encode_prompt; stacked negative | positive)
+    run()                                     # warm: tiles tuned, scratch sized
+    with Recorder(dict(input_ids=input_ids)) as rec:
+        rec.output("prompt_embeds", run())
+    meta = dict(entry="mf_encode_prompt", reference="pipelines/brushnet/pipeline_brushnet.py:271-450", precision=te.prec.name,
+                clip_skip=clip_skip, vocab_size=int(te.config["vocab_size"]), layouts=rec.layouts)
+    info = rec.save(path, meta=json.dumps(meta))
+    info["meta"] = meta
+    return info
+
+
+def _flat_items(prefix: str, v):
+    if isinstance(v, dict):
+        for k, x in v.items():
+            yield from _flat_items(f"{prefix}.{k}" if prefix else str(k), x)
+    elif isinstance(v, (list, tuple)):
+        yield prefix, ",".join(str(int(x)) if isinstance(x, bool) else str(x) for x in v)
+    elif isinstance(v, bool):
+        yield prefix, str(int(v))
+    else:
+        yield prefix, str(v)
+
+
+def write_manifest(directory: str, manifest: dict) -> None:
+    """manifest.json, and the same settings as manifest.txt for a host without a JSON parser (examples/c_host/manifest_reader.h): one
+    `key value` line per leaf, nested keys joined by dots, lists by commas, booleans as 0 / 1.  Settings and names only."""
+    import json
+    import os
+    lines = []
+    for k, v in _flat_items("", manifest):
+        if not k or any(c.isspace() for c in k) or "\n" in v or len(k) > 95 or len(v) > 255:
+            raise ProgramError(f"manifest entry {k!r} = {v!r} does not fit a `key value` line")
+        lines.append(f"{k} {v}\n")
+    with open(os.path.join(directory, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=2)
+    with open(os.path.join(directory, "manifest.txt"), "w") as f:
+        f.writelines(lines)

@@ -1,6 +1,10 @@
 """Export the denoise step of BASELINE configs[1] (batch 4 x 512 x 512, 50-step DDIM, CFG 7.5) as a step program, run the whole
 loop from a C host with no Python in the process (examples/c_host/denoise_host.c), and compare its latents with the pipeline's.
-usage: python tools/export_step.py [--precision bf16] [--steps 50] [--out /tmp/step.mfprog]"""
+usage: python tools/export_step.py [--precision bf16] [--steps 50] [--out /tmp/step.mfprog]
+       python tools/export_step.py --call [--precision bf16] [--steps 50] [--out /tmp/call_dir] [--repeats 3]
+--call: export the WHOLE call (pipe.export_call: prompt encoding, prompt binding, conditioning, step, decode) and run it from
+examples/c_host/inpaint_host.c; its uint8 image is compared with the pipeline's, and the host's time from the first upload to the image
+on the host is printed next to the wall time of `pipe(...)` on the same inputs, the two alternating."""
 import argparse
 import os
 import subprocess
@@ -18,11 +22,100 @@ from reflecting_reality_amd import hip, synth  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--precision", default="bf16")
 ap.add_argument("--steps", type=int, default=50)
-ap.add_argument("--out", default="/tmp/step.mfprog")
+ap.add_argument("--out", default=None)
+ap.add_argument("--call", action="store_true")
+ap.add_argument("--repeats", type=int, default=3)
 a = ap.parse_args()
+a.out = a.out or ("/tmp/call_dir" if a.call else "/tmp/step.mfprog")
 dev = torch.device("cuda", 0)
 hip.load()
 pipe, _ = bench.build_pipeline(a.precision, dev)
+
+
+def whole_call():
+    import re
+    import shutil
+    from reflecting_reality_amd.configs import CLIP_L_TEXT
+    from reflecting_reality_amd.text_encoder import CLIPTextModel
+    te = CLIPTextModel(dict(CLIP_L_TEXT), precision=a.precision, device=dev)
+    te.load_state_dict(synth.state_dict_for(te.param_shapes(), 3))
+    pipe.text_encoder, pipe.tokenizer = te, synth.HashTokenizer(int(CLIP_L_TEXT["vocab_size"]), 77)
+    g = torch.Generator().manual_seed(1234)
+    image = torch.randint(0, 256, (4, 512, 512, 3), generator=g, dtype=torch.uint8)
+    mask = torch.zeros(4, 512, 512, 3, dtype=torch.uint8)
+    mask[:, 128:384, 128:384] = 255
+    image = image * (mask == 0)
+    depth = torch.rand(4, 1, 512, 512, generator=g) * 2.0 - 1.0
+    noise, latents = torch.randn(8, 4, 64, 64, generator=g), torch.randn(4, 4, 64, 64, generator=g)
+    prompts = [f"a mirror reflecting scene number {i} of a quiet room" for i in range(4)]
+    neg = ["blurry, low quality"] * 4
+    kw = dict(prompt=prompts, negative_prompt=neg, depth=depth, num_inference_steps=a.steps, guidance_scale=7.5, latents=latents,
+              brushnet_conditioning_scale=1.0, height=512, width=512, conditioning_noise=noise)
+    t0 = time.time()
+    info = pipe.export_call(a.out, image=image, mask=mask, **kw)
+    size = sum(os.path.getsize(os.path.join(a.out, f)) for f in os.listdir(a.out))
+    print(f"exported in {time.time() - t0:.1f} s: {size / 1e9:.3f} GB in {sorted(os.listdir(a.out))}; "
+          + ", ".join(f"{k}: {v['calls']} calls" for k, v in info["programs"].items()))
+    exe, libdir = "/tmp/inpaint_host", os.path.join(ROOT, "reflecting-reality_amd", "lib")
+    subprocess.run(["gcc", "-O2", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{os.path.join(ROOT, 'include')}",
+                    os.path.join(ROOT, "examples", "c_host", "inpaint_host.c"), f"-L{libdir}", "-lmfhip", "-L/opt/rocm/lib", "-lamdhip64", "-o", exe], check=True)
+    ids = pipe.tokenizer(neg + prompts, padding="max_length", max_length=77, truncation=True, return_tensors="pt").input_ids.to(torch.int32)
+    files = {}
+    for name, t in (("ids", ids), ("image", image), ("mask", mask), ("depth", depth), ("noise", noise), ("latents", latents)):
+        files[name] = f"/tmp/call_{name}.bin"
+        t.contiguous().numpy().tofile(files[name])
+    planes = lambda u8: hip.u8_to_planes(u8.to(dev))
+    env = dict(os.environ, LD_LIBRARY_PATH=f"{libdir}:/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
+    cmd = [exe, a.out] + [x for k in files for x in (f"--{k}", files[k])] + ["--out", "/tmp/call_image_out.bin"]
+    py_ms, c_ms, want = [], [], None
+    for r in range(a.repeats + 1):                  # (the first pair warms both sides and is not reported)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        img = pipe(image=planes(image), mask=planes(mask), output_type="np", **kw).images
+        t1 = time.perf_counter()
+        want = (img * 255).round().astype("uint8")
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env)
+        if out.returncode != 0:
+            print(out.stdout + out.stderr)
+            return
+        if r:
+            py_ms.append((t1 - t0) * 1e3)
+            c_ms.append(float(re.search(r"([0-9.]+) ms from the first upload", out.stdout).group(1)))
+    got = np.fromfile("/tmp/call_image_out.bin", dtype=np.uint8).reshape(want.shape)
+    print("C host image == pipeline image (bitwise):", bool(np.array_equal(got, want)), "differing bytes:", int((got != want).sum()))
+    print(f"pipe(...) wall time, ms: {[round(x, 1) for x in py_ms]}; C host, first upload -> image on the host, ms: {[round(x, 1) for x in c_ms]}")
+    # stage by stage from this process: each program against the pipeline's own intermediate on the same inputs
+    from reflecting_reality_amd import program
+    path = lambda k: os.path.join(a.out, info["manifest"]["files"][k])
+    pe, ne = pipe.encode_prompt(prompts, 1, True, negative_prompt=neg)
+    want_pe = torch.cat([ne, pe]).to(dev, te.prec.act).contiguous()
+    enc = program.Program(path("encode_prompt"), dev)
+    enc.write("input_ids", ids)
+    enc.run()
+    torch.cuda.synchronize()
+    print("  encode_prompt program == pipe.encode_prompt:", torch.equal(enc.buffer("prompt_embeds", te.prec.act).view(want_pe.shape), want_pe))
+    enc.close()
+    want_cond = pipe.build_conditioning(planes(image), planes(mask), depth, 512, 512, 4, 1, True, noise)
+    cond = program.Program(path("conditioning"), dev)
+    for k, t in (("image_u8", image), ("mask_u8", mask), ("depth", depth), ("cond_noise", noise)):
+        cond.write(k, t)
+    cond.run()
+    torch.cuda.synchronize()
+    print("  conditioning program == pipe.build_conditioning:", torch.equal(cond.buffer("cond", torch.float32).view(want_cond.shape), want_cond))
+    cond.close()
+    lat = pipe(image=planes(image), mask=planes(mask), output_type="latent", **kw).images.float().contiguous()
+    dec = program.Program(path("decode"), dev)
+    dec.write("latents", lat)
+    dec.run()
+    torch.cuda.synchronize()
+    print("  decode program on the pipeline's latents == pipeline image:", bool(np.array_equal(dec.buffer("image_u8").view(want.shape).cpu().numpy(), want)))
+    dec.close()
+    shutil.rmtree(a.out)
+
+
+if a.call:
+    whole_call()
+    sys.exit(0)
 inp = {k: v.to(dev) for k, v in synth.pipeline_inputs(4, 512, 512, seed=1234, cross_dim=768).items()}
 kw = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"], image=inp["image"], mask=inp["mask"],
           depth=inp["depth"], num_inference_steps=a.steps, guidance_scale=7.5, latents=inp["latents"], output_type="latent",

@@ -548,6 +548,29 @@ int mf_hwc_to_chw_affine(const float* x, float* y, int64_t hw, int32_t channels,
 int mf_u8_to_planes(const void* src_u8_nhwc, float* dst_nchw, int32_t batch, int32_t channels_in, int32_t channels_out, int64_t hw,
                     void* stream);
 
+/* ---- image scoring on the device (metrics/metrics.py:51-67,108-165: torchmetrics' peak_signal_noise_ratio and
+ * structural_similarity_index_measure with their defaults, on the images taken as floats 0 .. 255) --------------------------------
+ * One row per image, written on the device; every image of a batch is scored on its own.  PSNR and the SSIM mean are finished from
+ * the row in float64 by whoever reads it:
+ *   psnr = 10 log10(R^2 / (sq_err / (h w c)))   R = target_max - target_min (or the given data_range); sq_err == 0: inf
+ *   ssim = ssim_sum / count                     count = (h - 10)(w - 10) c positions of the 11 x 11 Gaussian window (sigma 1.5) */
+typedef struct mf_metrics_row {
+    int64_t sq_err;      /* sum over every element of (pred - target)^2 after the region step: exact */
+    int64_t count;
+    double ssim_sum;     /* sum of the per-position SSIM values (fp32 each, added in float64 in a fixed order) */
+    int32_t pred_min, pred_max, target_min, target_max;      /* after the region step */
+} mf_metrics_row;
+int mf_sizeof_metrics_row(void);
+/* bytes of device scratch mf_image_metrics needs (8-byte aligned); -1 for dimensions it refuses */
+int64_t mf_image_metrics_ws_bytes(int32_t batch, int32_t h, int32_t w, int32_t channels);
+/* pred / target: uint8 [batch][h][w][channels], channels 1 .. 4, h and w >= 11; mask: uint8 [batch][h][w], or NULL with region 0.
+ * region (dataset.py:62-68, applied to BOTH images before anything else): 0 none; 1 "mask": pixels with mask == 255 become 0 in every
+ * channel; 2 "mirror": pixels with mask == 0 become 0.  data_range > 0: used for PSNR (by the caller) and for SSIM's c1 / c2, and the
+ * statistics ride in the SSIM pass (2 launches); <= 0: SSIM takes max(range(pred), range(target)) of each image from the data (4
+ * launches).  No host synchronisation, no floating-point atomics: the same inputs give the same bytes on every run. */
+int mf_image_metrics(const void* pred_u8_nhwc, const void* target_u8_nhwc, const void* mask_u8, int32_t region, int32_t batch,
+                     int32_t h, int32_t w, int32_t channels, float data_range, mf_metrics_row* rows_out, void* ws, void* stream);
+
 /* ============================================================================================
  * Training: the backward pass and the optimizer of examples/brushnet/train_brushnet_mirror.py:1459-1466
  * (accelerator.backward -> ATen autograd in the reference; clip_grad_norm_ :1463; torch.optim.AdamW :1188-1200).

@@ -10,7 +10,8 @@ Sub-modules:
   autograd   the tape of hand-written vector-Jacobian products behind the training step
   training   MirrorFusionModel, training_loss, train_step (backward + clip + AdamW), checkpoint save / load hooks
   distributed  batch sharding for inference, bucketed gradient all-reduce (RCCL) for training
-  inference  run_sharded: the examples/brushnet/test_brushnet.py harness (sample list split over ranks, N seeds each)
+  inference  run_sharded: the examples/brushnet/test_brushnet.py harness (sample list split over ranks, N seeds each); validate
+  metrics    compute_metrics, MetricsCalculator, score_regions: PSNR / SSIM (frame, mask, mirror) scored on the device
   pipeline   StableDiffusionBrushNetPipeline, StableDiffusionXLBrushNetPipeline
   text_encoder  CLIPTextModel, CLIPTextModelWithProjection (the prompt encoders of both pipelines)
 """

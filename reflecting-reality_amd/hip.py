@@ -134,6 +134,12 @@ class SchedOp(C.Structure):
     _fields_ = [("dst", C.c_int32), ("nterms", C.c_int32), ("src", C.c_int32 * SCHED_MAX_TERMS), ("coef", C.c_float * SCHED_MAX_TERMS)]
 
 
+class MetricsRow(C.Structure):
+    """mf_metrics_row: what mf_image_metrics writes per image (device memory; metrics.py finishes PSNR / SSIM from it in float64)."""
+    _fields_ = [("sq_err", C.c_int64), ("count", C.c_int64), ("ssim_sum", C.c_double),
+                ("pred_min", C.c_int32), ("pred_max", C.c_int32), ("target_min", C.c_int32), ("target_max", C.c_int32)]
+
+
 class SchedRow(C.Structure):
     """mf_sched_row: one denoise step of a multistep scheduler for mf_sched_step_dev (built by schedulers.device_plan)."""
     _fields_ = [("nops", C.c_int32), ("nslots", C.c_int32), ("load", C.c_uint32), ("store", C.c_uint32),
@@ -176,6 +182,8 @@ SIGNATURES = {
     "mf_depth_normalize": "i:ppplffipp", "mf_select_ws_bytes": "l:", "mf_select_ranks": "i:plpippp", "mf_depth_percentile_normalize": "i:pplpffippp",
     "mf_bicubic_resize_crop": "i:ppiiiiiiiiiffp", "mf_bicubic_aa_resize_crop": "i:ppiiiiiiiiiffp", "mf_hwc_to_chw_affine": "i:ppliffp",
     "mf_u8_to_planes": "i:ppiiilp",
+    # image scoring (csrc/metrics.hip)
+    "mf_sizeof_metrics_row": "i:", "mf_image_metrics_ws_bytes": "l:iiii", "mf_image_metrics": "i:pppiiiiifppp",
     # training (csrc/train.hip)
     "mf_sizeof_wgrad_desc": "i:", "mf_conv_wgrad_ws_floats": "l:W", "mf_conv_wgrad": "i:Wp", "mf_split_pack": "i:plpliip",
     "mf_transpose": "i:ppiiillllp", "mf_transpose_bf16": "i:ppiiillllp", "mf_colsum_ws_floats": "l:ili", "mf_colsum": "i:plpliliipp",
@@ -194,7 +202,8 @@ SIGNATURES = {
 EXPORTS = list(SIGNATURES)
 # (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
 _LAYOUTS = ((GemmDesc, "mf_sizeof_gemm_desc"), (GroupNormDesc, "mf_sizeof_groupnorm_desc"), (AttnBwdDesc, "mf_sizeof_attn_bwd_desc"),
-            (WgradDesc, "mf_sizeof_wgrad_desc"), (GroupNormBwdDesc, "mf_sizeof_groupnorm_bwd_desc"), (SchedRow, "mf_sizeof_sched_row"))
+            (WgradDesc, "mf_sizeof_wgrad_desc"), (GroupNormBwdDesc, "mf_sizeof_groupnorm_bwd_desc"), (SchedRow, "mf_sizeof_sched_row"),
+            (MetricsRow, "mf_sizeof_metrics_row"))
 _CTYPES = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "s": C.c_char_p, "v": None,
            **{kind: C.POINTER(struct) for kind, struct in DESC_KINDS.items()}}
 
@@ -1556,6 +1565,40 @@ def postprocess(x: torch.Tensor, denormalize: bool = True, uint8: bool = False) 
     out = torch.empty((b, h, w, c) if uint8 else (b, c, h, w), dtype=torch.uint8 if uint8 else torch.float32, device=x.device)
     _launch("mf_postprocess", x, None if uint8 else out, out if uint8 else None, b, c, h * w, int(denormalize))
     return out
+
+
+REGIONS = {None: 0, "": 0, "none": 0, "mask": 1, "mirror": 2}        # mf_image_metrics' region codes (dataset.py:62-68)
+
+
+def image_metrics(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None, region=0,
+                  data_range: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mf_image_metrics on uint8 NHWC device tensors [B, H, W, C] (mask: uint8 [B, H, W]): one mf_metrics_row per image as a uint8
+    [B, sizeof(MetricsRow)] DEVICE tensor.  Nothing synchronises with the host; metrics_rows() reads the rows."""
+    _req_cuda(pred, target, mask)
+    region = REGIONS[region] if region in REGIONS else int(region)
+    if pred.dtype != torch.uint8 or target.dtype != torch.uint8 or pred.dim() != 4 or pred.shape != target.shape:
+        raise MfhipError("image_metrics: two uint8 [batch, height, width, channels] tensors of one shape")
+    b, h, w, c = pred.shape
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (b, h, w)):
+        raise MfhipError(f"image_metrics: the mask must be uint8 [{b}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
+    pred, target = pred.contiguous(), target.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    nbytes = load().mf_image_metrics_ws_bytes(b, h, w, c)
+    if nbytes < 0:
+        raise MfhipError(f"image_metrics: {load().mf_last_error().decode()}")
+    ws = scratch("image_metrics", (nbytes + 3) // 4, pred.device)
+    if out is None:
+        out = torch.empty(b, C.sizeof(MetricsRow), dtype=torch.uint8, device=pred.device)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != b * C.sizeof(MetricsRow) or out.device != pred.device:
+        raise MfhipError(f"image_metrics: out must be a contiguous uint8 [{b}, {C.sizeof(MetricsRow)}] tensor on {pred.device}")
+    _launch("mf_image_metrics", pred, target, mask, region, b, h, w, c, float(data_range), out, ws)
+    return out
+
+
+def metrics_rows(rows: torch.Tensor):
+    """The rows of image_metrics() on the host, as a numpy record array with MetricsRow's fields (this is the synchronisation)."""
+    import numpy as np
+    return np.frombuffer(rows.cpu().numpy().tobytes(), dtype=np.dtype(MetricsRow))
 
 
 def _sel_ws(device) -> torch.Tensor:

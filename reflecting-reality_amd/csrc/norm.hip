@@ -2,6 +2,7 @@
 // All three are HBM-bound: one read + one write of the tensor (GroupNorm above 16x16 reads it twice: stats,
 // then apply), fp32 statistics, vectorised 4-channel accesses, no atomics (bitwise reproducible).
 #include <stdlib.h>
+#include <type_traits>
 #include "mf_common.h"
 
 namespace {
@@ -69,14 +70,98 @@ __device__ __forceinline__ void store8(char* p, int dt, int64_t idx, const float
     }
 }
 
-template <int VW, bool F16>
-__device__ __forceinline__ void loadv(const char* p, int dt, float* o) {
-    if (VW == 8) {
-        load8<F16>(p, dt, 0, o);
+// A row piece of VW channels as it lies in memory, with the storage dtype a TEMPLATE argument (MF_F32 / MF_BF16 / MF_F16): a dtype
+// code tested at run time makes hipcc merge the fp32 and 16-bit paths of every access (a dword + dwordx3 pair behind a uniform
+// branch with a full vmcnt wait behind each), which left ONE row in flight per wave however far the loops were unrolled.  Rows stay
+// packed (4 VGPRs for eight 16-bit channels) until they are used, so that U of them in flight cost U x 4 registers.
+template <int DT, int VW>
+struct gn_raw { uint4 q[DT == MF_F32 ? VW / 4 : 1]; };
+
+// (every tensor of these kernels lies in global memory: the accesses say so, since a pointer rebuilt from its uniform halves,
+// gn_uniform below, is otherwise a flat one, and a flat load waits on both counters)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GN_GLOBAL(T, p) reinterpret_cast<__attribute__((address_space(1))) T*>(reinterpret_cast<uintptr_t>(p))
+#else
+#define GN_GLOBAL(T, p) reinterpret_cast<T*>(p)
+#endif
+template <int DT, int VW>
+__device__ __forceinline__ void gn_load(const char* p, gn_raw<DT, VW>& r) {
+    if constexpr (DT == MF_F32) {
+#pragma unroll
+        for (int j = 0; j < VW / 4; ++j) r.q[j] = *GN_GLOBAL(const uint4, p + 16 * j);
+    } else if constexpr (VW == 8) {
+        r.q[0] = *GN_GLOBAL(const uint4, p);
     } else {
-        const float4 t = load4<F16>(p, dt, 0);
-        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+        const uint2 u = *GN_GLOBAL(const uint2, p);
+        r.q[0].x = u.x; r.q[0].y = u.y;
     }
+}
+template <int DT, int VW>
+__device__ __forceinline__ void gn_unpack(const gn_raw<DT, VW>& r, float* o) {
+    if constexpr (DT == MF_F32) {
+#pragma unroll
+        for (int j = 0; j < VW / 4; ++j) {
+            o[4 * j] = __uint_as_float(r.q[j].x); o[4 * j + 1] = __uint_as_float(r.q[j].y);
+            o[4 * j + 2] = __uint_as_float(r.q[j].z); o[4 * j + 3] = __uint_as_float(r.q[j].w);
+        }
+    } else {
+        constexpr bool F16 = DT == MF_F16;
+        unpack_h2<F16>(r.q[0].x, o[0], o[1]);
+        unpack_h2<F16>(r.q[0].y, o[2], o[3]);
+        if constexpr (VW == 8) {
+            unpack_h2<F16>(r.q[0].z, o[4], o[5]);
+            unpack_h2<F16>(r.q[0].w, o[6], o[7]);
+        }
+    }
+}
+template <int DT, int VW>
+__device__ __forceinline__ void gn_store(char* p, const float* v) {
+    if constexpr (DT == MF_F32) {
+#pragma unroll
+        for (int j = 0; j < VW / 4; ++j) *GN_GLOBAL(float4, p + 16 * j) = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+    } else {
+        constexpr bool F16 = DT == MF_F16;
+        if constexpr (VW == 8) *GN_GLOBAL(uint4, p) = pack_h8<F16>(v);
+        else *GN_GLOBAL(uint2, p) = uint2{pack_h2<F16>(v[0], v[1]), pack_h2<F16>(v[2], v[3])};
+    }
+}
+// A wave-uniform pointer, opaque to the optimizer: base + 32-bit lane offset then stays a scalar base with a VGPR offset in the
+// access itself.  Left alone, hipcc folds the lane offset into every row's pointer and keeps one 64-bit VGPR pair per row in flight.
+template <typename T>
+__device__ __forceinline__ T* gn_uniform(T* p) {
+    const uint64_t a = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return reinterpret_cast<T*>((uint64_t)hi << 32 | lo);
+}
+// A per-lane pointer the optimizer does not see through: row u's address is formed from it where it is used, not kept as one more
+// 64-bit induction variable per row in flight
+template <typename T>
+__device__ __forceinline__ T* gn_lane_ptr(T* p) {
+    asm("" : "+v"(p));
+    return p;
+}
+// The packed form of 8 values that the storage dtype holds exactly (so that unpacking gives the same bits back)
+template <int DT>
+__device__ __forceinline__ void gn_repack(const float* v, gn_raw<DT, 8>& r) {
+    if constexpr (DT == MF_F32) {
+        r.q[0] = uint4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+        r.q[1] = uint4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])};
+    } else {
+        r.q[0] = pack_h8<DT == MF_F16>(v);
+    }
+}
+// The optimizer forgets what a packed row holds: values unpacked from it before are not kept alive in their fp32 form
+template <int DT, int VW>
+__device__ __forceinline__ void gn_forget(gn_raw<DT, VW>& r) {
+#pragma unroll
+    for (int j = 0; j < (int)(sizeof(r.q) / sizeof(uint4)); ++j) asm volatile("" : "+v"(r.q[j].x), "+v"(r.q[j].y), "+v"(r.q[j].z), "+v"(r.q[j].w));
+}
+// VW fp32 parameters (gamma / beta / the per-channel affine), 16-byte aligned
+template <int VW>
+__device__ __forceinline__ void gn_loadf(const float* p, float* o) {
+    gn_raw<MF_F32, VW> r;
+    gn_load<MF_F32, VW>(reinterpret_cast<const char*>(p), r);
+    gn_unpack<MF_F32, VW>(r, o);
 }
 
 // Thread geometry shared by both passes: a row of C channels is cvn = C/VW vector columns; tpr = min(cvn, 512)
@@ -86,7 +171,7 @@ __device__ __forceinline__ void loadv(const char* p, int dt, float* o) {
 //
 // Pass 1, grid (nchunks, batch): per-(thread-row, channel) fp32 sums -> LDS -> one (mean, M2) per group of the
 // chunk, in double.  No atomics: bitwise reproducible.
-template <int VW, int U = 4, bool F16 = false>
+template <int IN_DT, int VW, int U>
 __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float2* chan = reinterpret_cast<float2*>(smem_raw);   // [rif][C] (sum, sum of squares)
@@ -95,7 +180,7 @@ __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
     const int r0 = chunk * p.rows_per_chunk;
     int r1 = r0 + p.rows_per_chunk;
     if (r1 > p.HW) r1 = p.HW;
-    const int esz = p.in_dt == MF_F32 ? 4 : 2;
+    constexpr int esz = IN_DT == MF_F32 ? 4 : 2;
     if (trow < p.rif) {
         for (int col = lcol; col < p.cvn; col += p.tpr) {
             const int c = col * VW;
@@ -109,20 +194,26 @@ __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
             const char* ptr = base + (((int64_t)b * p.HW + r0 + trow) * ld + cc) * esz;
             int r = r0 + trow;
             for (; r + (U - 1) * p.rif < r1; r += U * p.rif, ptr += U * step) {
-                float v[U][VW];
+                gn_raw<IN_DT, VW> raw[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) loadv<VW, F16>(ptr + u * step, p.in_dt, v[u]);
+                for (int u = 0; u < U; ++u) gn_load<IN_DT, VW>(ptr + u * step, raw[u]);      // U whole rows in flight
 #pragma unroll
-                for (int u = 0; u < U; u += 4)
+                for (int u = 0; u < U; u += 4) {
+                    float v[4][VW];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) gn_unpack<IN_DT, VW>(raw[u + k], v[k]);
 #pragma unroll
                     for (int e = 0; e < VW; ++e) {
-                        s[e] += (v[u][e] + v[u + 1][e]) + (v[u + 2][e] + v[u + 3][e]);
-                        ss[e] += (v[u][e] * v[u][e] + v[u + 1][e] * v[u + 1][e]) + (v[u + 2][e] * v[u + 2][e] + v[u + 3][e] * v[u + 3][e]);
+                        s[e] += (v[0][e] + v[1][e]) + (v[2][e] + v[3][e]);
+                        ss[e] += (v[0][e] * v[0][e] + v[1][e] * v[1][e]) + (v[2][e] * v[2][e] + v[3][e] * v[3][e]);
                     }
+                }
             }
             for (; r < r1; r += p.rif, ptr += step) {
+                gn_raw<IN_DT, VW> raw0;
+                gn_load<IN_DT, VW>(ptr, raw0);
                 float v0[VW];
-                loadv<VW, F16>(ptr, p.in_dt, v0);
+                gn_unpack<IN_DT, VW>(raw0, v0);
 #pragma unroll
                 for (int e = 0; e < VW; ++e) { s[e] += v0[e]; ss[e] += v0[e] * v0[e]; }
             }
@@ -173,29 +264,51 @@ __device__ __forceinline__ void gn_group_mean_rstd(const GnArgs& p, int b, float
         const int g = g0 + (t >> 3), j = t & 7;
         const bool on = g < p.G;
         const float* st = p.ws + ((int64_t)b * p.G + (on ? g : 0)) * p.nchunks * 2;
-        float pm[GN_MAX_CHUNKS / 8], pq[GN_MAX_CHUNKS / 8], pn[GN_MAX_CHUNKS / 8];
-        double s1 = 0.0;
+        // Both passes read the chunk statistics with all eight loads in flight (the second pass hits the cache): a chunk past the
+        // end is read from a clamped address and counts as zeros.  A branch around each load put a full wait behind every one of
+        // them (eight dependent round trips in front of the apply loop).  `pass` is opaque to the optimizer, so that the second pass
+        // re-reads instead of keeping 24 values (and their double forms, hoisted out of the g0 loop) alive across the butterflies:
+        // that cost the fused apply kernel its occupancy.
+        auto chunks = [&](int pass, float* m, float* q, float* cnt) {
+            float2 v[GN_MAX_CHUNKS / 8];
 #pragma unroll
-        for (int u = 0; u < GN_MAX_CHUNKS / 8; ++u) {
-            const int k = j + 8 * u;
-            pm[u] = 0.0f; pq[u] = 0.0f; pn[u] = 0.0f;
-            if (on && k < p.nchunks) {
-                const float2 v = *reinterpret_cast<const float2*>(st + 2 * k);
+            for (int u = 0; u < GN_MAX_CHUNKS / 8; ++u) {
+                const int k = j + 8 * u + pass;
+                v[u] = *reinterpret_cast<const float2*>(st + 2 * (k < p.nchunks ? k : 0));
+            }
+#pragma unroll
+            for (int u = 0; u < GN_MAX_CHUNKS / 8; ++u) {
+                asm volatile("" : "+v"(v[u].x), "+v"(v[u].y));      // (keeps the optimizer from sinking the load into the select below)
+                const int k = j + 8 * u + pass;
+                const bool have = on && k < p.nchunks;
                 int rows = p.rows_per_chunk;
                 if ((k + 1) * p.rows_per_chunk > p.HW) rows = p.HW - k * p.rows_per_chunk;
-                pm[u] = v.x; pq[u] = v.y; pn[u] = (float)(rows * p.cpg);
+                m[u] = have ? v[u].x : 0.0f; q[u] = have ? v[u].y : 0.0f; cnt[u] = have ? (float)(rows * p.cpg) : 0.0f;
             }
-            s1 += (double)pn[u] * (double)pm[u];
+        };
+        int pass0 = 0, pass1 = 0;
+        asm volatile("" : "+v"(pass0));
+        double s1 = 0.0;
+        {
+            float pm[GN_MAX_CHUNKS / 8], pq[GN_MAX_CHUNKS / 8], pn[GN_MAX_CHUNKS / 8];
+            chunks(pass0, pm, pq, pn);
+#pragma unroll
+            for (int u = 0; u < GN_MAX_CHUNKS / 8; ++u) s1 += (double)pn[u] * (double)pm[u];
         }
 #pragma unroll
         for (int off = 1; off < 8; off <<= 1) s1 += __shfl_xor(s1, off, 8);
+        asm volatile("" : "+v"(pass1), "+v"(s1));      // the second pass starts behind the butterfly
         const double n = (double)p.HW * p.cpg;
         const double mean = s1 / n;
         double m2 = 0.0;
+        {
+            float pm[GN_MAX_CHUNKS / 8], pq[GN_MAX_CHUNKS / 8], pn[GN_MAX_CHUNKS / 8];
+            chunks(pass1, pm, pq, pn);
 #pragma unroll
-        for (int u = 0; u < GN_MAX_CHUNKS / 8; ++u) {
-            const double d = (double)pm[u] - mean;
-            m2 += (double)pq[u] + (double)pn[u] * d * d;
+            for (int u = 0; u < GN_MAX_CHUNKS / 8; ++u) {
+                const double d = (double)pm[u] - mean;
+                m2 += (double)pq[u] + (double)pn[u] * d * d;
+            }
         }
 #pragma unroll
         for (int off = 1; off < 8; off <<= 1) m2 += __shfl_xor(m2, off, 8);
@@ -219,7 +332,15 @@ __device__ __forceinline__ void gn_group_from_sums(const GnArgs& p, int b, float
             for (int k0 = j; k0 < p.nch0; k0 += 32) {                  // up to four independent loads in flight (nch0 <= 64), added in order
                 float2 v[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = k0 + 8 * u < p.nch0 ? src[(int64_t)(k0 + 8 * u) * p.G] : make_float2(0.0f, 0.0f);
+                for (int u = 0; u < 4; ++u) {                           // (a block past the end: clamped address, counted as zeros)
+                    const bool have = k0 + 8 * u < p.nch0;
+                    v[u] = src[(int64_t)(have ? k0 + 8 * u : k0) * p.G];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    asm volatile("" : "+v"(v[u].x), "+v"(v[u].y));      // (keeps the optimizer from sinking the load into the select)
+                    v[u] = k0 + 8 * u < p.nch0 ? v[u] : make_float2(0.0f, 0.0f);
+                }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) { s += (double)v[u].x; q += (double)v[u].y; }
             }
@@ -342,15 +463,37 @@ __global__ __launch_bounds__(GN_BLK) void gn_finalize_part_kernel(const GnArgs p
     }
 }
 
+// Waves per SIMD the apply kernel is compiled for.  With U = 4 packed 16-bit rows (4 VGPRs each) and the scale / shift of 8 channels
+// the row loop needs about 60 VGPRs, but the statistics combine in the prologue (double-precision divisions, a square root) spills
+// below 80: 6 waves per SIMD = three resident blocks of 8 waves per CU.  Two segments (per-lane row pointers) and U = 8 take the
+// 96 VGPRs of 5 waves; fp32 rows need more.  tests/test_groupnorm_resources_cpu.py holds the 16-bit kernels to 96 and no scratch.
+constexpr int gn_apply_waves(int in_dt, int out_dt, int u, bool seg2) {
+    if (in_dt == MF_F32 && u > 4) return 2;             // (the developer sweep's 16 fp32 loads in flight: 64 VGPRs of rows alone)
+    return in_dt == MF_F32 || out_dt == MF_F32 ? 4 : u <= 4 && !seg2 ? 6 : 5;
+}
+
 // Pass 2, grid (row blocks, batch): pure streaming y = silu(x*a[c] + b[c]) with the thread's a/b in registers.
-template <int VW, int U = 4, bool F16 = false>
-__global__ __launch_bounds__(GN_BLK) void gn_apply_kernel(const GnArgs p, int rows_per_block) {
+// Storage dtypes, vector width, rows in flight and SiLU are template arguments, and everything else a launch decides (the three
+// fuse_finalize modes, the segment a column lies in) is settled before the row loop, so that the loop is U whole-row loads issued
+// back to back, counted waits, branch-free arithmetic on one unpacked row at a time and whole-row stores.
+template <int IN_DT, int OUT_DT, int VW, int U, bool SILU, bool SEG2>
+__global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, U, SEG2)) void gn_apply_kernel(const GnArgs p, int rows_per_block) {
     const int b = blockIdx.y, t = threadIdx.x;
     const int lcol = t % p.tpr, trow = t / p.tpr;
     __shared__ float gm[64], gr[64];
+    float ga[VW], be[VW];
     if (p.fuse_finalize) {       // every block combines the chunk statistics itself: one launch (and its gap) less
+        // (the affine parameters of the thread's first column are requested first: their latency hides under the combine)
+        if constexpr (U <= 4) {
+            gn_loadf<VW>(p.gamma + lcol * VW, ga);
+            gn_loadf<VW>(p.beta + lcol * VW, be);
+        }
         if (p.fuse_finalize == 2) gn_group_from_sums(p, b, gm, gr);
         else gn_group_mean_rstd(p, b, gm, gr);
+        if constexpr (U > 4) {                           // (U = 8, the developer sweep, has no registers to spare across the combine)
+            gn_loadf<VW>(p.gamma + lcol * VW, ga);
+            gn_loadf<VW>(p.beta + lcol * VW, be);
+        }
         __syncthreads();
         if (p.stats_out && blockIdx.x == 0)
             for (int g = t; g < p.G; g += blockDim.x) {
@@ -362,53 +505,86 @@ __global__ __launch_bounds__(GN_BLK) void gn_apply_kernel(const GnArgs p, int ro
     const int r0 = blockIdx.x * rows_per_block;
     int r1 = r0 + rows_per_block;
     if (r1 > p.HW) r1 = p.HW;
-    const int esz = p.in_dt == MF_F32 ? 4 : 2, osz = p.out_dt == MF_F32 ? 4 : 2;
+    constexpr int esz = IN_DT == MF_F32 ? 4 : 2, osz = OUT_DT == MF_F32 ? 4 : 2;
+    constexpr bool fast_silu = OUT_DT != MF_F32;        // 16-bit output: __expf is far inside the rounding
     const float* ab = p.ws_ab + (int64_t)b * 2 * p.C;
-    const bool fast_silu = p.out_dt != MF_F32;          // 16-bit output: __expf is far inside the rounding
+    float sa[VW], sb[VW];
+    auto affine = [&](int c, const float* gam, const float* bet) {
+        int g = c / p.cpg, rem = c - g * p.cpg;          // one division per column: channel c + e lies in group (c + e) / cpg
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            sa[e] = gr[g] * gam[e];
+            sb[e] = bet[e] - gm[g] * sa[e];
+            if (++rem == p.cpg) { rem = 0; ++g; }
+        }
+    };
+    if (p.fuse_finalize) affine(lcol * VW, ga, be);
+    // the output of a block: a wave-uniform base plus a 32-bit lane offset that is the same for every row of the thread
+    char* const obase = p.out + ((int64_t)b * p.HW + r0) * p.C * osz;
+    const int64_t ostep = (int64_t)p.rif * p.C * osz;
     for (int col = lcol; col < p.cvn; col += p.tpr) {
         const int c = col * VW;
-        const char* base; int64_t ld; int cc;
-        if (c < p.C0) { base = p.x0; ld = p.C0; cc = c; }
-        else { base = p.x1; ld = p.C1; cc = c - p.C0; }
-        float sa[VW], sb[VW];
-        if (p.fuse_finalize) {
-            loadv<VW, F16>(reinterpret_cast<const char*>(p.gamma + c), MF_F32, sa);
-            loadv<VW, F16>(reinterpret_cast<const char*>(p.beta + c), MF_F32, sb);
-#pragma unroll
-            for (int e = 0; e < VW; ++e) {
-                const int g = (c + e) / p.cpg;
-                sa[e] = gr[g] * sa[e];
-                sb[e] = sb[e] - gm[g] * sa[e];
-            }
-        } else {
-            loadv<VW, F16>(reinterpret_cast<const char*>(ab + c), MF_F32, sa);
-            loadv<VW, F16>(reinterpret_cast<const char*>(ab + p.C + c), MF_F32, sb);
+        if (!p.fuse_finalize) {
+            gn_loadf<VW>(ab + c, sa);
+            gn_loadf<VW>(ab + p.C + c, sb);
+        } else if (col != lcol) {
+            float g2[VW], b2[VW];
+            gn_loadf<VW>(p.gamma + c, g2);
+            gn_loadf<VW>(p.beta + c, b2);
+            affine(c, g2, b2);
         }
-        const int64_t step = (int64_t)p.rif * ld * esz, ostep = (int64_t)p.rif * p.C * osz;
-        const char* ptr = base + (((int64_t)b * p.HW + r0 + trow) * ld + cc) * esz;
-        char* optr = p.out + (((int64_t)b * p.HW + r0 + trow) * p.C + c) * osz;
-        auto finish = [&](float* v, char* o) {
+        // One segment (SEG2 = false): like the output, a wave-uniform row pointer plus one 32-bit lane offset — the addresses of
+        // all rows in flight cost one VGPR.  Two segments: the segment, and with it the row pitch, differs from lane to lane, so
+        // the row pointer is per lane (ioff = 0) and the pitch a 32-bit lane value.
+        const char* ptr; unsigned ioff;
+        typename std::conditional<SEG2, unsigned, int64_t>::type step;
+        if constexpr (SEG2) {
+            const bool first = c < p.C0;
+            const int ld = first ? p.C0 : p.C1, cc = first ? c : c - p.C0;
+            ptr = (first ? p.x0 : p.x1) + (((int64_t)b * p.HW + r0 + trow) * ld + cc) * esz;
+            ioff = 0;
+            step = (unsigned)(p.rif * ld) * esz;
+        } else {
+            ptr = p.x0 + ((int64_t)b * p.HW + r0) * p.C0 * esz;
+            ioff = (unsigned)(trow * p.C0 + c) * esz;
+            step = (int64_t)p.rif * p.C0 * esz;
+        }
+        const unsigned ooff = (unsigned)(trow * p.C + c) * osz;
+        char* optr = obase;
+        auto finish = [&](const gn_raw<IN_DT, VW>& raw, char* o) {
+            float v[VW];
+            gn_unpack<IN_DT, VW>(raw, v);
 #pragma unroll
             for (int e = 0; e < VW; ++e) {
                 float y = v[e] * sa[e] + sb[e];
-                if (p.silu) y = fast_silu ? silu_f(y) : silu_precise(y);
+                if constexpr (SILU) y = fast_silu ? silu_f(y) : silu_precise(y);
                 v[e] = y;
             }
-            if (VW == 8) store8<F16>(o, p.out_dt, 0, v);
-            else store4<F16>(o, p.out_dt, 0, make_float4(v[0], v[1], v[2], v[3]));
+            gn_store<OUT_DT, VW>(gn_uniform(o) + ooff, v);
         };
         int r = r0 + trow;
         for (; r + (U - 1) * p.rif < r1; r += U * p.rif, ptr += U * step, optr += U * ostep) {
-            float v[U][VW];
+            gn_raw<IN_DT, VW> raw[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) loadv<VW, F16>(ptr + u * step, p.in_dt, v[u]);      // U independent 16-byte loads in flight
+            for (int u = 0; u < U; ++u) {                                                       // U whole rows in flight
+                if constexpr (SEG2) gn_load<IN_DT, VW>(gn_lane_ptr(ptr) + u * step, raw[u]);
+                else gn_load<IN_DT, VW>(gn_uniform(ptr + u * step) + ioff, raw[u]);
+            }
 #pragma unroll
-            for (int u = 0; u < U; ++u) finish(v[u], optr + u * ostep);
+            for (int u = 0; u < U; ++u) {
+                if constexpr (U > 4) __builtin_amdgcn_sched_barrier(0);      // (eight rows are held: one row's temporaries at a time)
+                finish(raw[u], optr + u * ostep);
+            }
         }
-        for (; r < r1; r += p.rif, ptr += step, optr += ostep) {
-            float v0[VW];
-            loadv<VW, F16>(ptr, p.in_dt, v0);
-            finish(v0, optr);
+        // at most U - 1 rows are left: TB at a time, their loads go out together too (a row past the end re-reads row r)
+        constexpr int TB = U > 4 ? 1 : 3;      // (U = 8, the developer sweep, holds eight rows already: its tail goes row by row)
+        for (; r < r1; r += TB * p.rif, ptr += TB * step, optr += TB * ostep) {
+            gn_raw<IN_DT, VW> raw[TB];
+#pragma unroll
+            for (int u = 0; u < TB; ++u) gn_load<IN_DT, VW>((r + u * p.rif < r1 ? ptr + u * step : ptr) + ioff, raw[u]);
+#pragma unroll
+            for (int u = 0; u < TB; ++u)
+                if (r + u * p.rif < r1) finish(raw[u], optr + u * ostep);
         }
     }
 }
@@ -420,8 +596,11 @@ __global__ __launch_bounds__(GN_BLK) void gn_apply_kernel(const GnArgs p, int ro
 // Thread t = lane * nv + vcol keeps vector column vcol of rows lane, lane + P, ... (at most ROWS): per-channel fp32
 // (sum, sum of squares) -> LDS -> one wave per group combines them in double in a fixed order (bitwise
 // reproducible) -> y = silu(x * a[c] + b[c]) from the registers.
-template <int ROWS, bool F16 = false>
-__global__ __launch_bounds__(1024) void gn_slab_kernel(const GnArgs p, int SC, int nv, int P) {
+// Storage dtypes, SiLU and the deferred split-K input (SK: GnArgs::sk_ws) are template arguments.  Everything the block needs from
+// memory is requested at the top, before the first wait: gamma / beta (and bias / temb of a deferred reduce), then all ROWS rows —
+// a row past HW is read from a clamped address and replaced by zeros, not branched around.
+template <int IN_DT, int OUT_DT, bool SILU, bool SK, int ROWS = 4>
+__global__ __launch_bounds__(1024, IN_DT != MF_F32 && OUT_DT != MF_F32 ? 5 : 4) void gn_slab_kernel(const GnArgs p, int SC, int nv, int P) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float2* chan = reinterpret_cast<float2*>(smem_raw);              // [P][SC or SC/8] (sum, sum of squares)
     __shared__ float gm[8], gr[8];
@@ -429,69 +608,83 @@ __global__ __launch_bounds__(1024) void gn_slab_kernel(const GnArgs p, int SC, i
     const int vcol = t % nv, lane = t / nv;
     const bool active = lane < P;                      // the block is padded to whole waves for the butterflies
     const int c = slab * SC + vcol * 8;
-    const int esz = p.in_dt == MF_F32 ? 4 : 2, osz = p.out_dt == MF_F32 ? 4 : 2;
-    const char* base; int64_t ld; int cc;
-    if (c < p.C0) { base = p.x0; ld = p.C0; cc = c; }
-    else { base = p.x1; ld = p.C1; cc = c - p.C0; }
-    const int64_t step = (int64_t)P * ld * esz;
-    const char* ptr = base + (((int64_t)b * p.HW + lane) * ld + cc) * esz;
+    constexpr int esz = IN_DT == MF_F32 ? 4 : 2, osz = OUT_DT == MF_F32 ? 4 : 2;
     const bool whole = p.cpg % 8 == 0;                 // a thread's 8 channels lie in one group: pre-reduce them
     const int W = whole ? SC / 8 : SC;                 // LDS items per lane
+    float sa[8], sb[8];
+    if constexpr (!SK) {
+        gn_loadf<8>(p.gamma + c, sa);
+        gn_loadf<8>(p.beta + c, sb);
+    }
+    // the rows of the thread stay PACKED from here to the stores behind the two barriers (4 VGPRs per 16-bit row, not 8): they
+    // are unpacked once for the statistics and once more for the output
+    gn_raw<IN_DT, 8> raw[ROWS];
     float v[ROWS][8];
-    if (active) {
+    if constexpr (!SK) {
+        const char* base; int64_t ld; int cc;
+        if (c < p.C0) { base = p.x0; ld = p.C0; cc = c; }
+        else { base = p.x1; ld = p.C1; cc = c - p.C0; }
 #pragma unroll
         for (int i = 0; i < ROWS; ++i) {
-            if (lane + i * P < p.HW && p.sk_ws == nullptr) load8<F16>(ptr + i * step, p.in_dt, 0, v[i]);
-            else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[i][e] = 0.0f;
-            }
+            const int row = lane + i * P < p.HW ? lane + i * P : p.HW - 1;
+            gn_load<IN_DT, 8>(base + (((int64_t)b * p.HW + row) * ld + cc) * esz, raw[i]);
         }
-        if (p.sk_ws) {
-            // the producer's split-K slabs: summed in slab order, + bias + temb, * alpha, rounded to the storage dtype — what
-            // splitk_reduce_kernel + epilogue_store8 (csrc/gemm_conv.hip) would have stored and this kernel read back
-            float bt[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) bt[e] = 0.0f;
-            float tb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (p.sk_bias) load8<false>(reinterpret_cast<const char*>(p.sk_bias + c), MF_F32, 0, bt);
-            if (p.sk_temb) load8<false>(reinterpret_cast<const char*>(p.sk_temb + (int64_t)b * p.sk_ld_temb + c), MF_F32, 0, tb);
+        for (int i = 0; i < ROWS; ++i) {
+            gn_unpack<IN_DT, 8>(raw[i], v[i]);
+            const bool in = lane + i * P < p.HW;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[i][e] = in ? v[i][e] : 0.0f;
+        }
+    } else {
+        // the producer's split-K slabs: summed in slab order, + bias + temb, * alpha, rounded to the storage dtype — what
+        // splitk_reduce_kernel + epilogue_store8 (csrc/gemm_conv.hip) would have stored and this kernel read back
+        const bool has_bias = p.sk_bias != nullptr, has_temb = p.sk_temb != nullptr;
+        float bt[8], tb[8];                            // (an absent term is read from gamma and never added)
+        gn_loadf<8>(has_bias ? p.sk_bias + c : p.gamma + c, bt);
+        gn_loadf<8>(has_temb ? p.sk_temb + (int64_t)b * p.sk_ld_temb + c : p.gamma + c, tb);
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[i][e] = 0.0f;
+        unsigned roff[ROWS];                            // a slab of one image is below 4 GB: uniform slab pointer + 32-bit lane offsets
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i) roff[i] = (unsigned)((lane + i * P < p.HW ? lane + i * P : p.HW - 1) * p.C + c) * 4u;
+        const char* src = reinterpret_cast<const char*>(p.sk_ws + (int64_t)b * p.HW * p.C);
+        for (int z = 0; z < p.sk_splits; ++z, src += p.sk_mn * 4) {  // a slab's ROWS rows in flight together; the additions keep the slab order
+            gn_raw<MF_F32, 8> part[ROWS];
+#pragma unroll
+            for (int i = 0; i < ROWS; ++i) gn_load<MF_F32, 8>(gn_uniform(src) + roff[i], part[i]);
 #pragma unroll
             for (int i = 0; i < ROWS; ++i) {
-                if (lane + i * P >= p.HW) continue;
-                const float* src = p.sk_ws + ((int64_t)b * p.HW + lane + i * P) * p.C + c;
-                int z = 0;
-                for (; z + 4 <= p.sk_splits; z += 4) {       // four slabs' loads in flight; the additions keep the slab order
-                    float4 lo[4], hi[4];
+                float x[8];
+                gn_unpack<MF_F32, 8>(part[i], x);
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        lo[u] = *reinterpret_cast<const float4*>(src + (z + u) * p.sk_mn);
-                        hi[u] = *reinterpret_cast<const float4*>(src + (z + u) * p.sk_mn + 4);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        v[i][0] += lo[u].x; v[i][1] += lo[u].y; v[i][2] += lo[u].z; v[i][3] += lo[u].w;
-                        v[i][4] += hi[u].x; v[i][5] += hi[u].y; v[i][6] += hi[u].z; v[i][7] += hi[u].w;
-                    }
-                }
-                for (; z < p.sk_splits; ++z) {
-                    const float4 lo = *reinterpret_cast<const float4*>(src + z * p.sk_mn);
-                    const float4 hi = *reinterpret_cast<const float4*>(src + z * p.sk_mn + 4);
-                    v[i][0] += lo.x; v[i][1] += lo.y; v[i][2] += lo.z; v[i][3] += lo.w;
-                    v[i][4] += hi.x; v[i][5] += hi.y; v[i][6] += hi.z; v[i][7] += hi.w;
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float x = v[i][e];
-                    if (p.sk_bias) x += bt[e];
-                    if (p.sk_temb) x += tb[e];
-                    x *= p.sk_alpha;
-                    if (p.in_dt == MF_BF16) x = bf16_to_f32(f32_to_bf16(x));
-                    else if (p.in_dt == MF_F16) x = (float)(_Float16)x;
-                    v[i][e] = x;
-                }
+                for (int e = 0; e < 8; ++e) v[i][e] += x[e];
             }
         }
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i) {
+            const bool in = lane + i * P < p.HW;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float x = v[i][e];
+                x = has_bias ? x + bt[e] : x;
+                x = has_temb ? x + tb[e] : x;
+                x *= p.sk_alpha;
+                v[i][e] = in ? x : 0.0f;
+            }
+            // rounded to the storage dtype (nearest-even, the conversion epilogue_store8 uses) by packing; the statistics take the
+            // rounded values
+            gn_repack<IN_DT>(v[i], raw[i]);
+            gn_forget(raw[i]);                         // (fp32 storage: what the reduce would have stored, not a product to contract into the sums below)
+            gn_unpack<IN_DT, 8>(raw[i], v[i]);
+        }
+        // (the slab sums, bias and temb took the registers until here: gamma / beta are requested now, two barriers ahead of their use)
+        gn_loadf<8>(p.gamma + c, sa);
+        gn_loadf<8>(p.beta + c, sb);
+    }
+    if (active) {
         float s[8], ss[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -511,6 +704,8 @@ __global__ __launch_bounds__(1024) void gn_slab_kernel(const GnArgs p, int SC, i
             for (int e = 0; e < 8; ++e) chan[lane * W + vcol * 8 + e] = make_float2(s[e], ss[e]);
         }
     }
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) gn_forget(raw[i]);
     __syncthreads();
     {   // one wave per group of the slab: fixed-order partial sums in double, then a butterfly
         const int l = t & 63, ipg = whole ? p.cpg / 8 : p.cpg, items = P * ipg, gps = SC / p.cpg;
@@ -543,28 +738,29 @@ __global__ __launch_bounds__(1024) void gn_slab_kernel(const GnArgs p, int SC, i
     }
     __syncthreads();
     if (!active) return;
-    float sa[8], sb[8];
-    load8<false>(reinterpret_cast<const char*>(p.gamma + c), MF_F32, 0, sa);
-    load8<false>(reinterpret_cast<const char*>(p.beta + c), MF_F32, 0, sb);
+    {
+        int g = vcol * 8 / p.cpg, rem = vcol * 8 - g * p.cpg;       // channel vcol * 8 + e of the slab lies in its group (vcol * 8 + e) / cpg
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int g = (vcol * 8 + e) / p.cpg;
-        sa[e] = gr[g] * sa[e];
-        sb[e] = sb[e] - gm[g] * sa[e];
+        for (int e = 0; e < 8; ++e) {
+            sa[e] = gr[g] * sa[e];
+            sb[e] = sb[e] - gm[g] * sa[e];
+            if (++rem == p.cpg) { rem = 0; ++g; }
+        }
     }
-    const bool fast_silu = p.out_dt != MF_F32;
+    constexpr bool fast_silu = OUT_DT != MF_F32;
     const int64_t ostep = (int64_t)P * p.C * osz;
     char* optr = p.out + (((int64_t)b * p.HW + lane) * p.C + c) * osz;
 #pragma unroll
     for (int i = 0; i < ROWS; ++i) {
         if (lane + i * P < p.HW) {
+            float y[8];
+            gn_unpack<IN_DT, 8>(raw[i], y);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                float y = v[i][e] * sa[e] + sb[e];
-                if (p.silu) y = fast_silu ? silu_f(y) : silu_precise(y);
-                v[i][e] = y;
+                y[e] = y[e] * sa[e] + sb[e];
+                if constexpr (SILU) y[e] = fast_silu ? silu_f(y[e]) : silu_precise(y[e]);
             }
-            store8<F16>(optr + i * ostep, p.out_dt, 0, v[i]);
+            gn_store<OUT_DT, 8>(optr + i * ostep, y);
         }
     }
 }
@@ -707,6 +903,38 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* s, char*
     }
 }
 
+// ---- dispatch of the dtype-templated GroupNorm kernels: every (in, out) storage pair mf_groupnorm accepts — all pairs of
+// {fp32, bf16, fp16} except fp16 mixed with bf16.  A pair outside the table is an error of the call, never another pair's kernel.
+template <int V> struct gn_int { static constexpr int value = V; };
+
+template <typename F>
+bool gn_for_dtypes(int in_dt, int out_dt, F&& f) {
+#define MF_GN_PAIR(I_, O_) if (in_dt == I_ && out_dt == O_) { f(gn_int<I_>{}, gn_int<O_>{}); return true; }
+    MF_GN_PAIR(MF_BF16, MF_BF16) MF_GN_PAIR(MF_F16, MF_F16) MF_GN_PAIR(MF_F32, MF_F32)
+    MF_GN_PAIR(MF_F32, MF_BF16) MF_GN_PAIR(MF_F32, MF_F16) MF_GN_PAIR(MF_BF16, MF_F32) MF_GN_PAIR(MF_F16, MF_F32)
+#undef MF_GN_PAIR
+    return false;
+}
+
+template <int I, int O>
+void gn_launch_slab(const GnArgs& a, dim3 grid, int nthr, size_t smem, hipStream_t s, int sc, int nv, int P) {
+    auto* kern = a.sk_ws ? (a.silu ? gn_slab_kernel<I, O, true, true> : gn_slab_kernel<I, O, false, true>)
+                         : (a.silu ? gn_slab_kernel<I, O, true, false> : gn_slab_kernel<I, O, false, false>);
+    hipLaunchKernelGGL(kern, grid, dim3(nthr), smem, s, a, sc, nv, P);
+}
+
+template <int I>
+void gn_launch_stats(const GnArgs& a, int vw, int u, dim3 grid, int nthr, size_t smem, hipStream_t s) {
+    auto* kern = vw == 8 ? (u == 8 ? gn_stats_kernel<I, 8, 8> : gn_stats_kernel<I, 8, 4>) : gn_stats_kernel<I, 4, 4>;
+    hipLaunchKernelGGL(kern, grid, dim3(nthr), smem, s, a);
+}
+
+template <int I, int O, bool SILU, bool SEG2>
+void gn_launch_apply(const GnArgs& a, int vw, int u, dim3 grid, int nthr, hipStream_t s, int rows_per_block) {
+    auto* kern = vw == 8 ? (u == 8 ? gn_apply_kernel<I, O, 8, 8, SILU, SEG2> : gn_apply_kernel<I, O, 8, 4, SILU, SEG2>) : gn_apply_kernel<I, O, 4, 4, SILU, SEG2>;
+    hipLaunchKernelGGL(kern, grid, dim3(nthr), 0, s, a, rows_per_block);
+}
+
 }  // namespace
 
 extern "C" int64_t mf_groupnorm_ws_floats(int32_t batch, int32_t groups, int32_t channels) {
@@ -721,7 +949,6 @@ extern "C" int mf_groupnorm(const mf_groupnorm_desc* d, void* stream) {
     MF_CHECK_ARG(d->c0 % 4 == 0 && d->c1 % 4 == 0, "mf_groupnorm: channel counts must be multiples of 4");
     MF_CHECK_ARG(d->batch >= 1 && d->hw >= 1, "mf_groupnorm: bad batch/hw");
     MF_CHECK_ARG(!(mf_any_f16(d->in_dtype, d->out_dtype) && mf_any_bf16(d->in_dtype, d->out_dtype)), "mf_groupnorm: fp16 and bf16 operands in one launch");
-    const bool f16 = mf_any_f16(d->in_dtype, d->out_dtype);
     GnArgs a{};
     a.x0 = (const char*)d->x0; a.x1 = (const char*)d->x1;
     a.C0 = d->c0; a.C1 = d->c1; a.C = C; a.in_dt = d->in_dtype; a.HW = d->hw; a.G = d->groups;
@@ -764,8 +991,10 @@ extern "C" int mf_groupnorm(const mf_groupnorm_desc* d, void* stream) {
                          ">= 2 slabs, 16-byte aligned slabs / bias / temb and no stats_out");
         }
         if ((!two_pass || d->sk_ws) && slab_ok) {
-            if (f16) hipLaunchKernelGGL((gn_slab_kernel<4, true>), dim3(C / sc, d->batch), dim3(nthr), smem, s, a, sc, nv, P);
-            else hipLaunchKernelGGL((gn_slab_kernel<4, false>), dim3(C / sc, d->batch), dim3(nthr), smem, s, a, sc, nv, P);
+            const bool known = gn_for_dtypes(d->in_dtype, d->out_dtype, [&](auto in_c, auto out_c) {
+                gn_launch_slab<decltype(in_c)::value, decltype(out_c)::value>(a, dim3(C / sc, d->batch), nthr, smem, s, sc, nv, P);
+            });
+            MF_CHECK_ARG(known, "mf_groupnorm: no kernel for in_dtype %d with out_dtype %d", d->in_dtype, d->out_dtype);
             MF_CHECK_LAUNCH("mf_groupnorm(slab)");
             return MF_OK;
         }
@@ -804,23 +1033,23 @@ extern "C" int mf_groupnorm(const mf_groupnorm_desc* d, void* stream) {
         if (gn_kparts < 1) gn_kparts = 1;
         while ((size_t)gn_kparts * gn_gps * a.cpg * sizeof(double2) > 48 * 1024 && gn_kparts > 1) --gn_kparts;
     }
-#define MF_GN_LAUNCH(VW_, U_, F_)                                                                                              \
-    do {                                                                                                                          \
-        if (from_groups) {                                                                                                        \
-        } else if (from_parts) {                                                                                                  \
-            hipLaunchKernelGGL(gn_finalize_part_kernel, dim3(d->batch, gn_slices), dim3(GN_BLK), (size_t)gn_kparts * gn_gps * a.cpg * sizeof(double2), s, a, gn_gps, gn_kparts); \
-            MF_CHECK_LAUNCH("mf_groupnorm(finalize from partial sums)");                                                          \
-        } else {                                                                                                                  \
-            hipLaunchKernelGGL((gn_stats_kernel<VW_, U_, F_>), dim3(a.nchunks, d->batch), dim3(nthr), smem1, s, a);               \
-            MF_CHECK_LAUNCH("mf_groupnorm(stats)");                                                                               \
-            if (!a.fuse_finalize) hipLaunchKernelGGL(gn_finalize_kernel, dim3(d->batch), dim3(GN_BLK), 0, s, a);                 \
-        }                                                                                                                         \
-        hipLaunchKernelGGL((gn_apply_kernel<VW_, U_, F_>), dim3(nblk, d->batch), dim3(nthr), 0, s, a, rows_per_block);            \
-    } while (0)
-    if (vw == 8 && gn_u == 8) { if (f16) MF_GN_LAUNCH(8, 8, true); else MF_GN_LAUNCH(8, 8, false); }
-    else if (vw == 8) { if (f16) MF_GN_LAUNCH(8, 4, true); else MF_GN_LAUNCH(8, 4, false); }
-    else { if (f16) MF_GN_LAUNCH(4, 4, true); else MF_GN_LAUNCH(4, 4, false); }
-#undef MF_GN_LAUNCH
+    const int u = vw == 8 && gn_u == 8 ? 8 : 4;
+    const bool known = gn_for_dtypes(d->in_dtype, d->out_dtype, [&](auto in_c, auto out_c) {
+        constexpr int I = decltype(in_c)::value, O = decltype(out_c)::value;
+        if (from_groups) {
+        } else if (from_parts) {
+            hipLaunchKernelGGL(gn_finalize_part_kernel, dim3(d->batch, gn_slices), dim3(GN_BLK), (size_t)gn_kparts * gn_gps * a.cpg * sizeof(double2), s, a, gn_gps, gn_kparts);
+        } else {
+            gn_launch_stats<I>(a, vw, u, dim3(a.nchunks, d->batch), nthr, smem1, s);
+            if (!a.fuse_finalize) hipLaunchKernelGGL(gn_finalize_kernel, dim3(d->batch), dim3(GN_BLK), 0, s, a);
+        }
+        const dim3 grid(nblk, d->batch);
+        if (a.silu && a.C1) gn_launch_apply<I, O, true, true>(a, vw, u, grid, nthr, s, rows_per_block);
+        else if (a.silu) gn_launch_apply<I, O, true, false>(a, vw, u, grid, nthr, s, rows_per_block);
+        else if (a.C1) gn_launch_apply<I, O, false, true>(a, vw, u, grid, nthr, s, rows_per_block);
+        else gn_launch_apply<I, O, false, false>(a, vw, u, grid, nthr, s, rows_per_block);
+    });
+    MF_CHECK_ARG(known, "mf_groupnorm: no kernel for in_dtype %d with out_dtype %d", d->in_dtype, d->out_dtype);
     MF_CHECK_LAUNCH("mf_groupnorm(apply)");
     return MF_OK;
 }

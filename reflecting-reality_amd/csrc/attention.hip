@@ -19,6 +19,7 @@
 // The softmax rescale factor is per query = per lane, so rescaling O^T is a plain register multiply.
 // O^T is transposed once through LDS at the end so the global stores are row-contiguous.
 #include <stdlib.h>
+#include <string>
 #include <type_traits>
 #include "mf_common.h"
 
@@ -923,12 +924,6 @@ __global__ __launch_bounds__(256) void rowdot_heads_kernel(const float* a, const
     }
 }
 
-template <int HD, bool SP = false, bool F16 = false, bool CAUSAL = false, bool IP = false>
-void launch_attn(const AttnArgs& a, int batch, hipStream_t s) {
-    dim3 grid((unsigned)(((a.sq + 127) / 128) * a.heads * batch));
-    hipLaunchKernelGGL((attn_fwd_kernel<HD, true, SP, F16, CAUSAL, IP>), grid, dim3(256), 0, s, a);
-}
-
 // fp32 [rows][ld] (first `cols` columns) -> two fp16 planes of the same layout: hi toward zero, lo = x - hi
 __global__ __launch_bounds__(256) void split_halves_kernel(const float* x, unsigned short* hi, unsigned short* lo, int64_t n4) {
     float amax = 0.0f;
@@ -952,92 +947,162 @@ unsigned* mf_ovf_flag_attention() {
     return p;
 }
 
+// ---- host side: every entry below validates and dispatches through one function per family -----------------------------------------
+constexpr float LOG2E = 1.44269504088896340736f;     // the kernels compute exp2: the softmax scale reaches them as scale * log2(e)
+
+// The head dims a kernel is instantiated for, written once per family: launch_for_head_dim walks the list, so the list is both what
+// gets compiled and what the refusal's "have ..." names.
+template <int... HD>
+struct HeadDims {};
+
+// Calls launch(std::integral_constant<int, HD>) for the member of the list that equals head_dim and reports the launch as `entry`.
+template <int... HD, class Launch>
+static int launch_for_head_dim(const char* entry, HeadDims<HD...>, int head_dim, Launch launch) {
+    const bool found = ((head_dim == HD && (launch(std::integral_constant<int, HD>{}), true)) || ...);
+    if (!found) {
+        std::string have;
+        ((have += (have.empty() ? "" : ", ") + std::to_string(HD)), ...);
+        mf_set_error("%s: unsupported head_dim %d (have %s)", entry, head_dim, have.c_str());
+        return MF_EINVAL;
+    }
+    MF_CHECK_LAUNCH(entry);
+    return MF_OK;
+}
+
+enum Flavour { BF16, FP16, SPLIT };      // storage of q / k / vt: one bf16 or fp16 plane (out of the same type), or two fp16 planes (fp32 out)
+enum Variant { PLAIN, CAUSAL, IP };
+
+template <Flavour FL, Variant V>
+using FwdHeadDims = std::conditional_t<V == CAUSAL, HeadDims<8, 64>,                 // both CLIP text encoders and the tiny test configs
+                    std::conditional_t<FL == SPLIT, HeadDims<8, 40, 64, 80>,         // 160: two double-buffered K / V^T planes do not fit in LDS
+                                                    HeadDims<8, 40, 64, 80, 160>>>;
+
+// MFHIP_ATTN_NOXCD: the developer A/B switch behind AttnArgs::no_xcd_order, read once for every flavour
+static bool no_xcd_order() {
+    static const bool off = getenv("MFHIP_ATTN_NOXCD") != nullptr;
+    return off;
+}
+
+struct Operand { const void* hi; const void* lo; int64_t ld; };      // lo: the low-half plane of the split flavour, nullptr otherwise
+
+// The one forward path.  k_ip / vt_ip / skv_ip / ip_scale: the ip variant's second segment, {} and 0 otherwise; lse may be nullptr.
+template <Flavour FL, Variant V>
+static int attention_fwd(const char* entry, Operand q, Operand k, Operand vt, Operand k_ip, Operand vt_ip, void* out, int64_t ldo, float* lse,
+                         int32_t batch, int32_t heads, int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale, float ip_scale,
+                         void* stream) {
+    constexpr bool SP = FL == SPLIT;
+    const Operand* const operands[] = {&q, &k, &vt, &k_ip, &vt_ip};
+    bool null = !out, aligned = mf_aligned16(out), ld8 = true;
+    for (int i = 0; i < (V == IP ? 5 : 3); ++i) {
+        const Operand& o = *operands[i];
+        null |= !o.hi || (SP && !o.lo);
+        aligned &= mf_aligned16(o.hi) && mf_aligned16(o.lo);
+        ld8 &= o.ld % 8 == 0;
+    }
+    MF_CHECK_ARG(!null, "%s: null pointer", entry);
+    MF_CHECK_ARG(batch >= 1 && heads >= 1 && sq >= 1 && skv >= 1, "%s: bad sizes", entry);
+    MF_CHECK_ARG(V != CAUSAL || sq == skv, "%s: the causal mask needs sq == skv (got %d, %d)", entry, sq, skv);
+    MF_CHECK_ARG(V != IP || (skv_ip >= 1 && skv_ip <= 64), "%s: skv_ip = %d, the ip segment is one key tile (1 .. 64)", entry, skv_ip);
+    MF_CHECK_ARG(ld8 && ldo % (SP ? 4 : 8) == 0 && vt.ld >= skv && (V != IP || vt_ip.ld >= skv_ip),
+                 "%s: leading dims must be multiples of 8 (fp32 ldo: 4), ldvt >= skv and ldvt_ip >= skv_ip", entry);
+    if (!aligned) {
+        mf_set_error("%s: pointers must be 16-byte aligned", entry);
+        return MF_EALIGN;
+    }
+    AttnArgs a{};
+    a.q = (const char*)q.hi; a.q2 = (const char*)q.lo; a.ldq = q.ld;
+    a.k = (const char*)k.hi; a.k2 = (const char*)k.lo; a.ldk = k.ld;
+    a.vt = (const char*)vt.hi; a.vt2 = (const char*)vt.lo; a.ldvt = vt.ld;
+    a.k_ip = (const char*)k_ip.hi; a.k_ip2 = (const char*)k_ip.lo; a.ldk_ip = k_ip.ld;
+    a.vt_ip = (const char*)vt_ip.hi; a.vt_ip2 = (const char*)vt_ip.lo; a.ldvt_ip = vt_ip.ld;
+    a.out = (char*)out; a.ldo = ldo; a.lse = lse;
+    a.heads = heads; a.sq = sq; a.skv = skv; a.batch = batch; a.skv_ip = skv_ip;
+    a.c = scale * LOG2E; a.ip_scale = ip_scale; a.no_xcd_order = no_xcd_order();
+    return launch_for_head_dim(entry, FwdHeadDims<FL, V>{}, head_dim, [&](auto hd) {
+        dim3 grid((unsigned)(((sq + 127) / 128) * heads * batch));
+        hipLaunchKernelGGL((attn_fwd_kernel<decltype(hd)::value, true, SP, FL == FP16, V == CAUSAL, V == IP>), grid, dim3(256), 0,
+                           (hipStream_t)stream, a);
+    });
+}
+
 extern "C" int mf_attention_bf16_lse(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                                      void* out, int64_t ldo, float* lse, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
-                                     int32_t head_dim, float scale, void* stream);
+                                     int32_t head_dim, float scale, void* stream) {
+    return attention_fwd<BF16, PLAIN>("mf_attention_bf16_lse", {q, nullptr, ldq}, {k, nullptr, ldk}, {vt, nullptr, ldvt}, {}, {}, out, ldo, lse,
+                                      batch, heads, sq, skv, 0, head_dim, scale, 0.0f, stream);
+}
+
 extern "C" int mf_attention_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                                  void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
                                  int32_t head_dim, float scale, void* stream) {
     return mf_attention_bf16_lse(q, ldq, k, ldk, vt, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale, stream);
 }
 
-static int attention_16(bool f16, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
-                        void* out, int64_t ldo, float* lse, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
-                        int32_t head_dim, float scale, void* stream, bool causal = false);
-
-extern "C" int mf_attention_bf16_lse(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
-                                     void* out, int64_t ldo, float* lse, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
-                                     int32_t head_dim, float scale, void* stream) {
-    return attention_16(false, q, ldq, k, ldk, vt, ldvt, out, ldo, lse, batch, heads, sq, skv, head_dim, scale, stream);
-}
-
 extern "C" int mf_attention_f16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                                 void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
                                 int32_t head_dim, float scale, void* stream) {
-    return attention_16(true, q, ldq, k, ldk, vt, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale, stream);
+    return attention_fwd<FP16, PLAIN>("mf_attention_f16", {q, nullptr, ldq}, {k, nullptr, ldk}, {vt, nullptr, ldvt}, {}, {}, out, ldo, nullptr,
+                                      batch, heads, sq, skv, 0, head_dim, scale, 0.0f, stream);
 }
 
 extern "C" int mf_attention_causal_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                                         void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
                                         int32_t head_dim, float scale, void* stream) {
-    return attention_16(false, q, ldq, k, ldk, vt, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale, stream, true);
+    return attention_fwd<BF16, CAUSAL>("mf_attention_causal_bf16", {q, nullptr, ldq}, {k, nullptr, ldk}, {vt, nullptr, ldvt}, {}, {}, out, ldo,
+                                       nullptr, batch, heads, sq, skv, 0, head_dim, scale, 0.0f, stream);
 }
 
 extern "C" int mf_attention_causal_f16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                                        void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
                                        int32_t head_dim, float scale, void* stream) {
-    return attention_16(true, q, ldq, k, ldk, vt, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale, stream, true);
+    return attention_fwd<FP16, CAUSAL>("mf_attention_causal_f16", {q, nullptr, ldq}, {k, nullptr, ldk}, {vt, nullptr, ldvt}, {}, {}, out, ldo,
+                                       nullptr, batch, heads, sq, skv, 0, head_dim, scale, 0.0f, stream);
 }
 
-static int attention_16(bool f16, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
-                        void* out, int64_t ldo, float* lse, int32_t batch, int32_t heads, int32_t sq, int32_t skv,
-                        int32_t head_dim, float scale, void* stream, bool causal) {
-    MF_CHECK_ARG(q && k && vt && out, "mf_attention_bf16: null pointer");
-    MF_CHECK_ARG(batch >= 1 && heads >= 1 && sq >= 1 && skv >= 1, "mf_attention_bf16: bad sizes");
-    MF_CHECK_ARG(!causal || sq == skv, "mf_attention_causal: the causal mask needs sq == skv (got %d, %d)", sq, skv);
-    MF_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 8 == 0 && ldvt >= skv,
-                 "mf_attention_bf16: leading dims must be multiples of 8 and ldvt >= skv");
-    if (!mf_aligned16(q) || !mf_aligned16(k) || !mf_aligned16(vt) || !mf_aligned16(out)) {
-        mf_set_error("mf_attention_bf16: pointers must be 16-byte aligned");
-        return MF_EALIGN;
-    }
-    AttnArgs a{};
-    a.q = (const char*)q; a.ldq = ldq; a.k = (const char*)k; a.ldk = ldk; a.vt = (const char*)vt; a.ldvt = ldvt;
-    a.out = (char*)out; a.ldo = ldo; a.heads = heads; a.sq = sq; a.skv = skv; a.batch = batch;
-    a.lse = lse;
-    a.c = scale * 1.44269504088896340736f;
-    { static const bool off = getenv("MFHIP_ATTN_NOXCD") != nullptr; a.no_xcd_order = off; }
-    hipStream_t s = (hipStream_t)stream;
-    if (causal) {
-        switch (f16 ? -head_dim : head_dim) {
-            case 8: launch_attn<8, false, false, true>(a, batch, s); break;
-            case 64: launch_attn<64, false, false, true>(a, batch, s); break;
-            case -8: launch_attn<8, false, true, true>(a, batch, s); break;
-            case -64: launch_attn<64, false, true, true>(a, batch, s); break;
-            default:
-                mf_set_error("mf_attention_causal: unsupported head_dim %d (have 8, 64)", head_dim);
-                return MF_EINVAL;
-        }
-        MF_CHECK_LAUNCH("mf_attention_causal");
-        return MF_OK;
-    }
-    switch (f16 ? -head_dim : head_dim) {
-        case 8: launch_attn<8>(a, batch, s); break;
-        case 40: launch_attn<40>(a, batch, s); break;
-        case 64: launch_attn<64>(a, batch, s); break;
-        case 80: launch_attn<80>(a, batch, s); break;
-        case 160: launch_attn<160>(a, batch, s); break;
-        case -8: launch_attn<8, false, true>(a, batch, s); break;
-        case -40: launch_attn<40, false, true>(a, batch, s); break;
-        case -64: launch_attn<64, false, true>(a, batch, s); break;
-        case -80: launch_attn<80, false, true>(a, batch, s); break;
-        case -160: launch_attn<160, false, true>(a, batch, s); break;
-        default:
-            mf_set_error("mf_attention_bf16: unsupported head_dim %d (have 8, 40, 64, 80, 160)", head_dim);
-            return MF_EINVAL;
-    }
-    MF_CHECK_LAUNCH("mf_attention_bf16");
-    return MF_OK;
+extern "C" int mf_attention_f16x3_lse(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                                      const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, float* lse, int32_t batch,
+                                      int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream) {
+    return attention_fwd<SPLIT, PLAIN>("mf_attention_f16x3_lse", {q_hi, q_lo, ldq}, {k_hi, k_lo, ldk}, {vt_hi, vt_lo, ldvt}, {}, {}, out, ldo, lse,
+                                       batch, heads, sq, skv, 0, head_dim, scale, 0.0f, stream);
+}
+
+extern "C" int mf_attention_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                                  const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, int32_t batch,
+                                  int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream) {
+    return attention_fwd<SPLIT, PLAIN>("mf_attention_f16x3", {q_hi, q_lo, ldq}, {k_hi, k_lo, ldk}, {vt_hi, vt_lo, ldvt}, {}, {}, out, ldo, nullptr,
+                                       batch, heads, sq, skv, 0, head_dim, scale, 0.0f, stream);
+}
+
+extern "C" int mf_attention_causal_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                                         const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, int32_t batch,
+                                         int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream) {
+    return attention_fwd<SPLIT, CAUSAL>("mf_attention_causal_f16x3", {q_hi, q_lo, ldq}, {k_hi, k_lo, ldk}, {vt_hi, vt_lo, ldvt}, {}, {}, out, ldo,
+                                        nullptr, batch, heads, sq, skv, 0, head_dim, scale, 0.0f, stream);
+}
+
+// ---- decoupled cross-attention (IP): a second key / value segment with its own softmax, one launch ----
+extern "C" int mf_attention_ip_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, const void* k_ip,
+                                    int64_t ldk_ip, const void* vt_ip, int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads,
+                                    int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale, float ip_scale, void* stream) {
+    return attention_fwd<BF16, IP>("mf_attention_ip_bf16", {q, nullptr, ldq}, {k, nullptr, ldk}, {vt, nullptr, ldvt}, {k_ip, nullptr, ldk_ip},
+                                   {vt_ip, nullptr, ldvt_ip}, out, ldo, nullptr, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale, stream);
+}
+
+extern "C" int mf_attention_ip_f16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, const void* k_ip,
+                                   int64_t ldk_ip, const void* vt_ip, int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads,
+                                   int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale, float ip_scale, void* stream) {
+    return attention_fwd<FP16, IP>("mf_attention_ip_f16", {q, nullptr, ldq}, {k, nullptr, ldk}, {vt, nullptr, ldvt}, {k_ip, nullptr, ldk_ip},
+                                   {vt_ip, nullptr, ldvt_ip}, out, ldo, nullptr, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale, stream);
+}
+
+extern "C" int mf_attention_ip_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
+                                     const void* vt_hi, const void* vt_lo, int64_t ldvt, const void* k_ip_hi, const void* k_ip_lo,
+                                     int64_t ldk_ip, const void* vt_ip_hi, const void* vt_ip_lo, int64_t ldvt_ip, float* out, int64_t ldo,
+                                     int32_t batch, int32_t heads, int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale,
+                                     float ip_scale, void* stream) {
+    return attention_fwd<SPLIT, IP>("mf_attention_ip_f16x3", {q_hi, q_lo, ldq}, {k_hi, k_lo, ldk}, {vt_hi, vt_lo, ldvt}, {k_ip_hi, k_ip_lo, ldk_ip},
+                                    {vt_ip_hi, vt_ip_lo, ldvt_ip}, out, ldo, nullptr, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale,
+                                    stream);
 }
 
 extern "C" int mf_split_halves(const float* x, void* hi, void* lo, int64_t n, void* stream) {
@@ -1055,160 +1120,9 @@ extern "C" int mf_split_halves(const float* x, void* hi, void* lo, int64_t n, vo
     return MF_OK;
 }
 
-extern "C" int mf_attention_f16x3_lse(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
-                                      const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, float* lse, int32_t batch,
-                                      int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream);
-
-extern "C" int mf_attention_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
-                                  const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, int32_t batch,
-                                  int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream) {
-    return mf_attention_f16x3_lse(q_hi, q_lo, ldq, k_hi, k_lo, ldk, vt_hi, vt_lo, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale,
-                                  stream);
-}
-
-static int attention_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
-                           const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, float* lse, int32_t batch,
-                           int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream, bool causal);
-
-extern "C" int mf_attention_f16x3_lse(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
-                                      const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, float* lse, int32_t batch,
-                                      int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream) {
-    return attention_f16x3(q_hi, q_lo, ldq, k_hi, k_lo, ldk, vt_hi, vt_lo, ldvt, out, ldo, lse, batch, heads, sq, skv, head_dim, scale, stream, false);
-}
-
-extern "C" int mf_attention_causal_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
-                                         const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, int32_t batch,
-                                         int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream) {
-    return attention_f16x3(q_hi, q_lo, ldq, k_hi, k_lo, ldk, vt_hi, vt_lo, ldvt, out, ldo, nullptr, batch, heads, sq, skv, head_dim, scale, stream, true);
-}
-
-static int attention_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
-                           const void* vt_hi, const void* vt_lo, int64_t ldvt, float* out, int64_t ldo, float* lse, int32_t batch,
-                           int32_t heads, int32_t sq, int32_t skv, int32_t head_dim, float scale, void* stream, bool causal) {
-    MF_CHECK_ARG(q_hi && q_lo && k_hi && k_lo && vt_hi && vt_lo && out, "mf_attention_f16x3: null pointer");
-    MF_CHECK_ARG(batch >= 1 && heads >= 1 && sq >= 1 && skv >= 1, "mf_attention_f16x3: bad sizes");
-    MF_CHECK_ARG(!causal || sq == skv, "mf_attention_causal: the causal mask needs sq == skv (got %d, %d)", sq, skv);
-    MF_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0 && ldvt >= skv,
-                 "mf_attention_f16x3: leading dims must be multiples of 8 (ldo: 4) and ldvt >= skv");
-    if (!mf_aligned16(q_hi) || !mf_aligned16(q_lo) || !mf_aligned16(k_hi) || !mf_aligned16(k_lo) || !mf_aligned16(vt_hi) ||
-        !mf_aligned16(vt_lo) || !mf_aligned16(out)) {
-        mf_set_error("mf_attention_f16x3: pointers must be 16-byte aligned");
-        return MF_EALIGN;
-    }
-    AttnArgs a{};
-    a.q = (const char*)q_hi; a.q2 = (const char*)q_lo; a.ldq = ldq;
-    a.k = (const char*)k_hi; a.k2 = (const char*)k_lo; a.ldk = ldk;
-    a.vt = (const char*)vt_hi; a.vt2 = (const char*)vt_lo; a.ldvt = ldvt;
-    a.out = (char*)out; a.ldo = ldo; a.heads = heads; a.sq = sq; a.skv = skv; a.batch = batch;
-    a.lse = lse;
-    a.c = scale * 1.44269504088896340736f;
-    hipStream_t s = (hipStream_t)stream;
-    if (causal) {
-        switch (head_dim) {
-            case 8: launch_attn<8, true, false, true>(a, batch, s); break;
-            case 64: launch_attn<64, true, false, true>(a, batch, s); break;
-            default:
-                mf_set_error("mf_attention_causal: unsupported head_dim %d (have 8, 64)", head_dim);
-                return MF_EINVAL;
-        }
-        MF_CHECK_LAUNCH("mf_attention_causal");
-        return MF_OK;
-    }
-    switch (head_dim) {
-        case 8: launch_attn<8, true>(a, batch, s); break;
-        case 40: launch_attn<40, true>(a, batch, s); break;
-        case 64: launch_attn<64, true>(a, batch, s); break;
-        case 80: launch_attn<80, true>(a, batch, s); break;
-        default:
-            mf_set_error("mf_attention_f16x3: unsupported head_dim %d (have 8, 40, 64, 80)", head_dim);
-            return MF_EINVAL;
-    }
-    MF_CHECK_LAUNCH("mf_attention_f16x3");
-    return MF_OK;
-}
-
-// ---- decoupled cross-attention (IP): a second key / value segment with its own softmax, one launch ----
-static int attention_ip(int flavour /* 0 bf16, 1 fp16, 2 split */, const void* const q[2], int64_t ldq, const void* const k[2], int64_t ldk,
-                        const void* const vt[2], int64_t ldvt, const void* const k_ip[2], int64_t ldk_ip, const void* const vt_ip[2],
-                        int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads, int32_t sq, int32_t skv, int32_t skv_ip,
-                        int32_t head_dim, float scale, float ip_scale, void* stream) {
-    const int np = flavour == 2 ? 2 : 1;
-    for (int pl = 0; pl < np; ++pl) {
-        MF_CHECK_ARG(q[pl] && k[pl] && vt[pl] && k_ip[pl] && vt_ip[pl] && out, "mf_attention_ip: null pointer");
-        if (!mf_aligned16(q[pl]) || !mf_aligned16(k[pl]) || !mf_aligned16(vt[pl]) || !mf_aligned16(k_ip[pl]) || !mf_aligned16(vt_ip[pl]) ||
-            !mf_aligned16(out)) {
-            mf_set_error("mf_attention_ip: pointers must be 16-byte aligned");
-            return MF_EALIGN;
-        }
-    }
-    MF_CHECK_ARG(batch >= 1 && heads >= 1 && sq >= 1 && skv >= 1, "mf_attention_ip: bad sizes");
-    MF_CHECK_ARG(skv_ip >= 1 && skv_ip <= 64, "mf_attention_ip: skv_ip = %d, the ip segment is one key tile (1 .. 64)", skv_ip);
-    MF_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldk_ip % 8 == 0 && ldvt_ip % 8 == 0 && ldo % (flavour == 2 ? 4 : 8) == 0 &&
-                     ldvt >= skv && ldvt_ip >= skv_ip,
-                 "mf_attention_ip: leading dims must be multiples of 8 (fp32 ldo: 4), ldvt >= skv and ldvt_ip >= skv_ip");
-    AttnArgs a{};
-    a.q = (const char*)q[0]; a.q2 = (const char*)q[1]; a.ldq = ldq;
-    a.k = (const char*)k[0]; a.k2 = (const char*)k[1]; a.ldk = ldk;
-    a.vt = (const char*)vt[0]; a.vt2 = (const char*)vt[1]; a.ldvt = ldvt;
-    a.k_ip = (const char*)k_ip[0]; a.k_ip2 = (const char*)k_ip[1]; a.ldk_ip = ldk_ip;
-    a.vt_ip = (const char*)vt_ip[0]; a.vt_ip2 = (const char*)vt_ip[1]; a.ldvt_ip = ldvt_ip;
-    a.out = (char*)out; a.ldo = ldo; a.heads = heads; a.sq = sq; a.skv = skv; a.batch = batch;
-    a.skv_ip = skv_ip; a.ip_scale = ip_scale;
-    a.c = scale * 1.44269504088896340736f;
-    { static const bool off = getenv("MFHIP_ATTN_NOXCD") != nullptr; a.no_xcd_order = off; }
-    hipStream_t s = (hipStream_t)stream;
-    switch (flavour * 1000 + head_dim) {
-        case 8: launch_attn<8, false, false, false, true>(a, batch, s); break;
-        case 40: launch_attn<40, false, false, false, true>(a, batch, s); break;
-        case 64: launch_attn<64, false, false, false, true>(a, batch, s); break;
-        case 80: launch_attn<80, false, false, false, true>(a, batch, s); break;
-        case 160: launch_attn<160, false, false, false, true>(a, batch, s); break;
-        case 1008: launch_attn<8, false, true, false, true>(a, batch, s); break;
-        case 1040: launch_attn<40, false, true, false, true>(a, batch, s); break;
-        case 1064: launch_attn<64, false, true, false, true>(a, batch, s); break;
-        case 1080: launch_attn<80, false, true, false, true>(a, batch, s); break;
-        case 1160: launch_attn<160, false, true, false, true>(a, batch, s); break;
-        case 2008: launch_attn<8, true, false, false, true>(a, batch, s); break;
-        case 2040: launch_attn<40, true, false, false, true>(a, batch, s); break;
-        case 2064: launch_attn<64, true, false, false, true>(a, batch, s); break;
-        case 2080: launch_attn<80, true, false, false, true>(a, batch, s); break;
-        default:
-            mf_set_error("mf_attention_ip: unsupported head_dim %d (have 8, 40, 64, 80, and 160 for the 16-bit flavours)", head_dim);
-            return MF_EINVAL;
-    }
-    MF_CHECK_LAUNCH("mf_attention_ip");
-    return MF_OK;
-}
-
-extern "C" int mf_attention_ip_bf16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, const void* k_ip,
-                                    int64_t ldk_ip, const void* vt_ip, int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads,
-                                    int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale, float ip_scale, void* stream) {
-    const void *qq[2] = {q, nullptr}, *kk[2] = {k, nullptr}, *vv[2] = {vt, nullptr}, *ki[2] = {k_ip, nullptr}, *vi[2] = {vt_ip, nullptr};
-    return attention_ip(0, qq, ldq, kk, ldk, vv, ldvt, ki, ldk_ip, vi, ldvt_ip, out, ldo, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale,
-                        stream);
-}
-
-extern "C" int mf_attention_ip_f16(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt, const void* k_ip,
-                                   int64_t ldk_ip, const void* vt_ip, int64_t ldvt_ip, void* out, int64_t ldo, int32_t batch, int32_t heads,
-                                   int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale, float ip_scale, void* stream) {
-    const void *qq[2] = {q, nullptr}, *kk[2] = {k, nullptr}, *vv[2] = {vt, nullptr}, *ki[2] = {k_ip, nullptr}, *vi[2] = {vt_ip, nullptr};
-    return attention_ip(1, qq, ldq, kk, ldk, vv, ldvt, ki, ldk_ip, vi, ldvt_ip, out, ldo, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale,
-                        stream);
-}
-
-extern "C" int mf_attention_ip_f16x3(const void* q_hi, const void* q_lo, int64_t ldq, const void* k_hi, const void* k_lo, int64_t ldk,
-                                     const void* vt_hi, const void* vt_lo, int64_t ldvt, const void* k_ip_hi, const void* k_ip_lo,
-                                     int64_t ldk_ip, const void* vt_ip_hi, const void* vt_ip_lo, int64_t ldvt_ip, float* out, int64_t ldo,
-                                     int32_t batch, int32_t heads, int32_t sq, int32_t skv, int32_t skv_ip, int32_t head_dim, float scale,
-                                     float ip_scale, void* stream) {
-    const void *qq[2] = {q_hi, q_lo}, *kk[2] = {k_hi, k_lo}, *vv[2] = {vt_hi, vt_lo}, *ki[2] = {k_ip_hi, k_ip_lo}, *vi[2] = {vt_ip_hi, vt_ip_lo};
-    return attention_ip(2, qq, ldq, kk, ldk, vv, ldvt, ki, ldk_ip, vi, ldvt_ip, out, ldo, batch, heads, sq, skv, skv_ip, head_dim, scale, ip_scale,
-                        stream);
-}
-
 template <int HD, bool B16 = false>
 static void launch_attn_bwd(const mf_attn_bwd_desc* d, hipStream_t s) {
-    const float c = d->scale * 1.44269504088896340736f;
+    const float c = d->scale * LOG2E;
     int sh = 0;
     while (!B16 && sh < 8 && (2 << sh) <= d->skv) ++sh;        // 2^sh <= skv, at most 2^8: P * 2^sh <= 256, far inside fp16 (bf16: none)
     const float pshift = (float)sh, inv_pscale = 1.0f / (float)(1 << sh);
@@ -1244,73 +1158,68 @@ static void launch_attn_bwd(const mf_attn_bwd_desc* d, hipStream_t s) {
 
 extern "C" int mf_sizeof_attn_bwd_desc(void) { return (int)sizeof(mf_attn_bwd_desc); }
 
-extern "C" int mf_attention_bwd_f16x3(const mf_attn_bwd_desc* d, void* stream) {
-    MF_CHECK_ARG(d && d->q_hi && d->q_lo && d->k_hi && d->k_lo && d->v_hi && d->v_lo && d->do_hi && d->do_lo && d->qt_hi && d->qt_lo && d->kt_hi &&
-                     d->kt_lo && d->dot_hi && d->dot_lo && d->lse && d->dd && d->dq && d->dk && d->dv,
-                 "mf_attention_bwd_f16x3: null pointer");
-    MF_CHECK_ARG(d->batch >= 1 && d->heads >= 1 && d->sq >= 1 && d->skv >= 1, "mf_attention_bwd_f16x3: bad sizes");
+template <bool B16>
+using BwdHeadDims = std::conditional_t<B16, HeadDims<8, 40, 80>,      // single planes only: the split form's tiles do not fit in LDS at 80
+                                       // 64 / 80 would need 204 KB of LDS for the double-buffered dK/dV pass; their layers (<= 1024 tokens) keep
+                                       // the unfused backward
+                                       HeadDims<8, 40>>;
+
+// The one backward path.  B16: one bf16 plane per operand (the *_hi pointers; *_lo are ignored), else two fp16 planes.
+template <bool B16>
+static int attention_bwd(const char* entry, const mf_attn_bwd_desc* d, void* stream) {
+    MF_CHECK_ARG(d, "%s: null pointer", entry);
+    const void* const planes[2][7] = {{d->q_hi, d->k_hi, d->v_hi, d->do_hi, d->qt_hi, d->kt_hi, d->dot_hi},
+                                      {d->q_lo, d->k_lo, d->v_lo, d->do_lo, d->qt_lo, d->kt_lo, d->dot_lo}};
+    const void* const single[] = {d->lse, d->dd, d->dq, d->dk, d->dv};
+    bool null = false, aligned = true;
+    auto look = [&](const void* p) { null |= !p; aligned &= mf_aligned16(p); };
+    for (const void* p : single) look(p);
+    for (int pl = 0; pl < (B16 ? 1 : 2); ++pl)
+        for (const void* p : planes[pl]) look(p);
+    MF_CHECK_ARG(!null, "%s: null pointer", entry);
+    MF_CHECK_ARG(d->batch >= 1 && d->heads >= 1 && d->sq >= 1 && d->skv >= 1, "%s: bad sizes", entry);
     MF_CHECK_ARG(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0 && d->lddo % 8 == 0 && d->ldqt % 8 == 0 && d->ldkt % 8 == 0 &&
                      d->lddot % 8 == 0 && d->ldo % 4 == 0 && d->ldqt >= d->sq && d->lddot >= d->sq && d->ldkt >= d->skv && d->sq % 4 == 0,
-                 "mf_attention_bwd_f16x3: leading dims must be multiples of 8 (ldo: 4), transposed rows at least as long as the sequence, sq %% 4 == 0");
-    const void* ptrs[] = {d->q_hi, d->q_lo, d->k_hi, d->k_lo, d->v_hi, d->v_lo, d->do_hi, d->do_lo, d->qt_hi, d->qt_lo, d->kt_hi, d->kt_lo,
-                          d->dot_hi, d->dot_lo, d->dq, d->dk, d->dv, d->lse, d->dd};
-    for (const void* q : ptrs)
-        if (!mf_aligned16(q)) {
-            mf_set_error("mf_attention_bwd_f16x3: pointers must be 16-byte aligned");
-            return MF_EALIGN;
-        }
-    hipStream_t s = (hipStream_t)stream;
-    switch (d->head_dim) {
-        case 8: launch_attn_bwd<8>(d, s); break;
-        case 40: launch_attn_bwd<40>(d, s); break;
-        default:       // 64 / 80 would need 204 KB of LDS for the double-buffered dK/dV pass; their layers (<= 1024 tokens) keep the unfused backward
-            mf_set_error("mf_attention_bwd_f16x3: unsupported head_dim %d (have 8, 40)", d->head_dim);
-            return MF_EINVAL;
+                 "%s: leading dims must be multiples of 8 (ldo: 4), transposed rows at least as long as the sequence, sq %% 4 == 0", entry);
+    if (!aligned) {
+        mf_set_error("%s: pointers must be 16-byte aligned", entry);
+        return MF_EALIGN;
     }
-    MF_CHECK_LAUNCH("mf_attention_bwd_f16x3");
-    return MF_OK;
+    return launch_for_head_dim(entry, BwdHeadDims<B16>{}, d->head_dim,
+                               [&](auto hd) { launch_attn_bwd<decltype(hd)::value, B16>(d, (hipStream_t)stream); });
 }
 
-extern "C" int mf_attention_bwd_bf16(const mf_attn_bwd_desc* d, void* stream) {
-    MF_CHECK_ARG(d && d->q_hi && d->k_hi && d->v_hi && d->do_hi && d->qt_hi && d->kt_hi && d->dot_hi && d->lse && d->dd && d->dq && d->dk && d->dv,
-                 "mf_attention_bwd_bf16: null pointer");
-    MF_CHECK_ARG(d->batch >= 1 && d->heads >= 1 && d->sq >= 1 && d->skv >= 1, "mf_attention_bwd_bf16: bad sizes");
-    MF_CHECK_ARG(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0 && d->lddo % 8 == 0 && d->ldqt % 8 == 0 && d->ldkt % 8 == 0 &&
-                     d->lddot % 8 == 0 && d->ldo % 4 == 0 && d->ldqt >= d->sq && d->lddot >= d->sq && d->ldkt >= d->skv && d->sq % 4 == 0,
-                 "mf_attention_bwd_bf16: leading dims must be multiples of 8 (ldo: 4), transposed rows at least as long as the sequence, sq %% 4 == 0");
-    const void* ptrs[] = {d->q_hi, d->k_hi, d->v_hi, d->do_hi, d->qt_hi, d->kt_hi, d->dot_hi, d->dq, d->dk, d->dv, d->lse, d->dd};
-    for (const void* q : ptrs)
-        if (!mf_aligned16(q)) {
-            mf_set_error("mf_attention_bwd_bf16: pointers must be 16-byte aligned");
-            return MF_EALIGN;
-        }
-    hipStream_t s = (hipStream_t)stream;
-    switch (d->head_dim) {
-        case 8: launch_attn_bwd<8, true>(d, s); break;
-        case 40: launch_attn_bwd<40, true>(d, s); break;
-        case 80: launch_attn_bwd<80, true>(d, s); break;      // single planes only: the split form's tiles do not fit in LDS at 80
-        default:
-            mf_set_error("mf_attention_bwd_bf16: unsupported head_dim %d (have 8, 40, 80)", d->head_dim);
-            return MF_EINVAL;
-    }
-    MF_CHECK_LAUNCH("mf_attention_bwd_bf16");
-    return MF_OK;
-}
+extern "C" int mf_attention_bwd_f16x3(const mf_attn_bwd_desc* d, void* stream) { return attention_bwd<false>("mf_attention_bwd_f16x3", d, stream); }
 
-extern "C" int mf_rowdot_heads(const float* a, const float* b, float* out, int32_t batch, int32_t sq, int32_t heads, int32_t head_dim, int64_t ld,
-                               void* stream) {
+extern "C" int mf_attention_bwd_bf16(const mf_attn_bwd_desc* d, void* stream) { return attention_bwd<true>("mf_attention_bwd_bf16", d, stream); }
+
+// B16: b (the forward's output O) is bf16.  A thread reads four elements of b at a time: 16 bytes of fp32, 8 of bf16.
+template <bool B16>
+static int rowdot_heads(const char* entry, const float* a, const void* b, float* out, int32_t batch, int32_t sq, int32_t heads, int32_t head_dim,
+                        int64_t ld, void* stream) {
+    constexpr uintptr_t b_mask = B16 ? 7 : 15;
     MF_CHECK_ARG(a && b && out && batch >= 1 && sq >= 1 && heads >= 1 && head_dim >= 4 && head_dim % 4 == 0 && ld % 4 == 0 && ld >= heads * head_dim,
-                 "mf_rowdot_heads: bad arguments (head_dim and ld multiples of 4)");
-    if (!mf_aligned16(a) || !mf_aligned16(b)) {
-        mf_set_error("mf_rowdot_heads: pointers must be 16-byte aligned");
+                 "%s: bad arguments (head_dim and ld multiples of 4)", entry);
+    if (!mf_aligned16(a) || (((uintptr_t)b) & b_mask) != 0) {
+        mf_set_error("%s: a must be 16-byte, b %d-byte aligned", entry, (int)b_mask + 1);
         return MF_EALIGN;
     }
     const int64_t total = (int64_t)batch * sq * heads;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(rowdot_heads_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, (const void*)b, out, batch, sq, heads, head_dim, ld);
-    MF_CHECK_LAUNCH("mf_rowdot_heads");
+    hipLaunchKernelGGL(rowdot_heads_kernel<B16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, batch, sq, heads, head_dim, ld);
+    MF_CHECK_LAUNCH(entry);
     return MF_OK;
+}
+
+extern "C" int mf_rowdot_heads(const float* a, const float* b, float* out, int32_t batch, int32_t sq, int32_t heads, int32_t head_dim, int64_t ld,
+                               void* stream) {
+    return rowdot_heads<false>("mf_rowdot_heads", a, b, out, batch, sq, heads, head_dim, ld, stream);
+}
+
+extern "C" int mf_rowdot_heads_bf16(const float* a, const void* b, float* out, int32_t batch, int32_t sq, int32_t heads, int32_t head_dim, int64_t ld,
+                                    void* stream) {
+    return rowdot_heads<true>("mf_rowdot_heads_bf16", a, b, out, batch, sq, heads, head_dim, ld, stream);
 }
 
 // D = rowdot(dO, O16) AND dO16 = bf16(dO) from one read of dO (the backward needs both).  A thread owns 8 channels of one row: two
@@ -1362,21 +1271,5 @@ extern "C" int mf_rowdot_heads_cast(const float* a, const void* b16, void* a16, 
     hipLaunchKernelGGL(rowdot_cast_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, (const unsigned short*)b16,
                        (unsigned short*)a16, out, batch, sq, heads, head_dim / 8, c8, rpp);
     MF_CHECK_LAUNCH("mf_rowdot_heads_cast");
-    return MF_OK;
-}
-
-extern "C" int mf_rowdot_heads_bf16(const float* a, const void* b, float* out, int32_t batch, int32_t sq, int32_t heads, int32_t head_dim, int64_t ld,
-                                    void* stream) {
-    MF_CHECK_ARG(a && b && out && batch >= 1 && sq >= 1 && heads >= 1 && head_dim >= 4 && head_dim % 4 == 0 && ld % 4 == 0 && ld >= heads * head_dim,
-                 "mf_rowdot_heads_bf16: bad arguments (head_dim and ld multiples of 4)");
-    if (!mf_aligned16(a) || (((uintptr_t)b) & 7) != 0) {
-        mf_set_error("mf_rowdot_heads_bf16: a must be 16-byte, b 8-byte aligned");
-        return MF_EALIGN;
-    }
-    const int64_t total = (int64_t)batch * sq * heads;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(rowdot_heads_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, batch, sq, heads, head_dim, ld);
-    MF_CHECK_LAUNCH("mf_rowdot_heads_bf16");
     return MF_OK;
 }

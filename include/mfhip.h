@@ -571,6 +571,35 @@ int64_t mf_image_metrics_ws_bytes(int32_t batch, int32_t h, int32_t w, int32_t c
 int mf_image_metrics(const void* pred_u8_nhwc, const void* target_u8_nhwc, const void* mask_u8, int32_t region, int32_t batch,
                      int32_t h, int32_t w, int32_t channels, float data_range, mf_metrics_row* rows_out, void* ws, void* stream);
 
+/* ---- CLIP prompt fidelity on the device (metrics/metrics.py:156-157 calculate_clip_similarity: torchmetrics' clip_score on
+ * openai/clip-vit-large-patch14, i.e. transformers' CLIPProcessor + CLIPModel).  Additive entries: the ABI version stays. ------------
+ * mf_clip_preprocess: uint8 [batch][h][w][3] images -> the A operand of the patch-embedding GEMM, bit for bit what CLIPImageProcessor
+ * (PIL backend) computes:
+ *   1. resize so that the shortest edge is `size`, the other int(size * long / short): PIL's Image.resize(BICUBIC) on 8-bit pixels, the
+ *      horizontal pass first, then the vertical one, a uint8 image between them; a pass whose size does not change is skipped.  htab /
+ *      vtab are that pass' table in device memory, int32 [n_out][2] (first source index, tap count) followed by int32 [n_out][hk or vk]
+ *      coefficients in 22-bit fixed point (built in float64 on the host: frontend.clip_resize_table); NULL exactly when the pass is skipped.
+ *      A sample is clip8((2^21 + sum src * k) >> 22): integer arithmetic only.
+ *   2. centre crop to crop x crop (crop <= size): top = (h1 - crop) / 2, left = (w1 - crop) / 2
+ *   3. (u8 * (1 / 255) - mean[c]) / std[c] in fp32, three roundings, then one rounding to out_dtype
+ *   4. patches_out [batch][(crop / patch)^2][k8]: column c * patch^2 + row * patch + col (patch_embedding.weight.reshape(C, -1)'s order),
+ *      k8 = 3 patch^2 rounded up to 8, the pad columns written as zero; 16-byte aligned.
+ * crop_u8_out (may be NULL): the cropped uint8 image [batch][crop][crop][3].  ws: mf_clip_preprocess_ws_bytes() bytes, 16-byte aligned
+ * (-1 for sizes it refuses).  One or two launches.
+ * mf_clip_vision_embed: out[b][0][:] = class_embedding + pos_table[0]; out[b][1 + i][:] = patches[b][i][:] + pos_table[1 + i], summed
+ * in fp32 and rounded once (mf_embed_tokens' contract); patches [batch][tokens - 1][hidden], hidden % 8 == 0, 16-byte accesses.
+ * mf_clip_score: out[b] = 100 <i, t> / (|i| |t|) for fp32 image_feats / text_feats [batch][dim]; one wave per row, fp32 sums in a fixed
+ * order, one launch; norms_out [batch][2] receives |i| and |t|.  No epsilon: a zero vector gives NaN, as in the reference. */
+int64_t mf_clip_preprocess_ws_bytes(int32_t batch, int32_t h, int32_t w, int32_t size, int32_t crop);
+int mf_clip_preprocess(const void* images_u8_nhwc, int32_t batch, int32_t h, int32_t w, int32_t channels, int32_t size, int32_t crop,
+                       int32_t patch, const int32_t* htab, int32_t hk, const int32_t* vtab, int32_t vk, float mean0, float mean1,
+                       float mean2, float std0, float std1, float std2, void* patches_out, int32_t out_dtype, int32_t k8,
+                       void* crop_u8_out, void* ws, void* stream);
+int mf_clip_vision_embed(const void* patches, const void* class_embedding, const void* pos_table, int32_t in_dtype, void* out,
+                         int32_t out_dtype, int32_t batch, int32_t tokens, int32_t hidden, void* stream);
+int mf_clip_score(const float* image_feats, const float* text_feats, int32_t batch, int32_t dim, float* out, float* norms_out,
+                  void* stream);
+
 /* ============================================================================================
  * Training: the backward pass and the optimizer of examples/brushnet/train_brushnet_mirror.py:1459-1466
  * (accelerator.backward -> ATen autograd in the reference; clip_grad_norm_ :1463; torch.optim.AdamW :1188-1200).

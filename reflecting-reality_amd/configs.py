@@ -70,3 +70,21 @@ CLIP_FIXTURES = {
     "tiny_l": (TINY_CLIP_L_TEXT, False), "tiny_g": (TINY_CLIP_G_TEXT, True), "clip_l": (CLIP_L_TEXT, False),
     "bigg4": (dict(OPENCLIP_BIGG_TEXT, num_hidden_layers=4), True),
 }
+# CLIP vision towers (transformers CLIPVisionConfig fields; image_encoder.py).  CLIP_L_VISION: openai/clip-vit-large-patch14, the scorer of
+# the reference's CLIP_Similarity (metrics/metrics.py:156-157) and the image encoder examples/brushnet/ip_adapter/ loads.  The tiny ones
+# (tools/make_golden_clip_vision.py): tiny_vit_a 17 tokens, K = 192; tiny_vit_b K = 147 -> 152 (pad columns); vit_d64 ViT-L/14's patch
+# width and head dim; vit_l4 ViT-L/14 at full width cut to 4 layers (257 tokens: one query row alone in the third q-tile).
+CLIP_L_VISION = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=224, patch_size=14,
+                     num_channels=3, hidden_act="quick_gelu", layer_norm_eps=1e-5, projection_dim=768)
+TINY_VIT_A = dict(hidden_size=32, intermediate_size=64, num_hidden_layers=2, num_attention_heads=4, image_size=32, patch_size=8,
+                  num_channels=3, hidden_act="quick_gelu", layer_norm_eps=1e-5, projection_dim=16)
+TINY_VIT_B = dict(TINY_VIT_A, image_size=28, patch_size=7)
+VIT_D64 = dict(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2, image_size=56, patch_size=14,
+               num_channels=3, hidden_act="quick_gelu", layer_norm_eps=1e-5, projection_dim=32)
+# fixture name (tests/golden/clip_<name>.npz) -> config; every one is a CLIPVisionModelWithProjection
+CLIP_VISION_FIXTURES = {"tiny_vit_a": TINY_VIT_A, "tiny_vit_b": TINY_VIT_B, "vit_d64": VIT_D64,
+                        "vit_l4": dict(CLIP_L_VISION, num_hidden_layers=4)}
+# tiny_clip: a CLIPModel of tiny_l's text tower and tiny_vit_a, projection 16 (captions through synth.HashTokenizer)
+TINY_CLIP = dict(projection_dim=16, logit_scale_init_value=2.6592, text_config=dict(TINY_CLIP_L_TEXT), vision_config=dict(TINY_VIT_A))
+# openai/clip-vit-large-patch14 as a CLIPModel (tools/bench_clip_score.py)
+CLIP_L = dict(projection_dim=768, logit_scale_init_value=2.6592, text_config=dict(CLIP_L_TEXT), vision_config=dict(CLIP_L_VISION))

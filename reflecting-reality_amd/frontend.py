@@ -88,6 +88,87 @@ def apply_transforms_normals(normals_map, resolution: int = 512, mask=None, norm
     return _resize_crop(hip.hwc_to_chw_affine(x, 1.0, 0.0), resolution, antialias, 2.0, -1.0)
 
 
+# ---- CLIPImageProcessor on the device (mf_clip_preprocess) -------------------------------------------------------------------------------
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)          # transformers.utils.constants OPENAI_CLIP_MEAN / OPENAI_CLIP_STD
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+_PRECISION_BITS = 32 - 8 - 2                             # PIL Resample.c: coefficients in 22-bit fixed point
+_clip_tables: dict = {}
+
+
+def _bicubic_pil(x: np.ndarray) -> np.ndarray:
+    """PIL's bicubic_filter (Resample.c, a = -0.5), in float64."""
+    a = -0.5
+    x = np.abs(x)
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+def clip_resize_table(in_size: int, out_size: int):
+    """The table of one pass of PIL's Image.resize(BICUBIC) on 8-bit pixels (Resample.c precompute_coeffs + normalize_coeffs_8bpc) for
+    in_size -> out_size samples: (bounds int32 [out_size, 2] = (first source index, tap count), coefficients int32 [out_size, ksize]), all
+    from float64 on the host.  An output sample is clip8((2^21 + sum_j src[xmin + j] * k[j]) >> 22)."""
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(np.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size)
+    count = xmax - xmin
+    j = np.arange(ksize, dtype=np.int64)[None, :]
+    w = _bicubic_pil((j + xmin[:, None] - center[:, None] + 0.5) * (1.0 / fs))
+    w = np.where(j < count[:, None], w, 0.0)
+    ww = np.zeros(out_size, dtype=np.float64)
+    for t in range(ksize):                                # the C loop's order of additions
+        ww = ww + w[:, t]
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    k = np.trunc(np.where(w < 0, -0.5, 0.5) + w * float(1 << _PRECISION_BITS)).astype(np.int32)
+    return np.stack([xmin, count], axis=1).astype(np.int32), k
+
+
+def clip_resize_geometry(h: int, w: int, size: int, crop: int):
+    """CLIPImageProcessor: the shortest edge becomes `size`, the other int(size * long / short); the centre crop's offsets are
+    (h1 - crop) // 2 and (w1 - crop) // 2.  -> ((h1, w1), (top, left))."""
+    if h <= w:
+        h1, w1 = size, int(size * w / h)
+    else:
+        h1, w1 = int(size * h / w), size
+    return (h1, w1), ((h1 - crop) // 2, (w1 - crop) // 2)
+
+
+def _clip_device_tables(h: int, w: int, size: int, crop: int, device):
+    key = (h, w, size, str(device))
+    ent = _clip_tables.get(key)
+    if ent is None:
+        (h1, w1), _ = clip_resize_geometry(h, w, size, crop)
+        ent = []
+        for n_in, n_out in ((w, w1), (h, h1)):            # horizontal first, then vertical; a pass whose size does not change is skipped
+            if n_in == n_out:
+                ent += [None, 0]
+            else:
+                bounds, k = clip_resize_table(n_in, n_out)
+                ent += [torch.from_numpy(np.concatenate([bounds.ravel(), k.ravel()])).to(device), k.shape[1]]
+        _clip_tables[key] = ent = tuple(ent)
+    return ent
+
+
+def clip_preprocess(images, size: int = 224, crop: Optional[int] = None, mean=CLIP_MEAN, std=CLIP_STD, out_dtype=torch.float32, patch: int = 14,
+                    return_u8: bool = False, device=None):
+    """CLIPImageProcessor (PIL backend: bicubic shortest-edge resize on uint8, centre crop, rescale, normalise) and the unfold of the patch
+    embedding on the device: images as metrics.to_u8_nhwc takes them (a uint8 NHWC device tensor is read where it lies) -> the patch matrix
+    [B, (crop / patch)^2, K8] in out_dtype, K8 = 3 patch^2 rounded up to 8 with zero pad columns (and, return_u8, the cropped uint8 image
+    [B, crop, crop, 3]).  The integer resize tables are built here in float64, once per (height, width, size), and kept on the device."""
+    from .metrics import to_u8_nhwc
+    crop = size if crop is None else crop
+    x = to_u8_nhwc(images, device)
+    if x.shape[-1] != 3:
+        raise ValueError(f"clip_preprocess takes RGB images, got {x.shape[-1]} channels")
+    if crop > size or crop % patch:
+        raise ValueError(f"clip_preprocess: crop {crop} must not exceed size {size} and must be a multiple of the patch size {patch}")
+    htab, hk, vtab, vk = _clip_device_tables(x.shape[1], x.shape[2], size, crop, x.device)
+    out, u8 = hip.clip_preprocess(x, size, crop, patch, htab, hk, vtab, vk, mean, std, out_dtype, want_u8=return_u8)
+    return (out, u8) if return_u8 else out
+
+
 def mean_normal_over_mask(normals_map, mask, device="cuda") -> torch.Tensor:
     """dataset.py:173-180 (`apply_transforms_normals(..., "ip_adapter")`): the mean of normals_map [H, W, 3] over the pixels where
     mask [H, W] > 0, L2-normalised, as a [1, 3] fp32 device tensor — one reduction on the device (mf_masked_mean_normal)."""

@@ -184,6 +184,9 @@ SIGNATURES = {
     "mf_u8_to_planes": "i:ppiiilp",
     # image scoring (csrc/metrics.hip)
     "mf_sizeof_metrics_row": "i:", "mf_image_metrics_ws_bytes": "l:iiii", "mf_image_metrics": "i:pppiiiiifppp",
+    # CLIP image side and score (csrc/clip_vision.hip)
+    "mf_clip_preprocess_ws_bytes": "l:iiiii", "mf_clip_preprocess": "i:piiiiiiipipiffffffpiippp", "mf_clip_vision_embed": "i:pppipiiiip",
+    "mf_clip_score": "i:ppiippp",
     # training (csrc/train.hip)
     "mf_sizeof_wgrad_desc": "i:", "mf_conv_wgrad_ws_floats": "l:W", "mf_conv_wgrad": "i:Wp", "mf_split_pack": "i:plpliip",
     "mf_transpose": "i:ppiiillllp", "mf_transpose_bf16": "i:ppiiillllp", "mf_colsum_ws_floats": "l:ili", "mf_colsum": "i:plpliliipp",
@@ -1599,6 +1602,53 @@ def metrics_rows(rows: torch.Tensor):
     """The rows of image_metrics() on the host, as a numpy record array with MetricsRow's fields (this is the synchronisation)."""
     import numpy as np
     return np.frombuffer(rows.cpu().numpy().tobytes(), dtype=np.dtype(MetricsRow))
+
+
+def clip_preprocess(images: torch.Tensor, size: int, crop: int, patch: int, htab: Optional[torch.Tensor], hk: int,
+                    vtab: Optional[torch.Tensor], vk: int, mean, std, out_dtype: torch.dtype, want_u8: bool = False):
+    """mf_clip_preprocess on a uint8 [B, H, W, 3] device tensor: (patch matrix [B, (crop / patch)^2, K8] in out_dtype, the cropped uint8
+    image [B, crop, crop, 3] or None).  htab / vtab: the int32 device tables of frontend.clip_resize_table (None: that pass is skipped)."""
+    _req_cuda(images, htab, vtab)
+    if images.dtype != torch.uint8 or images.dim() != 4:
+        raise MfhipError("clip_preprocess: a uint8 [batch, height, width, 3] tensor")
+    images = images.contiguous()
+    b, h, w, c = images.shape
+    nbytes = load().mf_clip_preprocess_ws_bytes(b, h, w, size, crop)
+    if nbytes < 0:
+        raise MfhipError(f"clip_preprocess: {load().mf_last_error().decode()}")
+    ws = scratch("clip_preprocess", (nbytes + 3) // 4, images.device)
+    k8 = (3 * patch * patch + 7) // 8 * 8
+    n = (crop // max(patch, 1)) ** 2
+    out = torch.empty(b, n, k8, dtype=out_dtype, device=images.device)
+    u8 = torch.empty(b, crop, crop, 3, dtype=torch.uint8, device=images.device) if want_u8 else None
+    _launch("mf_clip_preprocess", images, b, h, w, c, size, crop, patch, htab, hk, vtab, vk, *[float(v) for v in mean], *[float(v) for v in std],
+            out, dt_code(out_dtype), k8, u8, ws)
+    return out, u8
+
+
+def clip_vision_embed(patches: torch.Tensor, class_embedding: torch.Tensor, pos_table: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+    """out[b][0] = class_embedding + pos_table[0], out[b][1 + i] = patches[b][i] + pos_table[1 + i] (mf_clip_vision_embed)."""
+    _req_cuda(patches, class_embedding, pos_table)
+    b, n, hidden = patches.shape
+    if (not patches.is_contiguous() or not pos_table.is_contiguous() or tuple(pos_table.shape) != (n + 1, hidden)
+            or tuple(class_embedding.shape) != (hidden,) or not patches.dtype == class_embedding.dtype == pos_table.dtype):
+        raise MfhipError(f"clip_vision_embed: contiguous patches [B, n, hidden], class_embedding [hidden] and pos_table [n + 1, hidden] of one "
+                         f"dtype (got {tuple(patches.shape)}, {tuple(class_embedding.shape)}, {tuple(pos_table.shape)})")
+    out = torch.empty(b, n + 1, hidden, dtype=out_dtype, device=patches.device)
+    _launch("mf_clip_vision_embed", patches, class_embedding, pos_table, dt_code(patches.dtype), out, dt_code(out_dtype), b, n + 1, hidden)
+    return out
+
+
+def clip_score(image_feats: torch.Tensor, text_feats: torch.Tensor):
+    """mf_clip_score: (100 cos(i, t) per row [B], the norms [B, 2]) of two fp32 [B, P] device tensors.  Nothing synchronises."""
+    _req_cuda(image_feats, text_feats)
+    if image_feats.dtype != torch.float32 or text_feats.dtype != torch.float32 or image_feats.dim() != 2 or image_feats.shape != text_feats.shape:
+        raise MfhipError(f"clip_score: two fp32 [batch, dim] tensors of one shape (got {tuple(image_feats.shape)}, {tuple(text_feats.shape)})")
+    i, t = image_feats.contiguous(), text_feats.contiguous()
+    out = torch.empty(i.shape[0], dtype=torch.float32, device=i.device)
+    norms = torch.empty(i.shape[0], 2, dtype=torch.float32, device=i.device)
+    _launch("mf_clip_score", i, t, i.shape[0], i.shape[1], out, norms)
+    return out, norms
 
 
 def _sel_ws(device) -> torch.Tensor:

@@ -8,9 +8,14 @@ One launch sequence of csrc/metrics.hip (mf_image_metrics) over the uint8 NHWC b
 sum and the extrema as exact integers, the sum of the per-position SSIM values; PSNR and the SSIM mean are finished here in float64 from
 that row.  An image that is already uint8 NHWC in device memory is scored where it lies: no copy, no host round trip before the row is read.
 
-Not built (the constructor of MetricsCalculator refuses them by name): LPIPS, CLIP similarity, aesthetic score, ImageReward, HPS and the
-SAM-based `obj` / IoU scores — their networks and weights are not part of this package.  `compute_metrics(..., lpips_fn=f)` calls a
-caller-supplied LPIPS with the normalised tensors the reference builds (metrics.py:60-64)."""
+`CLIP_Similarity` (metrics.py:156-157: torchmetrics' clip_score on openai/clip-vit-large-patch14) is scored on the device too once the
+caller brings the network: clip_score() runs the uint8 image through mf_clip_preprocess, the vision tower of image_encoder.CLIPModel,
+the caption through its text tower, and mf_clip_score; the mean over the pairs and the clamp at 0 are finished here in float64.  The
+weights are something the reference downloads, so `MetricsCalculator(..., clip_model=, clip_tokenizer=)` takes them from the caller.
+
+Not built (the constructor of MetricsCalculator refuses them by name): LPIPS, CLIP similarity without a model, aesthetic score,
+ImageReward, HPS and the SAM-based `obj` / IoU scores — their networks and weights are not part of this package.
+`compute_metrics(..., lpips_fn=f)` calls a caller-supplied LPIPS with the normalised tensors the reference builds (metrics.py:60-64)."""
 from __future__ import annotations
 
 from typing import Callable, Dict, List, Optional, Sequence
@@ -157,7 +162,61 @@ def rows_to_regions(rows: torch.Tensor, elements: int) -> Dict[str, float]:
     return out
 
 
-# what compute_metric dispatches on besides PSNR / SSIM, and where the reference does it (metrics/metrics.py)
+# ---- CLIP_Similarity -------------------------------------------------------------------------------------------------------------------
+def clip_finish(row) -> float:
+    """torchmetrics' CLIPScore.compute from the per-pair scores: max(mean over the pairs, 0), in float64 on the host."""
+    r = np.asarray(row, dtype=np.float64).reshape(-1)
+    return float(max(r.sum() / np.float64(r.size), 0.0))
+
+
+def clip_score_rows(images, captions, model, tokenizer, device=None):
+    """100 cos(image feature, text feature) of every (image, caption) pair as an fp32 [B] DEVICE tensor, and the [B, 2] norms
+    (mf_clip_score); nothing is read back.  `model`: image_encoder.CLIPModel; `images`: what to_u8_nhwc takes (a uint8 NHWC device tensor
+    is read where it lies; a list is a batch of equally sized images); `tokenizer`: a CLIPTokenizer-like callable."""
+    if isinstance(captions, str):
+        captions = [captions]
+    captions = list(captions)
+    dev = model.device if device is None else device
+    if isinstance(images, (list, tuple)):
+        x = torch.cat([to_u8_nhwc(im, dev) for im in images])
+    else:
+        x = to_u8_nhwc(images, dev)
+    if x.shape[0] != len(captions):
+        raise ValueError(f"clip_score: {x.shape[0]} images but {len(captions)} captions")
+    enc = tokenizer(captions, padding="max_length", max_length=model.text.config["max_position_embeddings"], truncation=True,
+                    return_tensors="pt")
+    ids = enc["input_ids"] if isinstance(enc, dict) else enc.input_ids
+    img = model.get_image_features(images=x)
+    txt = model.get_text_features(ids.to(model.device))
+    return hip.clip_score(img, txt)
+
+
+def clip_score(images, captions, model, tokenizer, device=None) -> float:
+    """torchmetrics.functional.multimodal.clip_score (metrics.py:156-157 calculate_clip_similarity): the features of the two projections,
+    each L2-normalised, 100 * their dot product per pair, and max(mean over the pairs, 0).  Captions are tokenised to
+    max_position_embeddings with truncation=True.  Under the causal mask the pooled row (the end-of-text position) sees nothing after
+    its own position, so padding needs no attention_mask.  The mean and the clamp are finished on the host in float64 from the row
+    the device wrote, like finish() for PSNR / SSIM."""
+    rows, _ = clip_score_rows(images, captions, model, tokenizer, device)
+    return clip_finish(rows.cpu().numpy())
+
+
+def _load_clip(clip_model, clip_tokenizer, device):
+    if isinstance(clip_model, (str, bytes)) or hasattr(clip_model, "__fspath__"):
+        from .image_encoder import CLIPModel
+        path = str(clip_model)
+        if clip_tokenizer is None:
+            from transformers import CLIPTokenizer                       # (the checkpoint directory's own vocabulary files)
+            clip_tokenizer = CLIPTokenizer.from_pretrained(path, local_files_only=True)
+        clip_model = CLIPModel.from_pretrained(path, device=device if device is not None else "cuda")
+    if clip_tokenizer is None:
+        raise ValueError("clip_model needs its clip_tokenizer (a CLIPTokenizer of the same checkpoint)")
+    return clip_model, clip_tokenizer
+
+
+# what compute_metric dispatches on besides PSNR / SSIM, and where the reference does it (metrics/metrics.py).  CLIP_Similarity leaves the
+# list when the caller supplies the model.  Aesthetic_Score stays: the reference feeds floats 0 .. 255 through open_clip's transforms
+# (metrics.py:86-102), and neither open_clip nor torchvision exists here to pin that path against, so it is refused, not guessed.
 _UNBUILT = (("LPIPS", "metrics.py:150-151 (calculate_lpips: torchmetrics' LPIPS network)"),
             ("CLIP_Similarity", "metrics.py:156-157 (calculate_clip_similarity: a CLIP model)"),
             ("Aesthetic_Score", "metrics.py:86-102,158-159 (the LAION aesthetic head on open_clip ViT-L-14)"),
@@ -169,19 +228,27 @@ _UNBUILT = (("LPIPS", "metrics.py:150-151 (calculate_lpips: torchmetrics' LPIPS 
 
 class MetricsCalculator:
     """metrics.py:70-165 for the metrics this package computes: names that hold "PSNR" or "SSIM", on the frame or — with "mask" /
-    "mirror" in the name — on a region.  Every other name of the reference is refused at construction."""
+    "mirror" in the name — on a region; and, with `clip_model` (an image_encoder.CLIPModel or a checkpoint directory) and its
+    `clip_tokenizer`, names that hold "CLIP_Similarity".  Every other name of the reference is refused at construction."""
 
     def __init__(self, metrics_to_compute: Sequence[str], device=None, data_dir=None, cache_dir=None, ckpt_path="data/ckpt",
-                 norm_range=[-1, 1]) -> None:
+                 norm_range=[-1, 1], clip_model=None, clip_tokenizer=None) -> None:
         self.device = device                                                # (resolved at the first upload)
         self.metrics_to_compute = list(metrics_to_compute)
         self.norm_range, self.data_dir, self.cache_dir = norm_range, data_dir, cache_dir
+        self.clip_model = self.clip_tokenizer = None
+        if clip_model is not None:
+            self.clip_model, self.clip_tokenizer = _load_clip(clip_model, clip_tokenizer, device)
         for name in self.metrics_to_compute:
             for key, where in _UNBUILT:
+                if key == "CLIP_Similarity" and key in name and self.clip_model is not None:
+                    break
                 if key in name:
                     raise NotImplementedError(f"metric {name!r}: {key} is not built here (the reference: {where}); its network and "
                                               "weights are not part of this package")
-            if "PSNR" not in name and "SSIM" not in name:
+            else:
+                if "PSNR" in name or "SSIM" in name:
+                    continue
                 raise NotImplementedError(f"metric {name!r}: only PSNR and SSIM (frame, *mask*, *mirror*) are built; the reference "
                                           "dispatches at metrics.py:150-165")
 
@@ -190,8 +257,12 @@ class MetricsCalculator:
         return "mask" if "mask" in metric_name else ("mirror" if "mirror" in metric_name else None)      # metrics.py:139-146, in that order
 
     def compute_metric(self, metric_name: str, gen_image, gt_data, caption=None) -> float:
-        if metric_name not in self.metrics_to_compute:
-            MetricsCalculator([metric_name], self.device)                   # the same refusals for a name the constructor never saw
+        if metric_name not in self.metrics_to_compute:                      # the same refusals for a name the constructor never saw
+            MetricsCalculator([metric_name], self.device, clip_model=self.clip_model, clip_tokenizer=self.clip_tokenizer)
+        if "CLIP_Similarity" in metric_name:
+            if not caption:
+                raise ValueError(f"metric {metric_name!r} scores the image against its caption: compute_metric(..., caption=) is required")
+            return clip_score(gen_image, [caption], self.clip_model, self.clip_tokenizer, device=self.device)
         region = self.region_of(metric_name)
         # "mask": the reference takes the dataset's masked_image as the target (:140) and masks the generated image (:141); the region step
         # on that target is the identity (its mirror pixels are black already).  "mirror": both from the full image (:144-145).

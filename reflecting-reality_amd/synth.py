@@ -25,7 +25,8 @@ def fill(key: str, shape: Iterable[int], seed: int = 0) -> torch.Tensor:
     parts = key.split(".")
     leaf = parts[-1]
     parent = parts[-2] if len(parts) >= 2 else ""
-    is_norm = parent.startswith("norm") or parent in ("conv_norm_out", "group_norm") or "layer_norm" in parent   # (CLIP: layer_norm1, final_layer_norm)
+    is_norm = (parent.startswith("norm") or parent in ("conv_norm_out", "group_norm") or "layer_norm" in parent   # (CLIP: layer_norm1, final_layer_norm)
+               or parent in ("pre_layrnorm", "post_layernorm"))                                                  # (CLIP vision; `layrnorm` is transformers' spelling)
     if leaf == "weight" and is_norm and len(shape) == 1:
         return 1.0 + 0.1 * torch.randn(shape, generator=g)
     if leaf == "bias":
@@ -61,6 +62,17 @@ def pipeline_inputs(batch: int, height: int, width: int, seed: int = 1234, cross
     vae_noise = torch.randn(2 * batch, latent_channels, hl, wl, generator=g)   # uncond half, then cond half
     return dict(prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, image=image, mask=mask,
                 depth=depth, latents=latents, vae_noise=vae_noise)
+
+
+def images_u8(seed: int, batch: int, height: int, width: int):
+    """Seeded uint8 [batch, height, width, 3] images with some structure (a gradient under noise) as a numpy array: the inputs of the
+    CLIP vision fixtures, the same on every machine (numpy's PCG64 stream is stable across versions)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:height, 0:width]
+    base = (yy[None, :, :, None] * 3 + xx[None, :, :, None] * 2 + np.arange(3)[None, None, None, :] * 40
+            + np.arange(batch)[:, None, None, None] * 25) % 256
+    return ((base + rng.integers(0, 96, (batch, height, width, 3))) % 256).astype(np.uint8)
 
 
 class HashTokenizer:

@@ -29,6 +29,56 @@ _ACTS = {"quick_gelu": hip.ACT_QUICK_GELU, "gelu": hip.ACT_GELU_ERF}
 _POSITION_IDS = "text_model.embeddings.position_ids"     # integer buffer of older checkpoints: dropped on load, never written
 
 
+def layer_param_shapes(out, prefix: str, cfg) -> None:
+    """The state-dict keys of CLIPEncoder's layers under `prefix` ("text_model.encoder.layers." / "vision_model.encoder.layers."), in
+    transformers' order."""
+    c, inner = cfg["hidden_size"], cfg["intermediate_size"]
+    for i in range(cfg["num_hidden_layers"]):
+        p = f"{prefix}{i}."
+        for nm, shp in (("self_attn.k_proj", (c, c)), ("self_attn.v_proj", (c, c)), ("self_attn.q_proj", (c, c)),
+                        ("self_attn.out_proj", (c, c)), ("layer_norm1", None), ("mlp.fc1", (inner, c)), ("mlp.fc2", (c, inner)),
+                        ("layer_norm2", None)):
+            out[p + nm + ".weight"] = shp or (c,)
+            out[p + nm + ".bias"] = (shp[0],) if shp else (c,)
+
+
+def norm_pair(sd, name: str, device):
+    return (sd[name + ".weight"].to(device, F32).contiguous(), sd[name + ".bias"].to(device, F32).contiguous())
+
+
+def prepare_layers(P: Dict[str, Any], sd, prefix: str, layers: int, prec, dev) -> None:
+    """The device weights of the layers under `prefix`, as encoder_layer() reads them from P."""
+    for i in range(layers):
+        p = f"{prefix}{i}."
+        a = p + "self_attn."
+        P[f"{i}.ln1"] = norm_pair(sd, p + "layer_norm1", dev)
+        P[f"{i}.ln2"] = norm_pair(sd, p + "layer_norm2", dev)
+        P[f"{i}.to_qk"] = ConvWeight(torch.cat([sd[a + "q_proj.weight"], sd[a + "k_proj.weight"]]),
+                                     torch.cat([sd[a + "q_proj.bias"], sd[a + "k_proj.bias"]]), prec, dev)
+        # V^T leaves ops.linear_t with the weight as the A operand: never pre-split
+        P[f"{i}.to_v"] = ConvWeight(sd[a + "v_proj.weight"], sd[a + "v_proj.bias"], prec, dev, raw=True)
+        P[f"{i}.out"] = ConvWeight(sd[a + "out_proj.weight"], sd[a + "out_proj.bias"], prec, dev)
+        P[f"{i}.fc1"] = ConvWeight(sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"], prec, dev)
+        P[f"{i}.fc2"] = ConvWeight(sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"], prec, dev)
+
+
+def encoder_layer(P: Dict[str, Any], i: int, x: torch.Tensor, cfg, prec, eps: float, causal: bool) -> torch.Tensor:
+    """One pre-LN CLIPEncoderLayer (modeling_clip.py) on x [B, S, C]: the text towers run it under the causal mask, the vision tower
+    (image_encoder.py) without one."""
+    b, s, c = x.shape
+    heads = cfg["num_attention_heads"]
+    d = c // heads
+    h = ops.layernorm(x, P[f"{i}.ln1"], eps, prec.act)
+    qk = ops.linear(h, P[f"{i}.to_qk"])
+    vt = ops.linear_t(h, P[f"{i}.to_v"], (s + 7) // 8 * 8)            # 77 keys -> ld 80, pad columns zero
+    o = ops.attention(qk[..., :c], qk[..., c:], vt, heads, s, d ** -0.5, prec, c=c, causal=causal)
+    x = ops.linear(o, P[f"{i}.out"], res0=x)
+    h = ops.layernorm(x, P[f"{i}.ln2"], eps, prec.act)
+    m = ops.linear(h, P[f"{i}.fc1"])
+    hip.act(m, _ACTS[cfg["hidden_act"]], out=m)
+    return ops.linear(m, P[f"{i}.fc2"], res0=x)
+
+
 class CLIPTextOutput:
     """transformers' BaseModelOutputWithPooling / CLIPTextModelOutput as far as the pipelines index them: integer indices walk the
     non-None fields in order (`out[0]`, `out[1]`, `out[-1]`), the names are attributes."""
@@ -91,17 +141,11 @@ class CLIPTextModel(HipModel):
     # -- parameters ---------------------------------------------------------------------------------
     def param_shapes(self) -> "OrderedDict[str, Tuple[int, ...]]":
         cfg = self.config
-        c, inner = cfg["hidden_size"], cfg["intermediate_size"]
+        c = cfg["hidden_size"]
         out: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
         out["text_model.embeddings.token_embedding.weight"] = (cfg["vocab_size"], c)
         out["text_model.embeddings.position_embedding.weight"] = (cfg["max_position_embeddings"], c)
-        for i in range(cfg["num_hidden_layers"]):
-            p = f"text_model.encoder.layers.{i}."
-            for nm, shp in (("self_attn.k_proj", (c, c)), ("self_attn.v_proj", (c, c)), ("self_attn.q_proj", (c, c)),
-                            ("self_attn.out_proj", (c, c)), ("layer_norm1", None), ("mlp.fc1", (inner, c)), ("mlp.fc2", (c, inner)),
-                            ("layer_norm2", None)):
-                out[p + nm + ".weight"] = shp or (c,)
-                out[p + nm + ".bias"] = (shp[0],) if shp else (c,)
+        layer_param_shapes(out, "text_model.encoder.layers.", cfg)
         out["text_model.final_layer_norm.weight"] = (c,)
         out["text_model.final_layer_norm.bias"] = (c,)
         if self._projection:
@@ -134,18 +178,7 @@ class CLIPTextModel(HipModel):
         P: Dict[str, Any] = {}
         P["token_embedding"] = sd["text_model.embeddings.token_embedding.weight"].to(dev, tdt).contiguous()
         P["position_embedding"] = sd["text_model.embeddings.position_embedding.weight"].to(dev, tdt).contiguous()
-        for i in range(self.config["num_hidden_layers"]):
-            p = f"text_model.encoder.layers.{i}."
-            a = p + "self_attn."
-            P[f"{i}.ln1"] = self._norm_pair(sd, p + "layer_norm1")
-            P[f"{i}.ln2"] = self._norm_pair(sd, p + "layer_norm2")
-            P[f"{i}.to_qk"] = ConvWeight(torch.cat([sd[a + "q_proj.weight"], sd[a + "k_proj.weight"]]),
-                                         torch.cat([sd[a + "q_proj.bias"], sd[a + "k_proj.bias"]]), prec, dev)
-            # V^T leaves ops.linear_t with the weight as the A operand: never pre-split
-            P[f"{i}.to_v"] = ConvWeight(sd[a + "v_proj.weight"], sd[a + "v_proj.bias"], prec, dev, raw=True)
-            P[f"{i}.out"] = ConvWeight(sd[a + "out_proj.weight"], sd[a + "out_proj.bias"], prec, dev)
-            P[f"{i}.fc1"] = ConvWeight(sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"], prec, dev)
-            P[f"{i}.fc2"] = ConvWeight(sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"], prec, dev)
+        prepare_layers(P, sd, "text_model.encoder.layers.", self.config["num_hidden_layers"], prec, dev)
         P["final_layer_norm"] = self._norm_pair(sd, "text_model.final_layer_norm")
         if self._projection:
             P["text_projection"] = ConvWeight(sd["text_projection.weight"], None, prec, dev)
@@ -163,19 +196,7 @@ class CLIPTextModel(HipModel):
 
     # -- forward ------------------------------------------------------------------------------------
     def _layer(self, i: int, x: torch.Tensor) -> torch.Tensor:
-        P, prec = self.P, self.prec
-        b, s, c = x.shape
-        heads = self.config["num_attention_heads"]
-        d = c // heads
-        h = ops.layernorm(x, P[f"{i}.ln1"], self.eps, prec.act)
-        qk = ops.linear(h, P[f"{i}.to_qk"])
-        vt = ops.linear_t(h, P[f"{i}.to_v"], (s + 7) // 8 * 8)            # 77 keys -> ld 80, pad columns zero
-        o = ops.attention(qk[..., :c], qk[..., c:], vt, heads, s, d ** -0.5, prec, c=c, causal=True)
-        x = ops.linear(o, P[f"{i}.out"], res0=x)
-        h = ops.layernorm(x, P[f"{i}.ln2"], self.eps, prec.act)
-        m = ops.linear(h, P[f"{i}.fc1"])
-        hip.act(m, _ACTS[self.config["hidden_act"]], out=m)
-        return ops.linear(m, P[f"{i}.fc2"], res0=x)
+        return encoder_layer(self.P, i, x, self.config, self.prec, self.eps, causal=True)
 
     def _pool_index(self, ids: torch.Tensor) -> torch.Tensor:
         """modeling_clip.py: eos_token_id == 2 is the legacy rule (the SD1.5 / SDXL checkpoints): the highest id of the row is the

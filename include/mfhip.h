@@ -600,6 +600,32 @@ int mf_clip_vision_embed(const void* patches, const void* class_embedding, const
 int mf_clip_score(const float* image_feats, const float* text_feats, int32_t batch, int32_t dim, float* out, float* norms_out,
                   void* stream);
 
+/* ---- LPIPS (csrc/lpips.hip): the reference's third image-quality number (metrics/metrics.py:51-67, :150-151, :202-204: torchmetrics'
+ * learned_perceptual_image_patch_similarity(net_type="squeeze", normalize=False)).  The convolutions of squeezenet1_1.features are
+ * mf_gemm_conv calls; these entries are the arithmetic around them.  fp32, bf16 or fp16 activations, NHWC, 16-byte accesses.
+ * mf_lpips_prepare: uint8 NHWC pred / gt [batch][h][w][3] (mask [batch][h][w], region as in mf_image_metrics: the blackening happens
+ *   before anything else) -> out [2 * batch][h][w][8], the pred images first: per channel x / 127.5 - 1 (unit_range 0) or x / 255
+ *   (unit_range 1), then (v - shift[c]) / scale[c] of the LPIPS scaling layer, every step one fp32 rounding, then one rounding to
+ *   out_dtype; channels 3 .. 7 are written as zero (the first conv is an 8-channel-segment implicit GEMM with K = 72).
+ * mf_relu: x = max(x, 0) in place over rows x channels elements, row r at x + r * ld (channels % 8 == 0, ld % 8 == 0).
+ * mf_maxpool3s2_ceil: MaxPool2d(3, 2, ceil_mode=True) of x [batch][h][w][channels] into out [batch][ho][wo][channels], ho =
+ *   ceil((h - 3) / 2) + 1; a window that hangs over the edge takes the max of what exists; h, w >= 3, channels % 8 == 0.
+ * mf_lpips_layer: feat [2 * batch][pixels][channels] (image b against image batch + b), weight fp32 [channels]: per pair the sum over
+ *   the pixels of sum_c weight[c] (a_c / n(a) - b_c / n(b))^2, n(x) = sqrt(1e-8 + sum_c x_c^2), in fp32 per pixel; a fixed number of
+ *   per-block partial sums per pair go to slot `layer` (0 .. 6) of ws.  channels 8 .. 512, a multiple of 8.  Equal halves give 0 exactly.
+ * mf_lpips_finish: the partials of all seven slots, each summed in a fixed order -> rows_out fp32 [batch][7] (sums: the caller divides
+ *   by the pixel counts).  No floating-point atomics anywhere: the same inputs give the same bits.
+ * ws: mf_lpips_ws_bytes(batch) bytes, 8-byte aligned (-1 for a batch it refuses); every slot must have been written by a
+ * mf_lpips_layer call before mf_lpips_finish reads it.  One launch each. */
+int64_t mf_lpips_ws_bytes(int32_t batch);
+int mf_lpips_prepare(const void* pred_u8_nhwc, const void* gt_u8_nhwc, const void* mask_u8, int32_t region, int32_t batch, int32_t h,
+                     int32_t w, int32_t channels, int32_t unit_range, void* out, int32_t out_dtype, void* stream);
+int mf_relu(void* x, int32_t dtype, int64_t rows, int32_t channels, int64_t ld, void* stream);
+int mf_maxpool3s2_ceil(const void* x, void* out, int32_t dtype, int32_t batch, int32_t h, int32_t w, int32_t channels, void* stream);
+int mf_lpips_layer(const void* feat, int32_t dtype, const float* weight, int32_t batch, int64_t pixels, int32_t channels, int32_t layer,
+                   void* ws, void* stream);
+int mf_lpips_finish(const void* ws, int32_t batch, float* rows_out, void* stream);
+
 /* ============================================================================================
  * Training: the backward pass and the optimizer of examples/brushnet/train_brushnet_mirror.py:1459-1466
  * (accelerator.backward -> ATen autograd in the reference; clip_grad_norm_ :1463; torch.optim.AdamW :1188-1200).

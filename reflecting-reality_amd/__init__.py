@@ -11,10 +11,11 @@ Sub-modules:
   training   MirrorFusionModel, training_loss, train_step (backward + clip + AdamW), checkpoint save / load hooks
   distributed  batch sharding for inference, bucketed gradient all-reduce (RCCL) for training
   inference  run_sharded: the examples/brushnet/test_brushnet.py harness (sample list split over ranks, N seeds each); validate
-  metrics    compute_metrics, MetricsCalculator, score_regions, clip_score: PSNR / SSIM (frame, mask, mirror) and CLIP similarity on the device
+  metrics    compute_metrics, MetricsCalculator, score_regions, clip_score, lpips: PSNR / SSIM / LPIPS (frame, mask, mirror) and CLIP similarity on the device
   pipeline   StableDiffusionBrushNetPipeline, StableDiffusionXLBrushNetPipeline
   text_encoder  CLIPTextModel, CLIPTextModelWithProjection (the prompt encoders of both pipelines)
   image_encoder  CLIPVisionModel, CLIPVisionModelWithProjection, CLIPModel (the scorer of CLIP_Similarity)
+  lpips      LPIPS (net_type="squeeze": squeezenet1_1.features and the seven layer distances)
 """
 __version__ = "0.1.0"
 
@@ -26,6 +27,7 @@ _LAZY = {
     "MfhipAttnProcessor": "attn_processor", "MfhipIPAttnProcessor": "attn_processor", "StableDiffusionBrushNetPipeline": "pipeline", "StableDiffusionXLBrushNetPipeline": "pipeline", "StableDiffusionPipelineOutput": "pipeline",
     "VaeImageProcessor": "pipeline", "Precision": "ops", "CLIPTextModel": "text_encoder", "CLIPTextModelWithProjection": "text_encoder",
     "CLIPVisionModel": "image_encoder", "CLIPVisionModelWithProjection": "image_encoder", "CLIPModel": "image_encoder",
+    "LPIPS": "lpips",
 }
 
 

@@ -187,6 +187,9 @@ SIGNATURES = {
     # CLIP image side and score (csrc/clip_vision.hip)
     "mf_clip_preprocess_ws_bytes": "l:iiiii", "mf_clip_preprocess": "i:piiiiiiipipiffffffpiippp", "mf_clip_vision_embed": "i:pppipiiiip",
     "mf_clip_score": "i:ppiippp",
+    # LPIPS (csrc/lpips.hip)
+    "mf_lpips_ws_bytes": "l:i", "mf_lpips_prepare": "i:pppiiiiiipip", "mf_relu": "i:pililp", "mf_maxpool3s2_ceil": "i:ppiiiiip",
+    "mf_lpips_layer": "i:pipiliipp", "mf_lpips_finish": "i:pipp",
     # training (csrc/train.hip)
     "mf_sizeof_wgrad_desc": "i:", "mf_conv_wgrad_ws_floats": "l:W", "mf_conv_wgrad": "i:Wp", "mf_split_pack": "i:plpliip",
     "mf_transpose": "i:ppiiillllp", "mf_transpose_bf16": "i:ppiiillllp", "mf_colsum_ws_floats": "l:ili", "mf_colsum": "i:plpliliipp",
@@ -1649,6 +1652,76 @@ def clip_score(image_feats: torch.Tensor, text_feats: torch.Tensor):
     norms = torch.empty(i.shape[0], 2, dtype=torch.float32, device=i.device)
     _launch("mf_clip_score", i, t, i.shape[0], i.shape[1], out, norms)
     return out, norms
+
+
+LPIPS_LAYERS = 7
+
+
+def lpips_prepare(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor], region, unit_range: bool,
+                  out_dtype: torch.dtype) -> torch.Tensor:
+    """mf_lpips_prepare on uint8 NHWC device tensors [B, H, W, 3] (mask: uint8 [B, H, W]): the normalised, scaled input of the LPIPS
+    network as [2 B, H, W, 8] in out_dtype (pred images first, channels 3 .. 7 zero)."""
+    _req_cuda(pred, gt, mask)
+    region = REGIONS[region] if region in REGIONS else int(region)
+    if pred.dtype != torch.uint8 or gt.dtype != torch.uint8 or pred.dim() != 4 or pred.shape != gt.shape:
+        raise MfhipError("lpips_prepare: two uint8 [batch, height, width, 3] tensors of one shape")
+    b, h, w, c = pred.shape
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (b, h, w)):
+        raise MfhipError(f"lpips_prepare: the mask must be uint8 [{b}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
+    pred, gt = pred.contiguous(), gt.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    out = torch.empty(2 * b, h, w, 8, dtype=out_dtype, device=pred.device)
+    _launch("mf_lpips_prepare", pred, gt, mask, region, b, h, w, c, int(bool(unit_range)), out, dt_code(out_dtype))
+    return out
+
+
+def relu_(x: torch.Tensor) -> torch.Tensor:
+    """mf_relu: max(x, 0) in place.  x is [..., channels] with unit channel stride and ONE stride between its rows (a contiguous tensor
+    or a channel slice of one): what a GEMM wrote through out / ldc."""
+    _req_cuda(x)
+    c = x.shape[-1]
+    rows = x.numel() // max(c, 1)
+    ld = x.stride(-2) if x.dim() >= 2 else c
+    flat = x.dim() < 2 or all(x.stride(i) == x.stride(i + 1) * x.shape[i + 1] for i in range(x.dim() - 2))
+    if x.stride(-1) != 1 or not flat:
+        raise MfhipError(f"relu_: rows of unit-stride channels, one stride apart (got shape {tuple(x.shape)}, strides {x.stride()})")
+    _launch("mf_relu", x, dt_code(x.dtype), rows, c, ld)
+    return x
+
+
+def maxpool3s2_ceil(x: torch.Tensor) -> torch.Tensor:
+    """mf_maxpool3s2_ceil: MaxPool2d(3, 2, ceil_mode=True) over a contiguous NHWC tensor."""
+    _req_cuda(x)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise MfhipError("maxpool3s2_ceil: a contiguous [batch, height, width, channels] tensor")
+    b, h, w, c = x.shape
+    out = torch.empty(b, max(-(-(h - 3) // 2) + 1, 1), max(-(-(w - 3) // 2) + 1, 1), c, dtype=x.dtype, device=x.device)
+    _launch("mf_maxpool3s2_ceil", x, out, dt_code(x.dtype), b, h, w, c)
+    return out
+
+
+def lpips_ws(batch: int, device) -> torch.Tensor:
+    nbytes = load().mf_lpips_ws_bytes(batch)
+    if nbytes < 0:
+        raise MfhipError(f"lpips: {load().mf_last_error().decode()}")
+    return scratch("lpips", (nbytes + 3) // 4 + 2, device)
+
+
+def lpips_layer(feat: torch.Tensor, weight: torch.Tensor, layer: int, ws: torch.Tensor) -> None:
+    """mf_lpips_layer: feat [2 B, h, w, C] (image b against image B + b), weight fp32 [C]; the partial sums go to slot `layer` of ws."""
+    _req_cuda(feat, weight, ws)
+    if feat.dim() != 4 or feat.shape[0] % 2 or not feat.is_contiguous() or weight.dtype != torch.float32 or weight.numel() != feat.shape[-1]:
+        raise MfhipError(f"lpips_layer: a contiguous [2 B, h, w, C] feature and C fp32 weights (got {tuple(feat.shape)}, {tuple(weight.shape)})")
+    b2, h, w, c = feat.shape
+    _launch("mf_lpips_layer", feat, dt_code(feat.dtype), weight.contiguous(), b2 // 2, h * w, c, layer, ws)
+
+
+def lpips_finish(ws: torch.Tensor, batch: int) -> torch.Tensor:
+    """mf_lpips_finish: the fp32 [B, 7] DEVICE row of per-layer sums.  Nothing synchronises with the host."""
+    _req_cuda(ws)
+    out = torch.empty(batch, LPIPS_LAYERS, dtype=torch.float32, device=ws.device)
+    _launch("mf_lpips_finish", ws, batch, out)
+    return out
 
 
 def _sel_ws(device) -> torch.Tensor:

@@ -58,13 +58,14 @@ def run_sharded(pipe, samples: Sequence[Dict], *, seed: int = 0, num_images_per_
 def validate(pipe, samples: Sequence[Dict], *, num_images_per_validation: int = 4, seed: int = 0, num_inference_steps: int = 50,
              guidance_scale: float = 7.5, brushnet_conditioning_scale: float = 1.0, gt_key: str = "gt_image", mask_key: str = "gt_mask",
              rank: Optional[int] = None, world: Optional[int] = None, generator_device: Optional[str] = None,
-             on_result: Optional[Callable[[int, List], None]] = None) -> Dict:
-    """train_brushnet_mirror.py:200-250 without LPIPS.  A sample is the pipeline's kwargs plus `gt_key`: its ground-truth image (PIL,
+             on_result: Optional[Callable[[int, List], None]] = None, lpips_model=None) -> Dict:
+    """train_brushnet_mirror.py:200-250; LPIPS when the caller brings the network (`lpips_model`: an lpips.LPIPS).  A sample is the pipeline's kwargs plus `gt_key`: its ground-truth image (PIL,
     uint8 HWC array or device tensor) and optionally `mask_key`: its uint8 mirror mask — then every image is also scored on the "mask" and
-    "mirror" regions (keys psnr_mask, ssim_mask, psnr_mirror, ssim_mirror).  The images are produced as [0, 1] device tensors and scored
+    "mirror" regions (keys psnr_mask, ssim_mask, psnr_mirror, ssim_mirror; with `lpips_model` also lpips, lpips_mask, lpips_mirror).  The images are produced as [0, 1] device tensors and scored
     as they appear: the launches are queued behind the decode, the rows are read once per sample.  Returns
       "per_image"  {sample index: [{"psnr", "ssim", ...} per image]}
       "psnr", "ssim" (and the region keys)  the per-sample best (max) in sample order: what the reference appends to all_metrics (:246-247)
+      "lpips" (and its region keys)         the per-sample best, which for LPIPS is the MINIMUM (:250)
       "mean_psnr", "mean_ssim", ...         their means over this rank's samples: what it logs (:258-262)
       "images"     run_sharded's {sample index: [images]}"""
     from . import hip, metrics as M
@@ -73,6 +74,7 @@ def validate(pipe, samples: Sequence[Dict], *, num_images_per_validation: int = 
     pending: Dict[int, List] = {}
     gts: Dict[int, tuple] = {}
     per_image: Dict[int, List[Dict[str, float]]] = {}
+    lp_pending: Dict[int, List] = {}
 
     def on_image(i: int, k: int, image) -> None:
         if i not in gts:
@@ -85,11 +87,17 @@ def validate(pipe, samples: Sequence[Dict], *, num_images_per_validation: int = 
             pending.setdefault(i, []).append(hip.image_metrics(pred, gt))
         else:
             pending.setdefault(i, []).append(M.score_regions(pred, gt, mask, rows_only=True))
+        if lpips_model is not None:                                        # queued behind the decode like the rows above; read per sample
+            regions = (None,) if mask is None else (None, "mask", "mirror")
+            lp_pending.setdefault(i, []).append([M.lpips_rows(pred, gt, lpips_model, mask, r) for r in regions])
 
     def finish_sample(i: int, images: List) -> None:
         gt = gts.pop(i)[0]
         n = gt.shape[1] * gt.shape[2] * gt.shape[3]
         per_image[i] = [M.rows_to_regions(r, n) for r in pending.pop(i)]
+        for scores, rows in zip(per_image[i], lp_pending.pop(i, [])):
+            for key, r in zip(M.REGION_KEYS, rows):
+                scores["lpips" + key] = float(M.lpips_finish(r.cpu().numpy(), gt.shape[1], gt.shape[2], lpips_model.stage_shapes)[0])
         if on_result is not None:
             on_result(i, images)
 
@@ -100,7 +108,8 @@ def validate(pipe, samples: Sequence[Dict], *, num_images_per_validation: int = 
     out: Dict = {"per_image": per_image, "images": images}
     keys = sorted({k for rows in per_image.values() for r in rows for k in r})
     for key in keys:
-        best = [max(r[key] for r in per_image[i]) for i in sorted(per_image) if all(key in r for r in per_image[i])]
+        pick = min if key.startswith("lpips") else max                     # train_brushnet_mirror.py:246-250
+        best = [pick(r[key] for r in per_image[i]) for i in sorted(per_image) if all(key in r for r in per_image[i])]
         out[key] = best
         out["mean_" + key] = float(sum(best) / len(best)) if best else float("nan")
     return out

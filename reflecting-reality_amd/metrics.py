@@ -13,9 +13,15 @@ caller brings the network: clip_score() runs the uint8 image through mf_clip_pre
 the caption through its text tower, and mf_clip_score; the mean over the pairs and the clamp at 0 are finished here in float64.  The
 weights are something the reference downloads, so `MetricsCalculator(..., clip_model=, clip_tokenizer=)` takes them from the caller.
 
-Not built (the constructor of MetricsCalculator refuses them by name): LPIPS, CLIP similarity without a model, aesthetic score,
+`LPIPS` (metrics.py:150-151, :202-204: torchmetrics' learned_perceptual_image_patch_similarity with net_type="squeeze") is scored on the
+device as well once the caller brings the weights (lpips.LPIPS: torchvision's squeezenet1_1 and the `lpips` package's linear layers):
+lpips_rows() runs the uint8 pair through mf_lpips_prepare, the network and mf_lpips_layer / mf_lpips_finish and leaves a [B, 7] row of
+per-layer sums on the device; the division by the pixel counts, the sum over the layers and the mean over the pairs are finished here
+in float64.  `compute_metrics(..., lpips_model=m)` and `MetricsCalculator(..., lpips_model=m)` take the model.
+
+Not built (the constructor of MetricsCalculator refuses them by name): LPIPS and CLIP similarity without a model, aesthetic score,
 ImageReward, HPS and the SAM-based `obj` / IoU scores — their networks and weights are not part of this package.
-`compute_metrics(..., lpips_fn=f)` calls a caller-supplied LPIPS with the normalised tensors the reference builds (metrics.py:60-64)."""
+`compute_metrics(..., lpips_fn=f)` still calls a caller-supplied LPIPS with the normalised tensors the reference builds (metrics.py:60-64)."""
 from __future__ import annotations
 
 from typing import Callable, Dict, List, Optional, Sequence
@@ -117,9 +123,11 @@ def _normalised(u8: torch.Tensor, norm_range) -> torch.Tensor:
     raise ValueError("Unsupported normalization range. Use [-1, 1] or [0, 1].")
 
 
-def compute_metrics(pred, gt, norm_range=[-1, 1], lpips_fn: Optional[Callable] = None, device=None) -> Dict[str, float]:
-    """metrics.py:51-67 for one image pair: {"ssim", "psnr"} as Python floats, and "lpips" = lpips_fn(pred_normalised, gt_normalised)
-    only when the caller brings an LPIPS (none ships with this package)."""
+def compute_metrics(pred, gt, norm_range=[-1, 1], lpips_fn: Optional[Callable] = None, device=None, lpips_model=None) -> Dict[str, float]:
+    """metrics.py:51-67 for one image pair: {"ssim", "psnr"} as Python floats, and "lpips" when the caller brings the network: an
+    lpips.LPIPS as `lpips_model` (scored on the device, lpips()), or a callable `lpips_fn(pred_normalised, gt_normalised)` of their own."""
+    if lpips_fn is not None and lpips_model is not None:
+        raise ValueError("compute_metrics: give lpips_model or lpips_fn, not both")
     p = to_u8_nhwc(pred, device)
     g = to_u8_nhwc(gt, p.device)
     _check_pair(p, g)
@@ -127,6 +135,8 @@ def compute_metrics(pred, gt, norm_range=[-1, 1], lpips_fn: Optional[Callable] =
         raise ValueError(f"compute_metrics scores one image per call, got a batch of {p.shape[0]} (metrics.score takes a batch)")
     rows = hip.image_metrics(p, g)
     out = {}
+    if lpips_model is not None:
+        out["lpips"] = lpips(p, g, lpips_model, norm_range=norm_range)
     if lpips_fn is not None:
         v = lpips_fn(_normalised(p, norm_range), _normalised(g, norm_range))
         out["lpips"] = float(v)
@@ -214,9 +224,46 @@ def _load_clip(clip_model, clip_tokenizer, device):
     return clip_model, clip_tokenizer
 
 
+# ---- LPIPS ---------------------------------------------------------------------------------------------------------------------------------
+def lpips_rows(pred, gt, model, mask=None, region=None, norm_range=[-1, 1], device=None) -> torch.Tensor:
+    """The fp32 [B, 7] DEVICE row of an lpips.LPIPS: per pair and tapped layer the sum over the pixels of the weighted squared difference
+    of the channel-normalised features; nothing is read back.  Images as to_u8_nhwc takes them (RGB), region None / "mask" / "mirror"
+    with a uint8 mask: the pixels are blackened in both images before normalising, as HDF5Dataset.get_masked_image does."""
+    dev = model.device if device is None else device
+    p = to_u8_nhwc(pred, dev)
+    g = to_u8_nhwc(gt, p.device)
+    _check_pair(p, g)
+    if p.shape[-1] != 3:
+        raise ValueError(f"LPIPS scores RGB images, got {p.shape[-1]} channels")
+    model.stage_shapes(p.shape[1], p.shape[2])                           # (a small side is refused before any upload of the mask)
+    if region and mask is None:
+        raise ValueError(f"region {region!r} needs a mask")
+    m = _mask_u8(mask, p) if region else None
+    return model(p, g, m, region, norm_range)
+
+
+def lpips_finish(rows, h: int, w: int, stage_shapes=None):
+    """The [B, 7] row -> the B LPIPS values in float64: every layer's sum divided by its pixel count (the spatial mean), then the sum over
+    the layers."""
+    if stage_shapes is None:
+        from .lpips import stage_shapes
+    counts = np.array([a * b for a, b in stage_shapes(h, w)], dtype=np.float64)
+    return (np.asarray(rows, dtype=np.float64).reshape(-1, counts.size) / counts).sum(axis=1)
+
+
+def lpips(pred, gt, model, mask=None, region=None, norm_range=[-1, 1], device=None) -> float:
+    """torchmetrics.functional.image.learned_perceptual_image_patch_similarity(pred, gt, net_type="squeeze", reduction="mean",
+    normalize=False) on the normalised tensors of get_normalised_tensor (metrics.py:24-48), from the uint8 images."""
+    p = to_u8_nhwc(pred, model.device if device is None else device)
+    rows = lpips_rows(p, gt, model, mask, region, norm_range, device)
+    per_pair = lpips_finish(rows.cpu().numpy(), p.shape[1], p.shape[2], model.stage_shapes)
+    return float(per_pair.sum() / np.float64(per_pair.size))
+
+
 # what compute_metric dispatches on besides PSNR / SSIM, and where the reference does it (metrics/metrics.py).  CLIP_Similarity leaves the
-# list when the caller supplies the model.  Aesthetic_Score stays: the reference feeds floats 0 .. 255 through open_clip's transforms
-# (metrics.py:86-102), and neither open_clip nor torchvision exists here to pin that path against, so it is refused, not guessed.
+# list when the caller supplies the model, and so does LPIPS (lpips_model=).  Aesthetic_Score stays: the reference feeds floats 0 .. 255
+# through open_clip's transforms (metrics.py:86-102), and neither open_clip nor torchvision exists here to pin that path against, so it is
+# refused, not guessed.
 _UNBUILT = (("LPIPS", "metrics.py:150-151 (calculate_lpips: torchmetrics' LPIPS network)"),
             ("CLIP_Similarity", "metrics.py:156-157 (calculate_clip_similarity: a CLIP model)"),
             ("Aesthetic_Score", "metrics.py:86-102,158-159 (the LAION aesthetic head on open_clip ViT-L-14)"),
@@ -229,25 +276,31 @@ _UNBUILT = (("LPIPS", "metrics.py:150-151 (calculate_lpips: torchmetrics' LPIPS 
 class MetricsCalculator:
     """metrics.py:70-165 for the metrics this package computes: names that hold "PSNR" or "SSIM", on the frame or — with "mask" /
     "mirror" in the name — on a region; and, with `clip_model` (an image_encoder.CLIPModel or a checkpoint directory) and its
-    `clip_tokenizer`, names that hold "CLIP_Similarity".  Every other name of the reference is refused at construction."""
+    `clip_tokenizer`, names that hold "CLIP_Similarity"; with `lpips_model` (an lpips.LPIPS), names that hold "LPIPS", on the frame or
+    a region.  Every other name of the reference is refused at construction."""
 
     def __init__(self, metrics_to_compute: Sequence[str], device=None, data_dir=None, cache_dir=None, ckpt_path="data/ckpt",
-                 norm_range=[-1, 1], clip_model=None, clip_tokenizer=None) -> None:
+                 norm_range=[-1, 1], clip_model=None, clip_tokenizer=None, lpips_model=None) -> None:
         self.device = device                                                # (resolved at the first upload)
         self.metrics_to_compute = list(metrics_to_compute)
         self.norm_range, self.data_dir, self.cache_dir = norm_range, data_dir, cache_dir
         self.clip_model = self.clip_tokenizer = None
+        self.lpips_model = lpips_model
         if clip_model is not None:
             self.clip_model, self.clip_tokenizer = _load_clip(clip_model, clip_tokenizer, device)
         for name in self.metrics_to_compute:
+            with_lpips = False
             for key, where in _UNBUILT:
+                if key == "LPIPS" and key in name and self.lpips_model is not None:
+                    with_lpips = True                                       # (the other names stay refused: the loop goes on)
+                    continue
                 if key == "CLIP_Similarity" and key in name and self.clip_model is not None:
                     break
                 if key in name:
                     raise NotImplementedError(f"metric {name!r}: {key} is not built here (the reference: {where}); its network and "
                                               "weights are not part of this package")
             else:
-                if "PSNR" in name or "SSIM" in name:
+                if with_lpips or "PSNR" in name or "SSIM" in name:
                     continue
                 raise NotImplementedError(f"metric {name!r}: only PSNR and SSIM (frame, *mask*, *mirror*) are built; the reference "
                                           "dispatches at metrics.py:150-165")
@@ -258,7 +311,8 @@ class MetricsCalculator:
 
     def compute_metric(self, metric_name: str, gen_image, gt_data, caption=None) -> float:
         if metric_name not in self.metrics_to_compute:                      # the same refusals for a name the constructor never saw
-            MetricsCalculator([metric_name], self.device, clip_model=self.clip_model, clip_tokenizer=self.clip_tokenizer)
+            MetricsCalculator([metric_name], self.device, clip_model=self.clip_model, clip_tokenizer=self.clip_tokenizer,
+                              lpips_model=self.lpips_model)
         if "CLIP_Similarity" in metric_name:
             if not caption:
                 raise ValueError(f"metric {metric_name!r} scores the image against its caption: compute_metric(..., caption=) is required")
@@ -267,6 +321,8 @@ class MetricsCalculator:
         # "mask": the reference takes the dataset's masked_image as the target (:140) and masks the generated image (:141); the region step
         # on that target is the identity (its mirror pixels are black already).  "mirror": both from the full image (:144-145).
         gt_image = gt_data["masked_image"] if region == "mask" else gt_data["image"]
+        if "LPIPS" in metric_name:
+            return lpips(gen_image, gt_image, self.lpips_model, gt_data["mask"] if region else None, region, self.norm_range, self.device)
         r = score(gen_image, gt_image, gt_data["mask"] if region else None, region, device=self.device)
         if len(r) != 1:
             raise ValueError("compute_metric scores one image per call")
@@ -279,3 +335,12 @@ class MetricsCalculator:
     @staticmethod
     def calculate_ssim(pred_img, gt_img) -> float:
         return score(pred_img, gt_img)[0]["ssim"]
+
+    def calculate_lpips(self, pred_img, gt_img, net_type="squeeze") -> float:
+        """metrics.py:202-204 on the uint8 images (the reference's is a staticmethod that downloads the network; this one needs the model
+        the calculator was built with)."""
+        if self.lpips_model is None:
+            raise NotImplementedError("calculate_lpips needs MetricsCalculator(..., lpips_model=): an lpips.LPIPS with its weights")
+        if net_type != "squeeze":
+            raise NotImplementedError(f"net_type {net_type!r}: only 'squeeze' is built")
+        return lpips(pred_img, gt_img, self.lpips_model, norm_range=self.norm_range, device=self.device)

@@ -242,14 +242,16 @@ def conv2d(x: torch.Tensor, cw: ConvWeight, *, stride: int = 1,
            res0: Optional[torch.Tensor] = None, res1: Optional[torch.Tensor] = None,
            alpha: float = 1.0, act: int = hip.ACT_NONE, out_dtype: Optional[torch.dtype] = None,
            splitk: int = 0, tile: int = 0, sk_fused: bool = False, gn_part: Union[bool, int] = False,
-           defer_reduce: Union[bool, int] = False) -> torch.Tensor:
+           defer_reduce: Union[bool, int] = False, out: Optional[torch.Tensor] = None, ldc: Optional[int] = None) -> torch.Tensor:
     """Convolution over NHWC x (optionally cat([x, x1], C) and/or nearest-2x upsampled), fused epilogue
     alpha*(conv + bias + temb[b]) + res0 + res1.  padding = int or (top, left, bottom, right).
     defer_reduce (the consumer's group count): the caller passes the result to groupnorm() with that many groups and to nothing else (a
     resnet's conv1 -> norm2, resnet.py:381-393): on the levels that run split-K (images up to 16 x 16) the launch that sums the K slices is
     then that GroupNorm (mf_gemm_desc.defer_reduce).
     gn_part: the output feeds a GroupNorm — the launch also leaves per-channel partial sums of its output (mf_gemm_desc.gn_part),
-    attached to the returned tensor, and groupnorm() then skips its statistics pass (inference, images above 16 x 16)."""
+    attached to the returned tensor, and groupnorm() then skips its statistics pass (inference, images above 16 x 16).
+    out / ldc: write into a caller's [B, Ho, Wo, N] view whose pixels are ldc elements apart (a channel range of a wider NHWC buffer:
+    concatenation without a copy; inference only)."""
     b, h, w, c0 = x.shape
     c1 = x1.shape[-1] if x1 is not None else 0
     if c0 + c1 != cw.cin_pad:
@@ -260,7 +262,16 @@ def conv2d(x: torch.Tensor, cw: ConvWeight, *, stride: int = 1,
     hu, wu = (h * 2, w * 2) if upsample else (h, w)
     ho = (hu + pt + pb - cw.kh) // stride + 1
     wo = (wu + pl + pr - cw.kw) // stride + 1
-    out = torch.empty(b, ho, wo, cw.n, dtype=out_dtype or cw.prec.act, device=x.device)
+    if out is None:
+        out, ldc = torch.empty(b, ho, wo, cw.n, dtype=out_dtype or cw.prec.act, device=x.device), None
+    else:
+        ldc = cw.n if ldc is None else int(ldc)
+        if TAPE is not None or defer_reduce or gn_part:
+            raise hip.MfhipError("conv2d: out= is inference only, without gn_part / defer_reduce")
+        if (tuple(out.shape) != (b, ho, wo, cw.n) or out.dtype != (out_dtype or cw.prec.act) or ldc < cw.n
+                or out.stride() != (ho * wo * ldc, wo * ldc, ldc, 1)):
+            raise hip.MfhipError(f"conv2d: out must be a [{b}, {ho}, {wo}, {cw.n}] {out_dtype or cw.prec.act} view with pixels {ldc} elements apart "
+                                 f"(got {tuple(out.shape)} {out.dtype}, strides {out.stride()})")
     wt, wsp, wld = cw.operand()
     code, xa, x1a = cw.prec.code, x, x1
     fast = cw.fast16(c0, c1)
@@ -271,7 +282,7 @@ def conv2d(x: torch.Tensor, cw: ConvWeight, *, stride: int = 1,
         raise hip.MfhipError("conv2d: a bf16 activation in the bf16x1 mode needs channel counts that are multiples of 8")
     hip.gemm_conv(xa, wt, out, dtype=code, w_split=wsp, ldw=wld, c0=c0, lda0=c0, a1=x1a, c1=c1, lda1=c1,
                   batch=b, h_in=h, w_in=w, h_out=ho, w_out=wo, kh=cw.kh, kw=cw.kw, stride=stride,
-                  pad_t=pt, pad_l=pl, upsample=upsample, n=cw.n, bias=cw.bias,
+                  pad_t=pt, pad_l=pl, upsample=upsample, n=cw.n, ldc=ldc, bias=cw.bias,
                   temb=temb, ld_temb=(temb.stride(0) if temb is not None else 0),
                   res0=res0, res1=res1, res1_rows=_shared_rows(res1, b * ho * wo, cw.n), alpha=alpha, act=act, splitk=splitk,
                   tile=tile, sk_fused=sk_fused, gn_part=(gn_part if _want_gn_part(gn_part, ho * wo, cw.n) else False),

@@ -177,7 +177,13 @@ typedef struct mf_gemm_desc {
      * epilogue (R = the tile's rows; fixed summation order, bit-reproducible) when the launch has no split-K reduce and the tile
      * is an implicit-GEMM tile with h_out * w_out a multiple of its rows; otherwise by one extra column-sum launch over the
      * stored output (R = 128, 64 or 32) — same contract.  Needs n % 8 == 0, nz == 1, h_out * w_out % 32 == 0, no GEGLU, no
-     * vt_out, and gn_part_floats >= 2 * n * (M / 32) (enough for the smallest R). */
+     * vt_out, and gn_part_floats >= 2 * n * (M / 32) (enough for the smallest R).
+     * Conditioning of the format: the sums are fp32 and UNSHIFTED, so the variance a consumer forms from them, sum x^2 - (sum x)^2 / n,
+     * loses digits as |mean| / std of a group grows, whatever precision the consumer combines them in.  Measured with an fp32 output at
+     * 640 channels x 1024 rows in blocks of 128 rows (tests/test_norm_conditioning_gpu.py): from the per-channel sums the normalised
+     * values stay inside the suite's fp32 bound (1e-4 + 2e-5 |y|, or 4 x torch's fp32 error) up to |mean| / std = 30 and leave it at
+     * 100 (7e-4, 19 x torch's fp32 error); from the per-group sums below they stay inside up to 10 and leave it at 30 (4e-4).  mf_groupnorm's
+     * own statistics pass (part0 == NULL) accumulates x - pivot and has no such limit. */
     float* gn_part; int64_t gn_part_floats; int32_t* gn_part_rows;
     /* gn_groups > 0 (with gn_part): the consumer is a GroupNorm over exactly this tensor with gn_groups groups (the common case: every
      * norm of the path but the decoder's concatenated ones).  When the epilogue produces the sums and the tile's columns hold whole

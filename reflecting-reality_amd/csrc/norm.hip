@@ -21,6 +21,11 @@ struct GnArgs {
     float* ws;   // [batch][G][nchunks][2] = (mean, M2) of each chunk
     float* ws_ab;   // [batch][2][C] per-channel scale / shift (separate-finalize path)
     int fuse_finalize;
+    // fp32 output: the apply pass forms y = ((x - mean_hi) - mean_lo) * a + beta with the group's mean as TWO floats, not x * a + shift:
+    // the fp32 shift beta - mean * a rounds a term of size |mean| * rstd * |gamma| (1000 |gamma| for mean 100 / std 0.1), which alone
+    // exceeds the 1e-4 the fp32-class modes promise.  centered: a separate finalize launch hands (mean_hi, mean_lo, rstd) of every group
+    // to the apply pass in the image's own (by then consumed, or unused) chunk-statistics slots of ws, 3 floats per group.
+    int centered;
     float* stats_out;   // nullable [batch][G][2]: (mean, rstd) of every group, kept for mf_groupnorm_bwd (training)
     // statistics handed over by the producers (mf_gemm_desc.gn_part): per-channel (sum, sum of squares) of every block of rows
     const float2* part0; const float2* part1; int pr0, pr1;
@@ -171,6 +176,25 @@ __device__ __forceinline__ void gn_loadf(const float* p, float* o) {
 //
 // Pass 1, grid (nchunks, batch): per-(thread-row, channel) fp32 sums -> LDS -> one (mean, M2) per group of the
 // chunk, in double.  No atomics: bitwise reproducible.
+//
+// The sums are those of x - pivot, one pivot per (image, group): the stored value at the image's first row, first channel of the
+// group (gn_pivot).  Sums of the raw values lose the variance once the mean dwarfs the spread (mean 100, std 0.1: sum x^2 is 1e4 n,
+// its fp32 rounding as large as the M2 = 0.01 n it is subtracted down to; tests/test_norm_conditioning_gpu.py).  A pivot inside the
+// data leaves |x - pivot| of the order of the spread, all partial sums stay additive, and the double combine restores
+// mean = pivot + S / n, M2 = SS - S^2 / n.  The pivot depends on the image's own data only.
+template <int IN_DT>
+__device__ __forceinline__ float gn_pivot(const GnArgs& p, int b, int g) {
+    constexpr int esz = IN_DT == MF_F32 ? 4 : 2;
+    const int c = g * p.cpg;
+    const char* q = c < p.C0 ? p.x0 + ((int64_t)b * p.HW * p.C0 + c) * esz : p.x1 + ((int64_t)b * p.HW * p.C1 + (c - p.C0)) * esz;
+    if constexpr (IN_DT == MF_F32) {
+        return *GN_GLOBAL(const float, q);
+    } else {
+        float lo, hi;
+        unpack_h2<IN_DT == MF_F16>((uint32_t)*GN_GLOBAL(const uint16_t, q), lo, hi);
+        return lo;
+    }
+}
 template <int IN_DT, int VW, int U>
 __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -187,9 +211,16 @@ __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
             const char* base; int64_t ld; int cc;
             if (c < p.C0) { base = p.x0; ld = p.C0; cc = c; }
             else { base = p.x1; ld = p.C1; cc = c - p.C0; }
-            float s[VW], ss[VW];
+            float s[VW], ss[VW], piv[VW];
+            {   // channel c + e lies in group (c + e) / cpg: one pivot load per group the column touches
+                int g = c / p.cpg, rem = c - g * p.cpg;
+                float pv = gn_pivot<IN_DT>(p, b, g);
 #pragma unroll
-            for (int e = 0; e < VW; ++e) { s[e] = 0.0f; ss[e] = 0.0f; }
+                for (int e = 0; e < VW; ++e) {
+                    s[e] = 0.0f; ss[e] = 0.0f; piv[e] = pv;
+                    if (++rem == p.cpg && e + 1 < VW) { rem = 0; pv = gn_pivot<IN_DT>(p, b, ++g); }
+                }
+            }
             const int64_t step = (int64_t)p.rif * ld * esz;
             const char* ptr = base + (((int64_t)b * p.HW + r0 + trow) * ld + cc) * esz;
             int r = r0 + trow;
@@ -201,7 +232,11 @@ __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
                 for (int u = 0; u < U; u += 4) {
                     float v[4][VW];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) gn_unpack<IN_DT, VW>(raw[u + k], v[k]);
+                    for (int k = 0; k < 4; ++k) {
+                        gn_unpack<IN_DT, VW>(raw[u + k], v[k]);
+#pragma unroll
+                        for (int e = 0; e < VW; ++e) v[k][e] -= piv[e];
+                    }
 #pragma unroll
                     for (int e = 0; e < VW; ++e) {
                         s[e] += (v[0][e] + v[1][e]) + (v[2][e] + v[3][e]);
@@ -215,7 +250,7 @@ __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
                 float v0[VW];
                 gn_unpack<IN_DT, VW>(raw0, v0);
 #pragma unroll
-                for (int e = 0; e < VW; ++e) { s[e] += v0[e]; ss[e] += v0[e] * v0[e]; }
+                for (int e = 0; e < VW; ++e) { const float d = v0[e] - piv[e]; s[e] += d; ss[e] += d * d; }
             }
 #pragma unroll
             for (int e = 0; e < VW; ++e) chan[trow * p.C + c + e] = make_float2(s[e], ss[e]);
@@ -240,11 +275,11 @@ __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
             }
             if (l == 0) {
                 const double n = (double)(r1 - r0) * p.cpg;
-                const double mean = s / n;
+                const double mean = s / n;                              // (of x - pivot)
                 double m2 = ss - s * mean;
                 if (m2 < 0.0) m2 = 0.0;
                 float* o = p.ws + (((int64_t)b * p.G + g) * p.nchunks + chunk) * 2;
-                o[0] = (float)mean;
+                o[0] = (float)((double)gn_pivot<IN_DT>(p, b, g) + mean);
                 o[1] = (float)m2;
             }
         }
@@ -258,7 +293,7 @@ __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
 // chunk k holds (mean_k, M2_k) over n_k elements: mean = sum n_k mean_k / N, M2 = sum M2_k + n_k (mean_k - mean)^2.
 // 8 lanes per group, each over chunks j, j+8, ...; fixed-order butterflies (xor partners add the same two values), so
 // every block that evaluates it gets the same bits.
-__device__ __forceinline__ void gn_group_mean_rstd(const GnArgs& p, int b, float* gm, float* gr) {
+__device__ __forceinline__ void gn_group_mean_rstd(const GnArgs& p, int b, float* gm, float* gr, float* gl) {
     const int t = threadIdx.x;
     for (int g0 = 0; g0 < p.G; g0 += (int)blockDim.x >> 3) {
         const int g = g0 + (t >> 3), j = t & 7;
@@ -314,6 +349,7 @@ __device__ __forceinline__ void gn_group_mean_rstd(const GnArgs& p, int b, float
         for (int off = 1; off < 8; off <<= 1) m2 += __shfl_xor(m2, off, 8);
         if (on && j == 0) {
             gm[g] = (float)mean;
+            gl[g] = (float)(mean - (double)gm[g]);                  // mean = gm + gl to 2^-48
             gr[g] = (float)(1.0 / sqrt(m2 / n + (double)p.eps));
         }
     }
@@ -321,7 +357,7 @@ __device__ __forceinline__ void gn_group_mean_rstd(const GnArgs& p, int b, float
 
 // (mean, rstd) of every group of sample b from the per-(row block, group) sums the producing GEMM left (GnArgs::grp0): 8 lanes per
 // group, each over blocks j, j + 8, ... in double; fixed-order butterflies, so every block that evaluates it gets the same bits.
-__device__ __forceinline__ void gn_group_from_sums(const GnArgs& p, int b, float* gm, float* gr) {
+__device__ __forceinline__ void gn_group_from_sums(const GnArgs& p, int b, float* gm, float* gr, float* gl) {
     const int t = threadIdx.x;
     for (int g0 = 0; g0 < p.G; g0 += (int)blockDim.x >> 3) {
         const int g = g0 + (t >> 3), j = t & 7;
@@ -356,16 +392,29 @@ __device__ __forceinline__ void gn_group_from_sums(const GnArgs& p, int b, float
             double m2 = q - s * mean;
             if (m2 < 0.0) m2 = 0.0;
             gm[g] = (float)mean;
+            gl[g] = (float)(mean - (double)gm[g]);
             gr[g] = (float)(1.0 / sqrt(m2 / n + (double)p.eps));
         }
     }
 }
 
+// Where a finalize launch leaves (mean_hi, mean_lo, rstd) of group g of image b for a centered apply pass (GnArgs::centered): the
+// first 3 G floats of the image's own chunk-statistics slots ([G][nchunks][2] floats, nchunks >= 2).  Only the block(s) of image b
+// touch them: gn_finalize_kernel has read all of them (a barrier lies in between), gn_finalize_part_kernel's route never fills them.
+__device__ __forceinline__ float* gn_group_triple(const GnArgs& p, int b, int g) {
+    return p.ws + (int64_t)b * p.G * p.nchunks * 2 + g * 3;
+}
+
 __global__ __launch_bounds__(GN_BLK) void gn_finalize_kernel(const GnArgs p) {
-    __shared__ float gm[64], gr[64];
+    __shared__ float gm[64], gr[64], gl[64];
     const int b = blockIdx.x, t = threadIdx.x;
-    gn_group_mean_rstd(p, b, gm, gr);
+    gn_group_mean_rstd(p, b, gm, gr, gl);
     __syncthreads();
+    if (p.centered)
+        for (int g = t; g < p.G; g += blockDim.x) {
+            float* o = gn_group_triple(p, b, g);
+            o[0] = gm[g]; o[1] = gl[g]; o[2] = gr[g];
+        }
     if (p.stats_out)
         for (int g = t; g < p.G; g += blockDim.x) {
             p.stats_out[((int64_t)b * p.G + g) * 2] = gm[g];
@@ -446,6 +495,10 @@ __global__ __launch_bounds__(GN_BLK) void gn_finalize_part_kernel(const GnArgs p
                 if (m2 < 0.0) m2 = 0.0;
                 gm[g - g0] = (float)mean;
                 gr[g - g0] = (float)(1.0 / sqrt(m2 / n + (double)p.eps));
+                if (p.centered) {
+                    float* o = gn_group_triple(p, b, g);
+                    o[0] = gm[g - g0]; o[1] = (float)(mean - (double)gm[g - g0]); o[2] = gr[g - g0];
+                }
                 if (p.stats_out) {
                     p.stats_out[((int64_t)b * p.G + g) * 2] = gm[g - g0];
                     p.stats_out[((int64_t)b * p.G + g) * 2 + 1] = gr[g - g0];
@@ -480,16 +533,28 @@ template <int IN_DT, int OUT_DT, int VW, int U, bool SILU, bool SEG2>
 __global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, U, SEG2)) void gn_apply_kernel(const GnArgs p, int rows_per_block) {
     const int b = blockIdx.y, t = threadIdx.x;
     const int lcol = t % p.tpr, trow = t / p.tpr;
-    __shared__ float gm[64], gr[64];
+    __shared__ float gm[64], gr[64], gl[64];
+    constexpr bool CENTERED = OUT_DT == MF_F32;      // y = ((x - sm) - sl) * sa + sb (GnArgs::centered); else y = x * sa + sb
+    // the statistics of the groups are in LDS (combined here, or left by a finalize launch): the affine is formed from gamma / beta
+    const bool from_stats = p.fuse_finalize || (CENTERED && p.centered);
     float ga[VW], be[VW];
+    if (!p.fuse_finalize && from_stats) {
+        gn_loadf<VW>(p.gamma + lcol * VW, ga);
+        gn_loadf<VW>(p.beta + lcol * VW, be);
+        for (int g = t; g < p.G; g += blockDim.x) {
+            const float* o = gn_group_triple(p, b, g);
+            gm[g] = o[0]; gl[g] = o[1]; gr[g] = o[2];
+        }
+        __syncthreads();
+    }
     if (p.fuse_finalize) {       // every block combines the chunk statistics itself: one launch (and its gap) less
         // (the affine parameters of the thread's first column are requested first: their latency hides under the combine)
         if constexpr (U <= 4) {
             gn_loadf<VW>(p.gamma + lcol * VW, ga);
             gn_loadf<VW>(p.beta + lcol * VW, be);
         }
-        if (p.fuse_finalize == 2) gn_group_from_sums(p, b, gm, gr);
-        else gn_group_mean_rstd(p, b, gm, gr);
+        if (p.fuse_finalize == 2) gn_group_from_sums(p, b, gm, gr, gl);
+        else gn_group_mean_rstd(p, b, gm, gr, gl);
         if constexpr (U > 4) {                           // (U = 8, the developer sweep, has no registers to spare across the combine)
             gn_loadf<VW>(p.gamma + lcol * VW, ga);
             gn_loadf<VW>(p.beta + lcol * VW, be);
@@ -508,25 +573,30 @@ __global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, U, SEG2)) voi
     constexpr int esz = IN_DT == MF_F32 ? 4 : 2, osz = OUT_DT == MF_F32 ? 4 : 2;
     constexpr bool fast_silu = OUT_DT != MF_F32;        // 16-bit output: __expf is far inside the rounding
     const float* ab = p.ws_ab + (int64_t)b * 2 * p.C;
-    float sa[VW], sb[VW];
+    float sa[VW], sb[VW], sm[CENTERED ? VW : 1], sl[CENTERED ? VW : 1];
     auto affine = [&](int c, const float* gam, const float* bet) {
         int g = c / p.cpg, rem = c - g * p.cpg;          // one division per column: channel c + e lies in group (c + e) / cpg
 #pragma unroll
         for (int e = 0; e < VW; ++e) {
             sa[e] = gr[g] * gam[e];
-            sb[e] = bet[e] - gm[g] * sa[e];
+            if constexpr (CENTERED) { sb[e] = bet[e]; sm[e] = gm[g]; sl[e] = gl[g]; }
+            else sb[e] = bet[e] - gm[g] * sa[e];
             if (++rem == p.cpg) { rem = 0; ++g; }
         }
     };
-    if (p.fuse_finalize) affine(lcol * VW, ga, be);
+    if (from_stats) affine(lcol * VW, ga, be);
     // the output of a block: a wave-uniform base plus a 32-bit lane offset that is the same for every row of the thread
     char* const obase = p.out + ((int64_t)b * p.HW + r0) * p.C * osz;
     const int64_t ostep = (int64_t)p.rif * p.C * osz;
     for (int col = lcol; col < p.cvn; col += p.tpr) {
         const int c = col * VW;
-        if (!p.fuse_finalize) {
+        if (!from_stats) {
             gn_loadf<VW>(ab + c, sa);
             gn_loadf<VW>(ab + p.C + c, sb);
+            if constexpr (CENTERED) {                    // (not centered — gamma / beta off 16 bytes, one chunk: the per-channel shift, around a mean of 0)
+#pragma unroll
+                for (int e = 0; e < VW; ++e) { sm[e] = 0.0f; sl[e] = 0.0f; }
+            }
         } else if (col != lcol) {
             float g2[VW], b2[VW];
             gn_loadf<VW>(p.gamma + c, g2);
@@ -556,7 +626,9 @@ __global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, U, SEG2)) voi
             gn_unpack<IN_DT, VW>(raw, v);
 #pragma unroll
             for (int e = 0; e < VW; ++e) {
-                float y = v[e] * sa[e] + sb[e];
+                float y;
+                if constexpr (CENTERED) y = ((v[e] - sm[e]) - sl[e]) * sa[e] + sb[e];
+                else y = v[e] * sa[e] + sb[e];
                 if constexpr (SILU) y = fast_silu ? silu_f(y) : silu_precise(y);
                 v[e] = y;
             }
@@ -594,7 +666,7 @@ __global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, U, SEG2)) voi
 // grid (C / SC, batch): a block owns a SLAB of SC = lcm(cpg, 8) channels = whole groups = nv 16-byte vector columns
 // over ALL HW rows of one sample, so the statistics never leave the block and the rows never leave the registers.
 // Thread t = lane * nv + vcol keeps vector column vcol of rows lane, lane + P, ... (at most ROWS): per-channel fp32
-// (sum, sum of squares) -> LDS -> one wave per group combines them in double in a fixed order (bitwise
+// (sum, sum of squares) of x - pivot -> LDS -> one wave per group combines them in double in a fixed order (bitwise
 // reproducible) -> y = silu(x * a[c] + b[c]) from the registers.
 // Storage dtypes, SiLU and the deferred split-K input (SK: GnArgs::sk_ws) are template arguments.  Everything the block needs from
 // memory is requested at the top, before the first wait: gamma / beta (and bias / temb of a deferred reduce), then all ROWS rows —
@@ -602,8 +674,8 @@ __global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, U, SEG2)) voi
 template <int IN_DT, int OUT_DT, bool SILU, bool SK, int ROWS = 4>
 __global__ __launch_bounds__(1024, IN_DT != MF_F32 && OUT_DT != MF_F32 ? 5 : 4) void gn_slab_kernel(const GnArgs p, int SC, int nv, int P) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float2* chan = reinterpret_cast<float2*>(smem_raw);              // [P][SC or SC/8] (sum, sum of squares)
-    __shared__ float gm[8], gr[8];
+    float2* chan = reinterpret_cast<float2*>(smem_raw);              // [P][SC or SC/8] (sum, sum of squares) of x - pivot
+    __shared__ float gm[8], gr[8], gp[8];                            // per group of the slab: mean, rstd, pivot
     const int slab = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
     const int vcol = t % nv, lane = t / nv;
     const bool active = lane < P;                      // the block is padded to whole waves for the butterflies
@@ -619,7 +691,6 @@ __global__ __launch_bounds__(1024, IN_DT != MF_F32 && OUT_DT != MF_F32 ? 5 : 4) 
     // the rows of the thread stay PACKED from here to the stores behind the two barriers (4 VGPRs per 16-bit row, not 8): they
     // are unpacked once for the statistics and once more for the output
     gn_raw<IN_DT, 8> raw[ROWS];
-    float v[ROWS][8];
     if constexpr (!SK) {
         const char* base; int64_t ld; int cc;
         if (c < p.C0) { base = p.x0; ld = p.C0; cc = c; }
@@ -629,13 +700,6 @@ __global__ __launch_bounds__(1024, IN_DT != MF_F32 && OUT_DT != MF_F32 ? 5 : 4) 
             const int row = lane + i * P < p.HW ? lane + i * P : p.HW - 1;
             gn_load<IN_DT, 8>(base + (((int64_t)b * p.HW + row) * ld + cc) * esz, raw[i]);
         }
-#pragma unroll
-        for (int i = 0; i < ROWS; ++i) {
-            gn_unpack<IN_DT, 8>(raw[i], v[i]);
-            const bool in = lane + i * P < p.HW;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[i][e] = in ? v[i][e] : 0.0f;
-        }
     } else {
         // the producer's split-K slabs: summed in slab order, + bias + temb, * alpha, rounded to the storage dtype — what
         // splitk_reduce_kernel + epilogue_store8 (csrc/gemm_conv.hip) would have stored and this kernel read back
@@ -643,6 +707,7 @@ __global__ __launch_bounds__(1024, IN_DT != MF_F32 && OUT_DT != MF_F32 ? 5 : 4) 
         float bt[8], tb[8];                            // (an absent term is read from gamma and never added)
         gn_loadf<8>(has_bias ? p.sk_bias + c : p.gamma + c, bt);
         gn_loadf<8>(has_temb ? p.sk_temb + (int64_t)b * p.sk_ld_temb + c : p.gamma + c, tb);
+        float v[ROWS][8];
 #pragma unroll
         for (int i = 0; i < ROWS; ++i)
 #pragma unroll
@@ -678,21 +743,45 @@ __global__ __launch_bounds__(1024, IN_DT != MF_F32 && OUT_DT != MF_F32 ? 5 : 4) 
             // rounded values
             gn_repack<IN_DT>(v[i], raw[i]);
             gn_forget(raw[i]);                         // (fp32 storage: what the reduce would have stored, not a product to contract into the sums below)
-            gn_unpack<IN_DT, 8>(raw[i], v[i]);
         }
-        // (the slab sums, bias and temb took the registers until here: gamma / beta are requested now, two barriers ahead of their use)
-        gn_loadf<8>(p.gamma + c, sa);
-        gn_loadf<8>(p.beta + c, sb);
     }
-    if (active) {
-        float s[8], ss[8];
+    // (the rows wait for the barrier in their packed form: the statistics unpack them once more, channel by channel)
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) gn_forget(raw[i]);
+    // The pivot of every group of the slab (see gn_stats_kernel): the value at row 0, first channel of the group, as stored (or as
+    // the deferred reduce would have stored it), published by the thread that holds it.  Row 0 is the first row of lane 0.
+    if (lane == 0) {
+        float x0[8];
+        gn_unpack<IN_DT, 8>(raw[0], x0);
+        int g = vcol * 8 / p.cpg, rem = vcol * 8 - g * p.cpg;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
+            if (rem == 0) gp[g] = x0[e];
+            if (++rem == p.cpg) { rem = 0; ++g; }
+        }
+    }
+    __syncthreads();
+    if (active) {
+        float s[8], ss[8];
+        int g = vcol * 8 / p.cpg, rem = vcol * 8 - g * p.cpg;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {                              // channel by channel: one pivot and one element of every row at a time
+            const float pv = gp[g];
+            if (++rem == p.cpg) { rem = 0; ++g; }
+            float d[ROWS];
+#pragma unroll
+            for (int i = 0; i < ROWS; ++i) {
+                float x[8];
+                gn_unpack<IN_DT, 8>(raw[i], x);
+                d[i] = lane + i * P < p.HW ? x[e] - pv : 0.0f;     // (a row past the end counts as zeros, not as minus the pivot)
+            }
             s[e] = 0.0f; ss[e] = 0.0f;
+            // The squares are summed as one explicit fma chain: left to the compiler, d0 * d0 + d1 * d1 is contracted one way in
+            // one instantiation and the other way in the next, and the deferred split-K form (SK) must give the bits of the plain one.
 #pragma unroll
             for (int i = 0; i < ROWS; i += 4) {
-                s[e] += (v[i][e] + v[i + 1][e]) + (v[i + 2][e] + v[i + 3][e]);
-                ss[e] += (v[i][e] * v[i][e] + v[i + 1][e] * v[i + 1][e]) + (v[i + 2][e] * v[i + 2][e] + v[i + 3][e] * v[i + 3][e]);
+                s[e] += (d[i] + d[i + 1]) + (d[i + 2] + d[i + 3]);
+                ss[e] += fmaf(d[i + 3], d[i + 3], fmaf(d[i + 2], d[i + 2], fmaf(d[i + 1], d[i + 1], __fmul_rn(d[i], d[i]))));
             }
         }
         if (whole) {
@@ -706,6 +795,12 @@ __global__ __launch_bounds__(1024, IN_DT != MF_F32 && OUT_DT != MF_F32 ? 5 : 4) 
     }
 #pragma unroll
     for (int i = 0; i < ROWS; ++i) gn_forget(raw[i]);
+    if constexpr (SK) {
+        // (the slab sums, bias and temb, then the shifted sums took the registers until here: gamma / beta are requested now, a
+        // barrier and the combine ahead of their use)
+        gn_loadf<8>(p.gamma + c, sa);
+        gn_loadf<8>(p.beta + c, sb);
+    }
     __syncthreads();
     {   // one wave per group of the slab: fixed-order partial sums in double, then a butterfly
         const int l = t & 63, ipg = whole ? p.cpg / 8 : p.cpg, items = P * ipg, gps = SC / p.cpg;
@@ -724,10 +819,10 @@ __global__ __launch_bounds__(1024, IN_DT != MF_F32 && OUT_DT != MF_F32 ? 5 : 4) 
             }
             if (l == 0) {
                 const double n = (double)p.HW * p.cpg;
-                const double mean = s / n;
+                const double mean = s / n;                              // (of x - pivot)
                 double m2 = ss - s * mean;
                 if (m2 < 0.0) m2 = 0.0;
-                gm[g] = (float)mean;
+                gm[g] = (float)((double)gp[g] + mean);
                 gr[g] = (float)(1.0 / sqrt(m2 / n + (double)p.eps));
                 if (p.stats_out) {
                     p.stats_out[((int64_t)b * p.G + slab * gps + g) * 2] = gm[g];
@@ -778,22 +873,30 @@ __global__ __launch_bounds__(256) void layernorm8_kernel(const char* x, int in_d
     constexpr int MAXV = 8;
     float v[MAXV][8];
     const int c8n = C >> 3;
-    float s = 0.0f;
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {
         const int c8 = l32 + 32 * j;
         if (live && c8 < c8n) {
             load8<F16>(x, in_dt, row * C + c8 * 8, v[j]);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s += v[j][e];
         } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[j][e] = 0.0f;
         }
     }
+    // The mean is pivot + sum(x - pivot) / C with the row's first element as the pivot: the fp32 sum of the raw values carries a
+    // rounding error of the order of |mean|, which rstd then multiplies (a constant row came out as beta + 1e-2)
+    const float piv = __shfl(v[0][0], 0, 32);
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < MAXV; ++j) {
+        if (l32 + 32 * j < c8n) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s += v[j][e] - piv;
+        }
+    }
 #pragma unroll
     for (int off = 16; off >= 1; off >>= 1) s += __shfl_xor(s, off, 32);
-    const float mean = s / (float)C;
+    const float mean = piv + s / (float)C;
     float q = 0.0f;
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {
@@ -832,20 +935,20 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const char* x, int in_dt
     constexpr int MAXV = 8;
     float4 v[MAXV];
     const int c4n = C >> 2;
-    float s = 0.0f;
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {
         const int c4 = lane + 64 * j;
-        if (c4 < c4n) {
-            v[j] = load4<F16>(x, in_dt, row * C + c4 * 4);
-            s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-        } else {
-            v[j] = make_float4(0, 0, 0, 0);
-        }
+        v[j] = c4 < c4n ? load4<F16>(x, in_dt, row * C + c4 * 4) : make_float4(0, 0, 0, 0);
+    }
+    const float piv = __shfl(v[0].x, 0, 64);             // (the mean as pivot + sum(x - pivot) / C: see layernorm8_kernel)
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < MAXV; ++j) {
+        if (lane + 64 * j < c4n) s += ((v[j].x - piv) + (v[j].y - piv)) + ((v[j].z - piv) + (v[j].w - piv));
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    const float mean = s / (float)C;
+    const float mean = piv + s / (float)C;
     float q = 0.0f;
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {
@@ -967,6 +1070,7 @@ extern "C" int mf_groupnorm(const mf_groupnorm_desc* d, void* stream) {
     // (round 3: fetching a thread's first rows AHEAD of the combine, so that the fused form could also serve 64x64, was
     // measured neutral there — 26.3 vs 25.6 us, tools/bench_gn.py, and 16.70 vs 16.75 ms per denoise step — and removed)
     a.fuse_finalize = !gn3 && d->hw <= 1024 && mf_aligned16(d->gamma) && mf_aligned16(d->beta);
+    a.centered = d->out_dtype == MF_F32 && a.nchunks >= 2 && mf_aligned16(d->gamma) && mf_aligned16(d->beta);
     const int vw = (d->c0 % 8 == 0 && d->c1 % 8 == 0) ? 8 : 4;
     hipStream_t s = (hipStream_t)stream;
     {   // one-launch slab kernel for the low-resolution levels

@@ -1110,7 +1110,7 @@ __global__ __launch_bounds__(256) void groupnorm_bwd_kernel(const GnBwdArgs p) {
 }
 
 // ---- the streaming form for hw >= 256: five launches, every load a coalesced float4 over channels --------------------
-// A: per (image, pixel chunk) per-channel  sum x, sum x^2            -> part      R1: per (image, group) mean, rstd
+// A: per (image, pixel chunk) per-channel  sum x', sum x'^2 (x' = x - pivot) -> part   R1: per (image, group) mean, rstd
 // B: per (image, pixel chunk) per-channel  sum dz, sum dz * xhat     -> part      R2: dgamma / dbeta partials, m1, m2
 // C: dx = rstd * (dz * gamma - m1 - xhat * m2)
 // One block per (image, group) as above leaves one block per CU and 40-byte runs per pixel at 320 channels (10 per group):
@@ -1130,7 +1130,15 @@ __device__ __forceinline__ float4 gn_ld4(const GnBwdArgs& p, int b, int px, int 
                     : *reinterpret_cast<const float4*>(p.x1 + ((int64_t)b * p.hw + px) * p.c1 + (c - p.c0));
 }
 
-template <int PHASE>      // 0: sums of x, x^2; 1: sums of dz, dz * xhat; 2: dx
+// Phase 0 sums x - pivot, one pivot per (image, group): the value at the image's first pixel, first channel of the group.  fp32 sums
+// of the raw x and x^2 lose the variance once the mean dwarfs the spread (csrc/norm.hip, gn_stats_kernel, does the same); R1
+// restores mean = pivot + S / n, var = SS / n - (S / n)^2 in double.
+__device__ __forceinline__ float gn_bwd_pivot(const GnBwdArgs& p, int b, int g, int cpg) {
+    const int c = g * cpg;
+    return c < p.c0 ? p.x0[(int64_t)b * p.hw * p.c0 + c] : p.x1[(int64_t)b * p.hw * p.c1 + (c - p.c0)];
+}
+
+template <int PHASE>      // 0: sums of x - pivot, (x - pivot)^2; 1: sums of dz, dz * xhat; 2: dx
 __global__ __launch_bounds__(256) void gn_bwd2_kernel(const GnBwd2Args q2) {
     const GnBwdArgs& p = q2.a;
     __shared__ float red[2][4][256];
@@ -1155,13 +1163,18 @@ __global__ __launch_bounds__(256) void gn_bwd2_kernel(const GnBwd2Args q2) {
             }
         }
         float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
+        float piv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (PHASE == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) piv[j] = gn_bwd_pivot(p, b, (4 * q + j) / cpg, cpg);
+        }
         if (active)
             for (int px = px0 + rl; px < px1; px += rif) {
                 const float4 xv4 = gn_ld4(p, b, px, q);
                 const float xv[4] = {xv4.x, xv4.y, xv4.z, xv4.w};
                 if (PHASE == 0) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) { s0[j] += xv[j]; s1[j] += xv[j] * xv[j]; }
+                    for (int j = 0; j < 4; ++j) { const float d = xv[j] - piv[j]; s0[j] += d; s1[j] += d * d; }
                 } else {
                     const float4 dy4 = *reinterpret_cast<const float4*>(p.dy + ((int64_t)b * p.hw + px) * C + 4 * q);
                     const float dyv[4] = {dy4.x, dy4.y, dy4.z, dy4.w};
@@ -1252,10 +1265,10 @@ __global__ __launch_bounds__(256) void gn_bwd2_reduce_kernel(const GnBwd2Args q2
         const double n = (double)p.hw * cpg;
         float* st = q2.stats + ((int64_t)b * p.groups + g) * 4;
         if (PH == 0) {
-            const double mean = s / n;
+            const double mean = s / n;                                  // (of x - pivot)
             double var = ss / n - mean * mean;
             if (var < 0.0) var = 0.0;
-            st[0] = (float)mean;
+            st[0] = (float)((double)gn_bwd_pivot(p, b, g, cpg) + mean);
             st[1] = (float)(1.0 / sqrt(var + (double)p.eps));
         } else {
             st[2] = (float)(s / n);

@@ -203,6 +203,22 @@ typedef struct mf_gemm_desc {
 } mf_gemm_desc;
 
 int mf_gemm_conv(const mf_gemm_desc* d, void* stream);
+/* What mf_gemm_conv would do with a descriptor, decided on the host: mf_gemm_conv is this plan followed by its launches.
+ * mf_gemm_conv_plan makes every check and every choice of the call (same return code, same mf_last_error text), launches nothing,
+ * needs no GPU and reads neither device memory nor the descriptor's host out-pointers (gn_part_rows, gn_grouped, deferred_splits:
+ * only their null-ness counts).  The one refusal left to the launch is "tile not instantiated for this dtype". */
+typedef struct mf_gemm_plan {
+    int32_t tile;               /* the resolved tile (descriptor's, tuned by the caller, or the library heuristic) */
+    int32_t splitk;             /* K slices after "no empty splits" (1 = none) */
+    int32_t tiles_per_block;    /* output tiles a block of the persistent tiles 69 / 70 walks; 1 elsewhere */
+    int32_t blocks;             /* blocks of the main launch */
+    int32_t reduce_launch;      /* 1: a separate split-K reduce launch follows the main one */
+    int32_t deferred_splits;    /* what *deferred_splits receives (0: the call completes `out` itself) */
+    int32_t gn_part_rows;       /* what *gn_part_rows receives (0 without gn_part) */
+    int32_t gn_grouped;         /* what *gn_grouped receives */
+} mf_gemm_plan;
+int mf_gemm_conv_plan(const mf_gemm_desc* d, mf_gemm_plan* out);
+int mf_sizeof_gemm_plan(void);
 /* number of instantiated tile configurations and their (BM, BN) */
 int mf_gemm_num_tiles(void);
 int mf_gemm_tile_shape(int tile, int* bm, int* bn);
@@ -247,6 +263,9 @@ typedef struct mf_groupnorm_desc {
 } mf_groupnorm_desc;
 int mf_groupnorm(const mf_groupnorm_desc* d, void* stream);
 int64_t mf_groupnorm_ws_floats(int32_t batch, int32_t groups, int32_t channels);
+/* 1 when the shape of [*, hw, channels] in `groups` groups (one segment) fits mf_groupnorm's one-launch slab form, the form sk_ws needs;
+ * the pointer alignments the form also asks for are checked by mf_groupnorm itself.  No GPU needed. */
+int mf_groupnorm_slab_applies(int32_t hw, int32_t channels, int32_t groups);
 
 /* LayerNorm over the last dim of [rows][c]; replaces nn.LayerNorm (attention.py:203,233,261). */
 int mf_layernorm(const void* x, int32_t in_dtype, void* out, int32_t out_dtype, const float* gamma,

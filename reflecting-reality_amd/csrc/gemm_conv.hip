@@ -1,5 +1,5 @@
-// Host entry point of the implicit-GEMM family (mf_gemm_conv): argument checks, tile / split-K choice, dispatch to the tile
-// groups (gemm_*.hip, conv_halo.hip).  Kernel template and design notes: gemm_conv_kernel.h.
+// Host entry points of the implicit-GEMM family (mf_gemm_conv, mf_gemm_conv_plan): argument checks, tile / split-K choice (gemm_plan),
+// dispatch to the tile groups (gemm_launch; gemm_*.hip, conv_halo.hip).  Kernel template and design notes: gemm_conv_kernel.h.
 #include "gemm_conv_kernel.h"
 
 namespace mfgemm {
@@ -252,33 +252,35 @@ int pick_tile(int M, int N, int nz, int splitk, int max_tile = kNumTiles, bool s
     return best;
 }
 
-}  // namespace
-}  // namespace mfgemm
-using namespace mfgemm;
+// ---- plan, then launch: gemm_plan makes every check and every decision of a call on the host (no HIP runtime call; no device pointer
+// and no host out-pointer of the descriptor is dereferenced), gemm_launch issues what the plan says.  mf_gemm_conv is one after the
+// other, mf_gemm_conv_plan reports the first.
+enum GemmFamily { kTiled, kHalo, kNloop, kPers };        // the implicit-GEMM template, resident-patch tiles 16-19, tile 69, tile 70
+enum GnStats { kGnNone, kGnFused, kGnColsum };           // mf_gemm_desc.gn_part: off, in the epilogue, by gn_colsum*_kernel afterwards
+struct GemmPlan {
+    GemmArgs a;                                 // everything but ovf / stamps (runtime addresses: gemm_launch)
+    int tile; GemmFamily family; dim3 grid;     // ... of the main launch
+    bool a_f32;                                 // fp32 activations converted on load (bf16 compute)
+    bool reduce_launch; int deferred_splits;    // a split-K reduce launch follows / (> 0) is left to the consumer (mf_gemm_desc.defer_reduce)
+    GnStats gn; int gn_rows; bool gn_grouped;   // rows per block of the statistics (*gn_part_rows), per-group sums too (*gn_grouped)
+};
 
-unsigned* mf_ovf_flag_gemm() {
-    unsigned* p = nullptr;
-    (void)hipGetSymbolAddress((void**)&p, HIP_SYMBOL(g_split_ovf_gemm));
-    return p;
+// column ranges per row tile of the persistent tiles: enough blocks for the chip (one block per CU), as many output tiles per block
+// as that leaves.  `forced`: the caller's developer sweep (MFHIP_*_RANGES), 0 = none
+int column_ranges(int tiles_m, int tiles_n, int forced) {
+    int ranges = 1;
+    while (tiles_m * ranges < 256 && tiles_n % (ranges * 2) == 0) ranges *= 2;
+    return (forced > 0 && tiles_n % forced == 0) ? forced : ranges;
 }
 
-#ifdef MF_STAMPS
-extern "C" int mf_debug_set_stamps(void* ptr) {
-    g_stamps_host = (unsigned long long*)ptr;      // handed to every later launch in GemmArgs::stamps
-    return 0;
-}
-#endif
-
-extern "C" int mf_gemm_num_tiles(void) { return kNumTiles; }
-extern "C" int mf_gemm_tile_table_version(void) { return 1; }
-extern "C" int mf_gemm_tile_shape(int tile, int* bm, int* bn) {
-    if (tile < 1 || tile > kNumTiles) return MF_EINVAL;
-    *bm = kTiles[tile - 1].bm;
-    *bn = kTiles[tile - 1].bn;
-    return MF_OK;
+// both operands addressable with 31-bit byte offsets from their bases (aes / es: bytes per element of A / W)
+bool operands_fit31(const mf_gemm_desc* d, const GemmArgs& a, int aes, int es) {
+    const int64_t ext_a = ((int64_t)d->batch * d->h_in * d->w_in - 1) * (a.ld0b > a.ld1b ? a.ld0b : a.ld1b) + (int64_t)a.Ctot * aes;
+    const int64_t ext_w = ((int64_t)(a.N - 1) * a.ldw + a.K) * es;
+    return ext_a < (1ll << 31) - (1 << 20) && ext_w < (1ll << 31) - (1 << 20);
 }
 
-extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
+int gemm_plan(const mf_gemm_desc* d, GemmPlan* plan) {
     MF_CHECK_ARG(d != nullptr, "mf_gemm_conv: null descriptor");
     MF_CHECK_ARG(d->dtype == MF_F32 || d->dtype == MF_BF16 || d->dtype == MF_F16X3 || d->dtype == MF_BF16X3 || d->dtype == MF_FP8 ||
                      d->dtype == MF_BF16X1 || d->dtype == MF_F16,
@@ -314,16 +316,9 @@ extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
     MF_CHECK_ARG((d->a_zs_o % vec) == 0 && (d->a_zs_i % vec) == 0 && (d->w_zs_o % vec) == 0 && (d->w_zs_i % vec) == 0,
                  "mf_gemm_conv: batch strides must be multiples of %d elements", vec);
 
-    GemmArgs a{};
-    a.howo_sh = a.wo_sh = a.ho_sh = -1;       // (set with the geometry below; the resident-patch tiles return before that)
-    {
-        static unsigned* ovf = mf_ovf_flag_gemm();
-        a.ovf = ovf;
-    }
-#ifdef MF_STAMPS
-    a.stamps = g_stamps_host;
-#endif
-    const bool a_f32 = (d->a_dtype == MF_F32 && d->dtype == MF_BF16);
+    *plan = GemmPlan{};
+    GemmArgs& a = plan->a;
+    const bool a_f32 = plan->a_f32 = (d->a_dtype == MF_F32 && d->dtype == MF_BF16);
     const int aes = a_f32 ? 4 : es;
     a.a0 = (const char*)d->a0; a.a1 = (const char*)d->a1;
     a.C0 = d->c0; a.Ctot = d->c0 + d->c1;
@@ -332,10 +327,8 @@ extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
     a.ld0b = (int)(d->lda0 * aes); a.ld1b = (int)(d->lda1 * aes);
     a.Hin = d->h_in; a.Win = d->w_in; a.Ho = d->h_out; a.Wo = d->w_out; a.HoWo = d->h_out * d->w_out;
     a.KW = d->kw; a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.ups = d->upsample;
-    {
-        auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (v > 0 && (1 << s) == v) ? s : -1; };
-        a.howo_sh = lg(a.HoWo); a.wo_sh = lg(a.Wo); a.ho_sh = lg(a.Ho);
-    }
+    auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (v > 0 && (1 << s) == v) ? s : -1; };
+    a.howo_sh = lg(a.HoWo); a.wo_sh = lg(a.Wo); a.ho_sh = lg(a.Ho);
     a.w = (const char*)d->w; a.ldw = d->ldw;
     const int64_t M64 = (int64_t)d->batch * d->h_out * d->w_out;
     MF_CHECK_ARG(M64 < (1ll << 31), "mf_gemm_conv: M too large");
@@ -381,30 +374,18 @@ extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
                  "mf_gemm_conv: the GEGLU epilogue needs n %% 8 == 0, ldc %% 4 == 0, no residuals and no forced split-K");
     MF_CHECK_ARG(d->nz == 1 || (d->res0 == nullptr && d->res1 == nullptr && d->temb == nullptr),
                  "mf_gemm_conv: residual/temb epilogue is not defined for batched (nz > 1) calls");
-    // GroupNorm partial sums of the output (mf_gemm_desc.gn_part): R rows per block, in the epilogue or by gn_colsum_kernel
+    // GroupNorm partial sums of the output (mf_gemm_desc.gn_part): R rows per block, in the epilogue (kGnFused, the implicit-GEMM
+    // template only) or by gn_colsum*_kernel over the stored output (kGnColsum)
     const int gn_hw = d->h_out * d->w_out;
-    const int gn_r_fallback = gn_hw % 128 == 0 ? 128 : (gn_hw % 64 == 0 ? 64 : 32);
     if (d->gn_part) {
         MF_CHECK_ARG(d->gn_part_rows != nullptr && d->n % 8 == 0 && d->nz == 1 && gn_hw % 32 == 0 && d->act != MF_ACT_GEGLU4 && !d->vt_out &&
                          d->ldc >= d->n && d->o_zs_o == 0 && d->o_zs_i == 0 && mf_aligned16(d->gn_part) &&
                          d->gn_part_floats >= 2ll * d->n * (M64 / 32),
                      "mf_gemm_conv: gn_part needs gn_part_rows, n %% 8 == 0, nz == 1, h_out * w_out %% 32 == 0, no GEGLU / vt_out, and "
                      "2 * n * (M / 32) = %lld floats (got %lld)", (long long)(2ll * d->n * (M64 / 32)), (long long)d->gn_part_floats);
+        plan->gn = kGnColsum;
+        plan->gn_rows = gn_hw % 128 == 0 ? 128 : (gn_hw % 64 == 0 ? 64 : 32);
     }
-    if (d->gn_grouped) *d->gn_grouped = 0;
-    auto gn_fallback = [&](hipStream_t st) -> int {     // after the launch(es) that wrote `out`
-        if ((mf_is16(d->out_dtype) || d->out_dtype == MF_F32) && d->ldc % 8 == 0 && mf_aligned16(d->out)) {
-            const dim3 g8((unsigned)(a.M / gn_r_fallback), (unsigned)cdiv(a.N, 256));
-            if (d->out_dtype == MF_F16) hipLaunchKernelGGL(gn_colsum8_kernel<1>, g8, dim3(256), 0, st, (const char*)d->out, d->ldc, a.M, a.N, gn_r_fallback, (float2*)d->gn_part);
-            else if (d->out_dtype == MF_F32) hipLaunchKernelGGL(gn_colsum8_kernel<2>, g8, dim3(256), 0, st, (const char*)d->out, d->ldc, a.M, a.N, gn_r_fallback, (float2*)d->gn_part);
-            else hipLaunchKernelGGL(gn_colsum8_kernel<0>, g8, dim3(256), 0, st, (const char*)d->out, d->ldc, a.M, a.N, gn_r_fallback, (float2*)d->gn_part);
-        } else
-        hipLaunchKernelGGL(gn_colsum_kernel, dim3((unsigned)(a.M / gn_r_fallback), (unsigned)cdiv(a.N, 256)), dim3(256), 0, st,
-                           (const char*)d->out, d->out_dtype, d->ldc, a.M, a.N, gn_r_fallback, (float2*)d->gn_part);
-        *d->gn_part_rows = gn_r_fallback;
-        MF_CHECK_LAUNCH("mf_gemm_conv(gn_part column sums)");
-        return MF_OK;
-    };
     // the 8-wide vector epilogue needs 8-channel-aligned rows and 16-byte aligned bases everywhere
     a.vec_ok = (d->n % 8 == 0) && (d->ldc % (d->act == MF_ACT_GEGLU4 ? 4 : 8) == 0) && mf_aligned16(d->out) && (d->o_zs_o % 8 == 0) &&
                (d->o_zs_i % 8 == 0) &&
@@ -428,18 +409,17 @@ extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
     MF_CHECK_ARG(tile < 31 || split_ws || (!a_f32 && !split && d->dtype != MF_FP8), "mf_gemm_conv: tile %d (deep ring) does not apply to this precision", tile);
     MF_CHECK_ARG(tile < 37 || mf_is16(d->dtype) || split_ws,
                  "mf_gemm_conv: tile %d (warp-specialised) does not apply: bf16, or f16x3 with a pre-split weight on tiles 37 / 38 / 41 / 44", tile);
+    plan->tile = tile;
     const TileCfg& tc = kTiles[tile - 1];
+    const bool fit31 = operands_fit31(d, a, aes, es);
+    const bool same3x3 = d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && !d->upsample &&
+                         d->h_out == d->h_in && d->w_out == d->w_in && d->nz == 1;
+    a.ws = d->ws;
     if (tc.halo) {
         // conv3x3_halo_kernel: bf16, 3x3 / stride 1 / pad 1, whole TH x 16 tiles, 32-channel chunks
-        const int64_t npix = (int64_t)d->batch * d->h_in * d->w_in;
-        const int64_t ext_a = (npix - 1) * (int64_t)(a.ld0b > a.ld1b ? a.ld0b : a.ld1b) + (int64_t)a.Ctot * 2;
-        const int64_t ext_w = ((int64_t)(a.N - 1) * a.ldw + a.K) * 2;
-        const bool ok = d->dtype == MF_BF16 && !a_f32 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_t == 1 &&
-                        d->pad_l == 1 && !d->upsample && d->h_out == d->h_in && d->w_out == d->w_in && d->nz == 1 &&
-                        d->h_in % tc.halo == 0 && d->w_in % 16 == 0 && a.C0 % (tc.halo == 16 ? 64 : 32) == 0 &&
-                        a.Ctot % (tc.halo == 16 ? 64 : 32) == 0 &&
-                        ext_a < (1ll << 31) - (1 << 20) && ext_w < (1ll << 31) - (1 << 20) && d->act != MF_ACT_GEGLU4 &&
-                        d->o_zs_o == 0 && d->o_zs_i == 0;
+        const bool ok = d->dtype == MF_BF16 && !a_f32 && same3x3 && d->h_in % tc.halo == 0 && d->w_in % 16 == 0 &&
+                        a.C0 % (tc.halo == 16 ? 64 : 32) == 0 && a.Ctot % (tc.halo == 16 ? 64 : 32) == 0 && fit31 &&
+                        d->act != MF_ACT_GEGLU4 && d->o_zs_o == 0 && d->o_zs_i == 0;
         MF_CHECK_ARG(ok, "mf_gemm_conv: tile %d (3x3 halo kernel) does not apply to this call", tile);
         a.nkt = a.Ctot / (tc.halo == 16 ? 64 : 32);
         const int64_t tiles = (int64_t)(a.M / tc.bm) * cdiv(a.N, tc.bn);
@@ -456,34 +436,19 @@ extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
         if (sk > a.nkt) sk = a.nkt;
         a.kt_per_split = cdiv(a.nkt, sk);
         a.splitk = cdiv(a.nkt, a.kt_per_split);
-        a.ws = d->ws;
         MF_CHECK_ARG(a.splitk == 1 || (a.ws != nullptr && (int64_t)a.splitk * a.M * a.N <= d->ws_floats),
                      "mf_gemm_conv: split-K=%d needs a workspace of %lld floats", a.splitk, (long long)a.splitk * a.M * a.N);
         a.tiles_n = cdiv(a.N, tc.bn);
         a.nblk = (int)tiles;
-        dim3 hgrid((unsigned)tiles, 1, (unsigned)a.splitk);
-        hipStream_t hs = (hipStream_t)stream;
-        MF_CHECK_ARG(launch_halo_family(tile, a, hgrid, hs), "mf_gemm_conv: tile %d is not a resident-patch tile", tile);
-        MF_CHECK_LAUNCH("mf_gemm_conv(halo)");
-        if (a.splitk > 1) {
-            const int64_t total = (int64_t)a.M * a.N / (a.vec_ok ? 8 : 1);
-            int blocks = (int)((total + 255) / 256);
-            if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL(d->dtype == MF_F16 ? splitk_reduce_kernel<true> : splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, hs, a);
-            MF_CHECK_LAUNCH("mf_gemm_conv(split-K reduce)");
-        }
-        if (d->gn_part) return gn_fallback(hs);
+        plan->family = kHalo;
+        plan->grid = dim3((unsigned)tiles, 1, (unsigned)a.splitk);
+        plan->reduce_launch = a.splitk > 1;
         return MF_OK;
     }
     const int bk = 128 / es;
     a.nkt = cdiv(a.K, bk);
     if (tc.dxr) {
-        const int64_t npix = (int64_t)d->batch * d->h_in * d->w_in;
-        const int64_t ext_a = (npix - 1) * (int64_t)(a.ld0b > a.ld1b ? a.ld0b : a.ld1b) + (int64_t)a.Ctot * aes;
-        const int64_t ext_w = ((int64_t)(a.N - 1) * a.ldw + a.K) * es;
-        const bool ok = !a_f32 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 && !d->upsample &&
-                        d->h_out == d->h_in && d->w_out == d->w_in && d->nz == 1 && a.C0 % bk == 0 && a.Ctot % bk == 0 &&
-                        ext_a < (1ll << 31) - (1 << 20) && ext_w < (1ll << 31) - (1 << 20) &&
+        const bool ok = !a_f32 && same3x3 && a.C0 % bk == 0 && a.Ctot % bk == 0 && fit31 &&
                         ((d->w_in <= tc.bm && tc.bm % d->w_in == 0 && (tc.bm / d->w_in) * (d->w_in + 2) <= tc.bm + tc.threads / 8) ||
                          (d->w_in > tc.bm && d->w_in % tc.bm == 0));
         MF_CHECK_ARG(ok, "mf_gemm_conv: tile %d (dx-tap reuse) does not apply to this call", tile);
@@ -506,28 +471,21 @@ extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
     a.kt_per_split = cdiv(a.nkt, a.splitk);
     if (tc.dxr) a.kt_per_split = (a.kt_per_split + 2) / 3 * 3;       // whole (ky, chunk) groups of three taps
     a.splitk = cdiv(a.nkt, a.kt_per_split);   // no empty splits
-    a.ws = d->ws;
     MF_CHECK_ARG(a.splitk == 1 || (a.ws != nullptr && (int64_t)a.splitk * a.nz * a.M * a.N <= d->ws_floats),
                  "mf_gemm_conv: split-K=%d needs a workspace of %lld floats", a.splitk,
                  (long long)a.splitk * a.nz * a.M * a.N);
     // in-launch combine: one ticket per output tile; a grid with more tiles than tickets keeps the reduce launch
     a.sk_tickets = (a.splitk > 1 && d->sk_tickets != nullptr && tiles_mn <= (int64_t)d->sk_ticket_cap &&
                     tile_has_skf(tile, d->dtype, d->w_split, a_f32)) ? (unsigned*)d->sk_tickets : nullptr;
-    {   // fast staging: every K tile inside one (tap, segment) and every operand addressable with 31-bit offsets
-        const int64_t npix = (int64_t)d->batch * d->h_in * d->w_in;
-        const int64_t ext_a = (npix - 1) * (int64_t)(a.ld0b > a.ld1b ? a.ld0b : a.ld1b) + (int64_t)a.Ctot * aes;
-        const int64_t ext_w = ((int64_t)(a.N - 1) * a.ldw + a.K) * es;
-        a.fast = (a.C0 % bk == 0) && (a.Ctot % bk == 0) && ext_a < (1ll << 31) - (1 << 20) && ext_w < (1ll << 31) - (1 << 20);
-    }
+    // fast staging: every K tile inside one (tap, segment) and every operand addressable with 31-bit offsets
+    a.fast = (a.C0 % bk == 0) && (a.Ctot % bk == 0) && fit31;
     MF_CHECK_ARG(d->act != MF_ACT_GEGLU4 || a.vec_ok, "mf_gemm_conv: GEGLU epilogue needs 16-byte aligned bias/out");
     a.pointwise = d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad_t == 0 && d->pad_l == 0 && !d->upsample && d->h_out == d->h_in &&
                   d->w_out == d->w_in;
     a.tiles_n = cdiv(a.N, tc.bn);
     a.tiles_m = cdiv(a.M, tc.bm);
-    {   // division-free prologue: shifts for the power-of-two extents, a magic multiplier for the dx-reuse window pitch
-        const int weff = a.Wo < tc.bm ? a.Wo : tc.bm;
-        a.wfr_magic = (unsigned)((1u << 20) / (unsigned)(weff + 2)) + 1u;
-    }
+    // division-free prologue: shifts for the power-of-two extents (above), a magic multiplier for the dx-reuse window pitch
+    a.wfr_magic = (unsigned)((1u << 20) / (unsigned)((a.Wo < tc.bm ? a.Wo : tc.bm) + 2)) + 1u;
     {   // staged epilogue rows (GemmArgs::epb): warp-specialised tiles, the vector epilogue, per-column bias, no split-K slabs;
         // a time embedding needs Ho * Wo a power of two and the tile's images inside the rows the tile reserves
         static const bool off = getenv("MFHIP_NO_EPB") != nullptr;          // A/B switch
@@ -547,8 +505,7 @@ extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
     const int64_t nblk = (int64_t)a.tiles_m * a.tiles_n * a.splitk;
     MF_CHECK_ARG(nblk < (1ll << 31) && a.nz < 65536, "mf_gemm_conv: grid too large");
     a.nblk = (int)nblk;
-    a.ord_mfast = 0;
-    a.ord_pw = a.tiles_n;
+    a.ord_pw = a.tiles_n;      // (ord_mfast = 0)
     // wide 1x1 GEMMs (FF projections, N = 2560 ... 10240): panels of 8 column tiles, so the ~64 tiles an XCD runs at once
     // are 8 x 8 and the panel's W stays in its L2 (tools/bench_order.py: 8192 x 5120 x 640 101 -> 93 us, 2048 x 10240 x
     // 1280 85 -> 82 us, 16384 x 5120 x 640 197 -> 185 us, fetch 426 -> ~115 MB; the 3x3 convs do not care: their W
@@ -567,96 +524,148 @@ extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
     }
     { static const bool off = getenv("MFHIP_NO_RES_PRE") != nullptr; a.dbg_no_res_pre = off; }     // A/B switch
     { static const int e = getenv("MFHIP_DBG_EPI") ? atoi(getenv("MFHIP_DBG_EPI")) : 0; a.dbg_epi = e; }
-    if (tile == kNloopTile) {
-        const bool ok = mf_is16(d->dtype) && !a_f32 && a.pointwise && d->c1 == 0 && a.nz == 1 && a.splitk == 1 && a.M % 64 == 0 && a.N % 160 == 0 &&
-                        a.K % 64 == 0 && a.nkt >= 2 && a.vec_ok && a.bias_mode == 0 && !a.temb && !a.vt_out && !a.rs && !a.cs && a.fast &&
-                        (int64_t)a.M * a.ld0b < (1ll << 31) - (1 << 20);
+    if (tile == kNloopTile || tile == kPersTile) {
+        // the persistent 1x1 GEMMs: a block walks a range of 160-column output tiles of its rows, the epilogue of every tile but
+        // its last under the next main loop.  Tile 70 also takes one 16-bit residual and transposed columns, and no fp32 output
+        const bool pers = tile == kPersTile;
+        const bool ok = mf_is16(d->dtype) && !a_f32 && a.pointwise && d->c1 == 0 && a.nz == 1 && a.splitk == 1 && a.M % tc.bm == 0 && a.N % 160 == 0 &&
+                        a.K % 64 == 0 && a.nkt >= 2 && a.vec_ok && a.bias_mode == 0 && !a.temb && !a.rs && !a.cs && a.fast &&
+                        (int64_t)a.M * a.ld0b < (1ll << 31) - (1 << 20) &&
+                        (pers ? !a.res1 && (!a.res0 || a.res0_dt != MF_F32) && a.out_dt != MF_F32 &&
+                                    (!a.vt_out || (a.vt_n0 % 160 == 0 && a.vt_tokens % 8 == 0 && a.act == MF_ACT_NONE && !a.res0))
+                              : !a.vt_out);
+        MF_CHECK_ARG(ok || !pers, "mf_gemm_conv: tile %d (persistent 128-row GEMM) takes a 1x1 bf16 / fp16 call with M %% 128 == 0, N %% 160 == 0, K %% 64 == 0, "
+                                  "K >= 128, one A segment, 16-bit output (and residual), per-column bias, one residual at most, no time embedding / scales / transposed columns / split-K", tile);
         MF_CHECK_ARG(ok, "mf_gemm_conv: tile %d (persistent short-K GEMM) takes a 1x1 bf16 / fp16 call with M %% 64 == 0, N %% 160 == 0, K %% 64 == 0, "
                          "K >= 128, one A segment, per-column bias, no time embedding / scales / transposed columns / split-K", tile);
-        // column ranges per row tile: enough blocks for the chip, as many output tiles per block as that leaves
-        static const int forced = getenv("MFHIP_NLOOP_RANGES") ? atoi(getenv("MFHIP_NLOOP_RANGES")) : 0;      // developer sweep
-        int ranges = 1;
-        while (a.tiles_m * ranges < 256 && a.tiles_n % (ranges * 2) == 0) ranges *= 2;
-        if (forced > 0 && a.tiles_n % forced == 0) ranges = forced;
-        a.nloop = a.tiles_n / ranges;
-        MF_CHECK_ARG(launch_nloop(d->dtype, a, (hipStream_t)stream), "mf_gemm_conv: tile %d is not instantiated for dtype %d", tile, d->dtype);
-        MF_CHECK_LAUNCH("mf_gemm_conv(nloop)");
-        if (d->gn_part) return gn_fallback((hipStream_t)stream);
+        static const int forced_pers = getenv("MFHIP_PERS_RANGES") ? atoi(getenv("MFHIP_PERS_RANGES")) : 0;        // developer sweeps
+        static const int forced_nloop = getenv("MFHIP_NLOOP_RANGES") ? atoi(getenv("MFHIP_NLOOP_RANGES")) : 0;
+        a.nloop = a.tiles_n / column_ranges(a.tiles_m, a.tiles_n, pers ? forced_pers : forced_nloop);
+        plan->family = pers ? kPers : kNloop;
+        plan->grid = dim3((unsigned)(a.tiles_m * (a.tiles_n / a.nloop)));
         return MF_OK;
     }
     // statistics in the epilogue: the final values of a block's rows are in its LDS slabs; one image per block of rows
-    const bool gn_fused = d->gn_part != nullptr && a.splitk == 1 && a.vec_ok && gn_hw % tc.bm == 0 && a.M % tc.bm == 0;
-    a.gn_part = gn_fused ? (float2*)d->gn_part : nullptr;
-    // per-group sums too: the consumer's groups are whole inside a tile's columns (and the LDS of the smallest tiles has room for
-    // one more row of column totals: (WAVES_M + 1) * BN float pairs)
-    bool gn_grouped = false;
-    if (gn_fused && d->gn_groups > 0 && a.N % d->gn_groups == 0) {
-        const int cpg = a.N / d->gn_groups;
-        gn_grouped = tc.bn % cpg == 0 && tc.bm >= 64 && (int64_t)2 * (a.N + d->gn_groups) * (a.M / tc.bm) <= d->gn_part_floats;
-        if (gn_grouped) { a.gn_grp = a.gn_part + (int64_t)a.N * (a.M / tc.bm); a.gn_cpg = cpg; }
+    if (d->gn_part != nullptr && a.splitk == 1 && a.vec_ok && gn_hw % tc.bm == 0 && a.M % tc.bm == 0) {
+        plan->gn = kGnFused;
+        plan->gn_rows = tc.bm;
+        a.gn_part = (float2*)d->gn_part;
+        // per-group sums too: the consumer's groups are whole inside a tile's columns (and the LDS of the smallest tiles has room for
+        // one more row of column totals: (WAVES_M + 1) * BN float pairs)
+        if (d->gn_groups > 0 && a.N % d->gn_groups == 0) {
+            const int cpg = a.N / d->gn_groups;
+            plan->gn_grouped = tc.bn % cpg == 0 && tc.bm >= 64 && (int64_t)2 * (a.N + d->gn_groups) * (a.M / tc.bm) <= d->gn_part_floats;
+            if (plan->gn_grouped) { a.gn_grp = a.gn_part + (int64_t)a.N * (a.M / tc.bm); a.gn_cpg = cpg; }
+        }
     }
-    if (d->gn_grouped) *d->gn_grouped = gn_grouped ? 1 : 0;
-    if (tile == kPersTile) {
-        const bool ok = mf_is16(d->dtype) && !a_f32 && a.pointwise && d->c1 == 0 && a.nz == 1 && a.splitk == 1 && a.M % 128 == 0 && a.N % 160 == 0 &&
-                        a.K % 64 == 0 && a.nkt >= 2 && a.vec_ok && a.bias_mode == 0 && !a.temb && !a.rs && !a.cs && a.fast && !a.res1 && (!a.res0 || a.res0_dt != MF_F32) && a.out_dt != MF_F32 &&
-                        (!a.vt_out || (a.vt_n0 % 160 == 0 && a.vt_tokens % 8 == 0 && a.act == MF_ACT_NONE && !a.res0)) &&
-                        (int64_t)a.M * a.ld0b < (1ll << 31) - (1 << 20);
-        MF_CHECK_ARG(ok, "mf_gemm_conv: tile %d (persistent 128-row GEMM) takes a 1x1 bf16 / fp16 call with M %% 128 == 0, N %% 160 == 0, K %% 64 == 0, "
-                         "K >= 128, one A segment, 16-bit output (and residual), per-column bias, one residual at most, no time embedding / scales / transposed columns / split-K", tile);
-        // column ranges per row tile: enough blocks for the chip (one block per CU: the kernel takes all of its LDS), as many
-        // output tiles per block as that leaves — the epilogue of every tile but a block's last runs under the next main loop
-        static const int forced = getenv("MFHIP_PERS_RANGES") ? atoi(getenv("MFHIP_PERS_RANGES")) : 0;        // developer sweep
-        int ranges = 1;
-        while (a.tiles_m * ranges < 256 && a.tiles_n % (ranges * 2) == 0) ranges *= 2;
-        if (forced > 0 && a.tiles_n % forced == 0) ranges = forced;
-        a.nloop = a.tiles_n / ranges;
-        MF_CHECK_ARG(launch_pers(d->dtype, a, (hipStream_t)stream), "mf_gemm_conv: tile %d is not instantiated for dtype %d", tile, d->dtype);
-        MF_CHECK_LAUNCH("mf_gemm_conv(pers)");
-        if (d->gn_part) return gn_fallback((hipStream_t)stream);
-        return MF_OK;
-    }
-    dim3 grid((unsigned)nblk, 1, (unsigned)a.nz);
-    hipStream_t s = (hipStream_t)stream;
-    bool launched;
-    if (d->dtype == MF_FP8) launched = launch_fp8(tile, a, grid, s);
-    else if (d->dtype == MF_BF16X1) launched = launch_bf16x1(tile, a, grid, s);
-    else if (d->dtype == MF_F16X3) launched = (d->w_split && tile >= 37) ? launch_f16x3_ws(tile, a, grid, s) : launch_f16x3(tile, a, grid, s, d->w_split != 0);
-    else if (d->dtype == MF_BF16X3) launched = launch_bf16x3(tile, a, grid, s, d->w_split != 0);
-    else if (d->dtype == MF_F16) {
-        launched = tile <= 6    ? launch_f16_a(tile, a, grid, s, false)
-                   : tile <= 24 ? launch_f16_b(tile, a, grid, s)
-                   : (tile <= 36 || !tile_ws(tile)) ? launch_f16_c(tile, a, grid, s)
-                   : tc.dxr     ? launch_f16_ws_dx(tile, a, grid, s)
-                                : launch_f16_ws_ring(tile, a, grid, s);
-    } else if (d->dtype == MF_BF16) {
-        launched = (a_f32 || tile <= 6) ? launch_bf16_a(tile, a, grid, s, a_f32)
-                   : tile <= 24         ? launch_bf16_b(tile, a, grid, s)
-                   : (tile <= 36 || !tile_ws(tile)) ? launch_bf16_c(tile, a, grid, s)
-                   : tc.dxr             ? launch_bf16_ws_dx(tile, a, grid, s)
-                                        : launch_bf16_ws_ring(tile, a, grid, s);
-    } else {
-        launched = tile <= 12 ? launch_f32_a(tile, a, grid, s) : launch_f32_b(tile, a, grid, s);
-    }
-    MF_CHECK_ARG(launched, "mf_gemm_conv: tile %d is not instantiated for dtype %d (w_split=%d)", tile, d->dtype, d->w_split);
-    MF_CHECK_LAUNCH("mf_gemm_conv");
-    if (d->deferred_splits) *d->deferred_splits = 0;
-    if (a.splitk > 1 && a.sk_tickets == nullptr && d->defer_reduce && d->deferred_splits && a.vec_ok && a.nz == 1 && !d->res0 && !d->res1 &&
+    plan->grid = dim3((unsigned)nblk, 1, (unsigned)a.nz);
+    plan->reduce_launch = a.splitk > 1 && a.sk_tickets == nullptr;
+    if (plan->reduce_launch && d->defer_reduce && d->deferred_splits && a.vec_ok && a.nz == 1 && !d->res0 && !d->res1 &&
         d->act == MF_ACT_NONE && !d->a_scale && !d->w_scale && d->bias_mode == 0 && !d->ln_colsum && !d->vt_out && !d->gn_part && d->ldc == d->n) {
-        // the consumer (mf_groupnorm, sk_ws) sums the slabs: no reduce launch, `out` stays unwritten
-        *d->deferred_splits = a.splitk;
-        return MF_OK;
+        plan->reduce_launch = false;          // the consumer (mf_groupnorm, sk_ws) sums the slabs: no reduce launch, `out` stays unwritten
+        plan->deferred_splits = a.splitk;
     }
-    if (a.splitk > 1 && a.sk_tickets == nullptr) {
+    return MF_OK;
+}
+
+// the implicit-GEMM template's instantiations, by precision and tile group (false: this tile is not instantiated for this precision)
+bool launch_tiled(const mf_gemm_desc* d, const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+    const int tile = p.tile, dxr = kTiles[tile - 1].dxr;
+    const dim3 grid = p.grid;
+    if (d->dtype == MF_FP8) return launch_fp8(tile, a, grid, s);
+    if (d->dtype == MF_BF16X1) return launch_bf16x1(tile, a, grid, s);
+    if (d->dtype == MF_F16X3) return (d->w_split && tile >= 37) ? launch_f16x3_ws(tile, a, grid, s) : launch_f16x3(tile, a, grid, s, d->w_split != 0);
+    if (d->dtype == MF_BF16X3) return launch_bf16x3(tile, a, grid, s, d->w_split != 0);
+    if (mf_is16(d->dtype)) {
+        const bool h = d->dtype == MF_F16;       // (a_f32: bf16 compute only)
+        if (p.a_f32 || tile <= 6) return h ? launch_f16_a(tile, a, grid, s, false) : launch_bf16_a(tile, a, grid, s, p.a_f32);
+        if (tile <= 24) return h ? launch_f16_b(tile, a, grid, s) : launch_bf16_b(tile, a, grid, s);
+        if (tile <= 36 || !tile_ws(tile)) return h ? launch_f16_c(tile, a, grid, s) : launch_bf16_c(tile, a, grid, s);
+        if (dxr) return h ? launch_f16_ws_dx(tile, a, grid, s) : launch_bf16_ws_dx(tile, a, grid, s);
+        return h ? launch_f16_ws_ring(tile, a, grid, s) : launch_bf16_ws_ring(tile, a, grid, s);
+    }
+    return tile <= 12 ? launch_f32_a(tile, a, grid, s) : launch_f32_b(tile, a, grid, s);
+}
+
+// Issues a plan: the main launch of its family, then one tail for all of them — the split-K reduce (unless the plan left it to the
+// consumer), the column-sum statistics, the three host out-ints.  The one refusal left to this side is a tile that is not instantiated
+// for the call's precision (the instantiation tables live with the kernels): it fires at the switch, so nothing has been launched.
+int gemm_launch(const GemmPlan& p, const mf_gemm_desc* d, hipStream_t s) {
+    GemmArgs a = p.a;
+    static unsigned* ovf = mf_ovf_flag_gemm();
+    a.ovf = ovf;
+#ifdef MF_STAMPS
+    a.stamps = g_stamps_host;
+#endif
+    bool launched = false;
+    const char* what = "mf_gemm_conv";
+    switch (p.family) {
+    case kHalo: launched = launch_halo_family(p.tile, a, p.grid, s); what = "mf_gemm_conv(halo)"; break;
+    case kNloop: launched = launch_nloop(d->dtype, a, s); what = "mf_gemm_conv(nloop)"; break;
+    case kPers: launched = launch_pers(d->dtype, a, s); what = "mf_gemm_conv(pers)"; break;
+    case kTiled: launched = launch_tiled(d, p, a, s); break;
+    }
+    MF_CHECK_ARG(launched, "mf_gemm_conv: tile %d is not instantiated for dtype %d (w_split=%d)", p.tile, d->dtype, d->w_split);
+    MF_CHECK_LAUNCH(what);
+    if (p.reduce_launch) {
         const int64_t total = (int64_t)a.M * a.N * a.nz / (a.vec_ok ? 8 : 1);
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        if (blocks < 1) blocks = 1;
+        const int blocks = total > 4096 * 256 ? 4096 : (int)((total + 255) / 256);        // (total >= 1)
         hipLaunchKernelGGL(d->dtype == MF_F16 ? splitk_reduce_kernel<true> : splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
         MF_CHECK_LAUNCH("mf_gemm_conv(split-K reduce)");
     }
-    if (d->gn_part) {
-        if (!gn_fused) return gn_fallback(s);
-        *d->gn_part_rows = tc.bm;
+    if (p.gn == kGnColsum) {       // over the stored output, after the launch(es) that wrote it
+        const dim3 g((unsigned)(a.M / p.gn_rows), (unsigned)cdiv(a.N, 256));
+        auto* sum8 = d->out_dtype == MF_F16 ? gn_colsum8_kernel<1> : d->out_dtype == MF_F32 ? gn_colsum8_kernel<2> : gn_colsum8_kernel<0>;
+        if ((mf_is16(d->out_dtype) || d->out_dtype == MF_F32) && d->ldc % 8 == 0 && mf_aligned16(d->out))
+            hipLaunchKernelGGL(sum8, g, dim3(256), 0, s, (const char*)d->out, d->ldc, a.M, a.N, p.gn_rows, (float2*)d->gn_part);
+        else hipLaunchKernelGGL(gn_colsum_kernel, g, dim3(256), 0, s, (const char*)d->out, d->out_dtype, d->ldc, a.M, a.N, p.gn_rows, (float2*)d->gn_part);
+        MF_CHECK_LAUNCH("mf_gemm_conv(gn_part column sums)");
     }
+    if (d->gn_part) *d->gn_part_rows = p.gn_rows;
+    if (d->gn_grouped) *d->gn_grouped = p.gn_grouped ? 1 : 0;
+    if (d->deferred_splits) *d->deferred_splits = p.deferred_splits;
     return MF_OK;
+}
+
+}  // namespace
+}  // namespace mfgemm
+using namespace mfgemm;
+
+unsigned* mf_ovf_flag_gemm() {
+    unsigned* p = nullptr;
+    (void)hipGetSymbolAddress((void**)&p, HIP_SYMBOL(g_split_ovf_gemm));
+    return p;
+}
+
+#ifdef MF_STAMPS
+extern "C" int mf_debug_set_stamps(void* ptr) {
+    g_stamps_host = (unsigned long long*)ptr;      // handed to every later launch in GemmArgs::stamps
+    return 0;
+}
+#endif
+
+extern "C" int mf_gemm_num_tiles(void) { return kNumTiles; }
+extern "C" int mf_gemm_tile_table_version(void) { return 1; }
+extern "C" int mf_gemm_tile_shape(int tile, int* bm, int* bn) {
+    if (tile < 1 || tile > kNumTiles) return MF_EINVAL;
+    *bm = kTiles[tile - 1].bm;
+    *bn = kTiles[tile - 1].bn;
+    return MF_OK;
+}
+
+extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
+    GemmPlan plan;
+    const int rc = gemm_plan(d, &plan);
+    return rc != MF_OK ? rc : gemm_launch(plan, d, (hipStream_t)stream);
+}
+
+extern "C" int mf_sizeof_gemm_plan(void) { return (int)sizeof(mf_gemm_plan); }
+extern "C" int mf_gemm_conv_plan(const mf_gemm_desc* d, mf_gemm_plan* out) {
+    MF_CHECK_ARG(out != nullptr, "mf_gemm_conv_plan: null plan");
+    GemmPlan p;
+    const int rc = gemm_plan(d, &p);
+    if (rc == MF_OK)
+        *out = mf_gemm_plan{p.tile, p.a.splitk, (p.family == kNloop || p.family == kPers) ? p.a.nloop : 1, (int32_t)(p.grid.x * p.grid.y * p.grid.z),
+                            p.reduce_launch, p.deferred_splits, p.gn_rows, p.gn_grouped};
+    return rc;
 }

@@ -1038,7 +1038,28 @@ void gn_launch_apply(const GnArgs& a, int vw, int u, dim3 grid, int nthr, hipStr
     hipLaunchKernelGGL(kern, grid, dim3(nthr), 0, s, a, rows_per_block);
 }
 
+// The one-launch slab form of mf_groupnorm, shape half: 8-channel vectors, slabs of sc = lcm(cpg, 8) channels x P rows of an image of at
+// most 4 P rows, at most 1024 threads and 64 KB of LDS per block.  (The alignment half is mf_groupnorm's.)
+struct GnSlab { int sc, nv, P, nthr; size_t smem; };
+bool gn_slab_shape(int hw, int c0, int c1, int groups, GnSlab* sl) {
+    const int C = c0 + c1;
+    if (hw < 1 || groups <= 0 || C % groups || c0 % 8 || c1 % 8) return false;
+    const int cpg = C / groups;
+    sl->sc = cpg;                                    // lcm(cpg, 8)
+    while (sl->sc % 8) sl->sc += cpg;
+    sl->nv = sl->sc / 8;
+    sl->P = hw < 64 ? hw : 64;     // (rows = 4; 32x32 with P 128, 8 rows, 128 blocks measured no faster: 17.3 vs 17.6 us)
+    sl->nthr = (sl->nv * sl->P + 63) / 64 * 64;
+    sl->smem = (size_t)sl->P * sl->sc * sizeof(float2);
+    return hw <= sl->P * 4 && C % sl->sc == 0 && sl->sc / cpg <= 8 && sl->nthr <= 1024 && sl->smem <= 64 * 1024;
+}
+
 }  // namespace
+
+extern "C" int mf_groupnorm_slab_applies(int32_t hw, int32_t channels, int32_t groups) {
+    GnSlab sl;
+    return gn_slab_shape(hw, channels, 0, groups, &sl) ? 1 : 0;
+}
 
 extern "C" int64_t mf_groupnorm_ws_floats(int32_t batch, int32_t groups, int32_t channels) {
     return (int64_t)batch * groups * GN_MAX_CHUNKS * 2 + (int64_t)batch * channels * 2;
@@ -1077,16 +1098,11 @@ extern "C" int mf_groupnorm(const mf_groupnorm_desc* d, void* stream) {
         // measured (tools/bench_gn.py, batch 8, us): 8x8 C 1280: 11.7 -> 5.0, 2560: 13.0 -> 6.0; 16x16 C 1280: 12.8 -> 8.1,
         // 2560: 17.4 -> 9.8
         static const bool two_pass = getenv("MFHIP_GN_2PASS") != nullptr;     // A/B switch: always the two-launch form
-        int sc = a.cpg;                                  // lcm(cpg, 8)
-        while (sc % 8) sc += a.cpg;
-        const int nv = sc / 8;
-        const int P = d->hw < 64 ? d->hw : 64, rows = 4;     // 32x32 (P 128, 8 rows, 128 blocks) measured no faster: 17.3 vs 17.6 us
-        const int nthr = (nv * P + 63) / 64 * 64;
-        const size_t smem = (size_t)P * sc * sizeof(float2);
+        GnSlab sl;
+        const bool shape_ok = gn_slab_shape(d->hw, d->c0, d->c1, d->groups, &sl);
         a.sk_ws = d->sk_ws; a.sk_splits = d->sk_splits; a.sk_bias = d->sk_bias; a.sk_temb = d->sk_temb; a.sk_ld_temb = d->sk_ld_temb;
         a.sk_alpha = d->sk_alpha; a.sk_mn = (int64_t)d->batch * d->hw * C;
-        const bool slab_ok = vw == 8 && d->hw <= P * rows && C % sc == 0 && sc / a.cpg <= 8 && nthr <= 1024 && smem <= 64 * 1024 &&
-                             mf_aligned16(d->gamma) && mf_aligned16(d->beta) && mf_aligned16(d->x0) && mf_aligned16(d->out) &&
+        const bool slab_ok = shape_ok && mf_aligned16(d->gamma) && mf_aligned16(d->beta) && mf_aligned16(d->x0) && mf_aligned16(d->out) &&
                              (!d->x1 || mf_aligned16(d->x1));
         if (d->sk_ws) {
             MF_CHECK_ARG(slab_ok && d->c1 == 0 && d->sk_splits >= 2 && d->stats_out == nullptr && mf_aligned16(d->sk_ws) &&
@@ -1096,7 +1112,7 @@ extern "C" int mf_groupnorm(const mf_groupnorm_desc* d, void* stream) {
         }
         if ((!two_pass || d->sk_ws) && slab_ok) {
             const bool known = gn_for_dtypes(d->in_dtype, d->out_dtype, [&](auto in_c, auto out_c) {
-                gn_launch_slab<decltype(in_c)::value, decltype(out_c)::value>(a, dim3(C / sc, d->batch), nthr, smem, s, sc, nv, P);
+                gn_launch_slab<decltype(in_c)::value, decltype(out_c)::value>(a, dim3(C / sl.sc, d->batch), sl.nthr, sl.smem, s, sl.sc, sl.nv, sl.P);
             });
             MF_CHECK_ARG(known, "mf_groupnorm: no kernel for in_dtype %d with out_dtype %d", d->in_dtype, d->out_dtype);
             MF_CHECK_LAUNCH("mf_groupnorm(slab)");

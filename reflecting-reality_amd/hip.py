@@ -59,6 +59,11 @@ class GemmDesc(C.Structure):
     ]
 
 
+class GemmPlan(C.Structure):
+    """mf_gemm_plan: what mf_gemm_conv would do with a descriptor (mf_gemm_conv_plan; decided on the host, nothing is launched)."""
+    _fields_ = [(f, C.c_int32) for f in "tile splitk tiles_per_block blocks reduce_launch deferred_splits gn_part_rows gn_grouped".split()]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [
         ("dtype", C.c_int32),
@@ -152,11 +157,12 @@ class SchedRow(C.Structure):
 # load() turns the table into argtypes / restype, so ctypes converts plain Python values and refuses the wrong ones before the library
 # is entered; program.py derives the recorder's signatures from it; tests/test_abi.py checks it against the header's prototypes in full.
 # A new entry is its prototype in mfhip.h and its line here.
-DESC_KINDS = {"G": GemmDesc, "N": GroupNormDesc, "A": AttnBwdDesc, "W": WgradDesc, "B": GroupNormBwdDesc}
+DESC_KINDS = {"G": GemmDesc, "P": GemmPlan, "N": GroupNormDesc, "A": AttnBwdDesc, "W": WgradDesc, "B": GroupNormBwdDesc}
 SIGNATURES = {
     "mf_abi_version": "i:", "mf_last_error": "s:", "mf_sizeof_gemm_desc": "i:", "mf_sizeof_groupnorm_desc": "i:",
-    "mf_gemm_conv": "i:Gp", "mf_gemm_num_tiles": "i:", "mf_gemm_tile_shape": "i:ipp", "mf_gemm_tile_table_version": "i:",
-    "mf_groupnorm": "i:Np", "mf_groupnorm_ws_floats": "l:iii", "mf_layernorm": "i:pipipplifp", "mf_softmax_rows": "i:ppiliip",
+    "mf_gemm_conv": "i:Gp", "mf_gemm_conv_plan": "i:GP", "mf_sizeof_gemm_plan": "i:", "mf_gemm_num_tiles": "i:", "mf_gemm_tile_shape": "i:ipp",
+    "mf_gemm_tile_table_version": "i:", "mf_groupnorm": "i:Np", "mf_groupnorm_ws_floats": "l:iii", "mf_groupnorm_slab_applies": "i:iii",
+    "mf_layernorm": "i:pipipplifp", "mf_softmax_rows": "i:ppiliip",
     "mf_attention_bf16": "i:plplplpliiiiifp", "mf_attention_f16": "i:plplplpliiiiifp",
     "mf_attention_f16x3": "i:pplpplpplpliiiiifp", "mf_attention_f16x3_lse": "i:pplpplpplplpiiiiifp", "mf_attention_causal_bf16": "i:plplplpliiiiifp",
     "mf_attention_causal_f16": "i:plplplpliiiiifp", "mf_attention_causal_f16x3": "i:pplpplpplpliiiiifp",
@@ -209,7 +215,7 @@ EXPORTS = list(SIGNATURES)
 # (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
 _LAYOUTS = ((GemmDesc, "mf_sizeof_gemm_desc"), (GroupNormDesc, "mf_sizeof_groupnorm_desc"), (AttnBwdDesc, "mf_sizeof_attn_bwd_desc"),
             (WgradDesc, "mf_sizeof_wgrad_desc"), (GroupNormBwdDesc, "mf_sizeof_groupnorm_bwd_desc"), (SchedRow, "mf_sizeof_sched_row"),
-            (MetricsRow, "mf_sizeof_metrics_row"))
+            (MetricsRow, "mf_sizeof_metrics_row"), (GemmPlan, "mf_sizeof_gemm_plan"))
 _CTYPES = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "s": C.c_char_p, "v": None,
            **{kind: C.POINTER(struct) for kind, struct in DESC_KINDS.items()}}
 
@@ -406,44 +412,32 @@ PERS_MIN_NLOOP = int(os.environ.get("MFHIP_PERS_MIN_NLOOP", "2"))
 
 def gn_slab_applies(hw: int, c: int, groups: int) -> bool:
     """Whether mf_groupnorm runs its one-launch form on [*, hw, c] in `groups` groups, one segment (csrc/norm.hip, the dispatch of
-    gn_slab_kernel) — the form a deferred split-K reduce needs (mf_groupnorm_desc.sk_ws)."""
-    if groups <= 0 or c % groups or c % 8:
-        return False
-    cpg = c // groups
-    sc = cpg
-    while sc % 8:
-        sc += cpg
-    p = hw if hw < 64 else 64
-    return hw <= 4 * p and c % sc == 0 and sc // cpg <= 8 and (sc // 8) * p <= 1024 and p * sc * 8 <= 64 * 1024
+    gn_slab_kernel) — the form a deferred split-K reduce needs (mf_groupnorm_desc.sk_ws).  The library's own predicate."""
+    return bool(load().mf_groupnorm_slab_applies(hw, c, groups))
 
 
-def _pers_applies(m, n, k, kh, kw, stride, pad_t, pad_l, upsample, h_in, h_out, w_in, w_out, c1, nz, temb, res0, res1, out, a0, bias_mode,
-                  a_scale, w_scale) -> bool:
-    """The call is one tile 70 serves (mf_gemm_conv's own check, gemm_conv.cpp kPersTile) AND its grid gives every block at least
-    PERS_MIN_NLOOP output tiles (the library's range choice: double the column ranges while there are fewer than 256 blocks)."""
-    if not (kh == 1 and kw == 1 and stride == 1 and pad_t == 0 and pad_l == 0 and not upsample and h_in == h_out and w_in == w_out):
-        return False
-    if c1 or nz != 1 or temb is not None or res1 is not None or bias_mode or a_scale is not None or w_scale is not None:
-        return False
-    if m % 128 or n % 160 or k % 64 or k < 128 or out.dtype not in (torch.bfloat16, torch.float16) or a0.dtype != out.dtype:
-        return False
-    if res0 is not None and res0.dtype != out.dtype:
-        return False
-    tiles_m, tiles_n, ranges = m // 128, n // 160, 1
-    while tiles_m * ranges < 256 and tiles_n % (ranges * 2) == 0:
-        ranges *= 2
-    return tiles_n // ranges >= PERS_MIN_NLOOP
+def _route_pers(d: GemmDesc) -> bool:
+    """Sends the call to the persistent tile 70 when the library's plan accepts it there (mf_gemm_conv_plan: nothing is launched) AND
+    its grid gives every block at least PERS_MIN_NLOOP output tiles; otherwise the descriptor's tile / split-K stay as they were."""
+    tile, splitk = d.tile, d.splitk
+    d.tile, d.splitk = PERS_TILE, 1
+    plan = GemmPlan()
+    if load().mf_gemm_conv_plan(C.byref(d), C.byref(plan)) == 0 and plan.tiles_per_block >= PERS_MIN_NLOOP:
+        return True
+    d.tile, d.splitk = tile, splitk
+    return False
 
 
 def pers_linear(m: int, n: int, k: int, dtype: torch.dtype) -> bool:
     """Would a plain Linear of this shape (16-bit, no time embedding, at most one residual) go to the persistent tile 70?  models.py asks
     before it picks a form only that tile serves well (a LayerNorm folded into the GEGLU projection)."""
-    if not PREFER_PERS or dtype not in (torch.bfloat16, torch.float16) or m % 128 or n % 160 or k % 64 or k < 128:
+    if not PREFER_PERS or dtype not in (torch.bfloat16, torch.float16):
         return False
-    tiles_m, tiles_n, ranges = m // 128, n // 160, 1
-    while tiles_m * ranges < 256 and tiles_n % (ranges * 2) == 0:
-        ranges *= 2
-    return tiles_n // ranges >= PERS_MIN_NLOOP
+    addr = 1 << 20        # a 16-byte aligned stand-in for a0 / w / out: a plan never reads through them
+    d = GemmDesc(a0=addr, w=addr, out=addr, c0=k, lda0=k, ldw=k, batch=m, h_in=1, w_in=1, h_out=1, w_out=1, kh=1, kw=1,
+                 stride=1, n=n, ldc=n, nz=1, zdiv=1, alpha=1.0)
+    d.dtype = d.a_dtype = d.out_dtype = dt_code(dtype)
+    return _route_pers(d)
 
 
 # GroupNorm statistics from the producing GEMM's epilogue (mf_gemm_desc.gn_part -> mf_groupnorm_desc.part0 / part1).  A/B switch.
@@ -684,16 +678,13 @@ def gemm_conv(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, dtype, w_
         d.vt_out, d.vt_n0, d.vt_tokens, d.vt_ld = _ptr(vt_out), vt_n0, vt_tokens, vt_out.shape[-1]
         fused |= 2
     tkey = None
-    use_pers = (PREFER_PERS and tile == 0 and splitk in (0, 1) and code in (MF_BF16, MF_F16) and not gn_part
-                and (vt_out is None or (vt_n0 % 160 == 0 and vt_tokens % 8 == 0 and res0 is None and act == ACT_NONE))
-                and _pers_applies(batch * h_out * w_out, n, kh * kw * (c0 + c1), kh, kw, stride, pad_t, pad_l, upsample, h_in, h_out, w_in, w_out, c1, nz,
-                                  temb, res0, res1, out, a0, bias_mode, a_scale, w_scale))
-    if use_pers:
-        # the persistent 128-row GEMM (tile 70) where a block walks two or more output tiles: the epilogue of every tile but the
-        # last runs under the next main loop (csrc/gemm_pers.hip; tools/bench_ff1.py for the per-shape table).  Not a tuner candidate
-        # for these calls: it wins them by 5-35 % in isolation and the step agrees (same-box A/B, profiles/r06_ab_switches.txt)
-        d.tile, d.splitk = PERS_TILE, 1
-    elif tile == 0 and splitk in (0, 1) and AUTOTUNE:
+    # the persistent 128-row GEMM (tile 70) where a block walks two or more output tiles: the epilogue of every tile but the
+    # last runs under the next main loop (csrc/gemm_pers.hip; tools/bench_ff1.py for the per-shape table).  Not a tuner candidate
+    # for these calls: it wins them by 5-35 % in isolation and the step agrees (same-box A/B, profiles/r06_ab_switches.txt).
+    # A cheap gate here; whether tile 70 serves the call is the library's answer (_route_pers)
+    use_pers = (PREFER_PERS and tile == 0 and splitk in (0, 1) and code in (MF_BF16, MF_F16) and not gn_part and kh == 1 and kw == 1
+                and _route_pers(d))
+    if tile == 0 and splitk in (0, 1) and AUTOTUNE and not use_pers:
         tkey = (code, d.a_dtype, batch * h_out * w_out, n, kh * kw * (c0 + c1), kh, stride, int(upsample), int(c1 > 0),
                 nz, int(splitk == 1) if not fused else 1, act, h_out, w_out) + ((w_split,) if code in (MF_F16X3, MF_BF16X3) else ()) \
             + ((("ln", "vt", "lnvt")[fused - 1],) if fused else ())

@@ -54,7 +54,8 @@ SIGNATURES_CALL["mf_axpby_n"] = "p" * _AXPBY_MAX + "f" * _AXPBY_MAX + "ipl"
 _ALL_SIGNATURES = {**SIGNATURES, **SIGNATURES_CALL}
 # queries / developer switches: forwarded, never recorded
 _PASS_THROUGH = ("mf_last_error", "mf_abi_version", "mf_gemm_num_tiles", "mf_gemm_tile_shape", "mf_gemm_tile_table_version",
-                 "mf_groupnorm_ws_floats", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc", "mf_sizeof_sched_row", "mf_minmax_ws_floats")
+                 "mf_groupnorm_ws_floats", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc", "mf_sizeof_sched_row", "mf_minmax_ws_floats",
+                 "mf_gemm_conv_plan", "mf_sizeof_gemm_plan", "mf_groupnorm_slab_applies")
 # descriptor fields that are HOST out-pointers (the library reports a choice through them): null in a program
 _HOST_FIELDS = {"gn_part_rows", "gn_grouped", "deferred_splits"}
 

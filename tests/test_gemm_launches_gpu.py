@@ -35,8 +35,9 @@ HOST_PTR_FIELDS = ("gn_part_rows", "gn_grouped", "deferred_splits")      # host 
 
 
 class Launch:
-    def __init__(self, d, rc, part_rows, grouped, deferred, tuner, ctx):
+    def __init__(self, d, rc, part_rows, grouped, deferred, tuner, ctx, key):
         self.d, self.rc, self.part_rows, self.grouped, self.deferred, self.tuner, self.ctx = d, rc, part_rows, grouped, deferred, tuner, ctx
+        self.key = key          # the tune key hip.gemm_conv looked up for this call; None: the tile was not the tuner's to choose
 
 
 def _host_int(addr):
@@ -60,8 +61,11 @@ class _LibProxy:
         d = hip.GemmDesc()
         C.memmove(C.addressof(d), C.addressof(src), C.sizeof(hip.GemmDesc))
         rc = self._lib.mf_gemm_conv(dref, stream)
+        tuner, key = self._state["tuner"] > 0, None
+        if not tuner and len(hip.KEY_LOG) > self._state["keys"]:
+            self._state["keys"], key = len(hip.KEY_LOG), hip.KEY_LOG[-1]
         self._log.append(Launch(d, rc, _host_int(src.gn_part_rows), _host_int(src.gn_grouped), _host_int(src.deferred_splits),
-                                self._state["tuner"] > 0, hip.TUNE_CTX))
+                                tuner, hip.TUNE_CTX, key))
         return rc
 
 
@@ -70,7 +74,7 @@ class trace_gemms:
     cache is held to the shipped file's entries and hip.KEY_LOG collects the tune keys looked up."""
 
     def __enter__(self):
-        self.launches, self.state = [], {"tuner": 0}
+        self.launches, self.state = [], {"tuner": 0, "keys": 0}
         lib = hip.load()
         self._saved = (hip._lib, hip._tune, hip._tuned_config, hip.KEY_LOG, hip._tune_misses)
         hip._tune = hip._tune_read(hip._TUNE_PATH, lib.mf_gemm_tile_table_version())
@@ -341,6 +345,26 @@ def run_precision(prec):
     return tr
 
 
+def plan_disagreements(x):
+    """mf_gemm_conv_plan on a recorded descriptor against what its launch reported through the host ints (the plan never reads them).
+    A launch on tile 70 gives every block hip.PERS_MIN_NLOOP output tiles or more — unless tile 70 was not hip.PREFER_PERS' choice but the
+    tuner's (the call looked up a tune key, so its tile is the cache's or a fresh measurement's).  Asserted for every tile-70 launch
+    alike, 6 of the bf16 step's 131 cases fail it with ONE tile per block: M8192 N640 K320; M8192 N640 K640 plain, with a residual and
+    with a folded LayerNorm; M2048 N1280 K1280 with a folded LayerNorm; M512 N10240 K1280 GEGLU.  The shipped tune cache holds tile 70
+    for them (measured the winner there), and they launched the same way before the plan existed."""
+    p = hip.GemmPlan()
+    if hip.load().mf_gemm_conv_plan(C.byref(x.d), C.byref(p)) != 0:
+        return [f"the plan refuses a call that launched: {hip.load().mf_last_error().decode()}"]
+    out = []
+    got, want = (p.gn_part_rows, p.gn_grouped, p.deferred_splits), (x.part_rows, x.grouped, x.deferred)
+    if got != want:
+        out.append(f"plan (gn_part_rows, gn_grouped, deferred_splits) {got} != launch {want}")
+    if x.d.tile == hip.PERS_TILE and p.tiles_per_block < hip.PERS_MIN_NLOOP:
+        if x.key is None:
+            out.append(f"routed to tile {hip.PERS_TILE} with {p.tiles_per_block} output tiles per block")
+    return out
+
+
 def audit(prec):
     t0 = time.time()
     tr = run_precision(prec)
@@ -360,6 +384,7 @@ def audit(prec):
         d = rec.d
         m, k = G.m_rows(d), G.k_depth(d)
         shape = f"M{m} N{d.n} K{k}"
+        fails += [f"case {i} {shape} tile {d.tile} sk {d.splitk} {features(d, rec)}: {msg}" for x in group for msg in plan_disagreements(x)]
         try:
             v, extra, nrows = replay(d, rec, 1000 + i, torch.device("cuda", 0))
         except (AssertionError, G.NotModelled, hip.MfhipError) as e:

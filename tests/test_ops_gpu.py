@@ -718,6 +718,51 @@ def test_persistent_short_k_gemm(prec_name, rows, c, n, mode, with_ln, ptile):
     assert d <= (2.0 ** -6 if prec_name == "bf16" else 2.0 ** -9) * max(1.0, ref.abs().max().item()), f"tile {ptile} vs tile 48: {d}"
 
 
+class _GemmSpy:
+    """The library handle with the (tile, return code) of every mf_gemm_conv call written down."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name != "mf_gemm_conv":
+            return fn
+
+        def call(dref, stream):
+            rc = fn(dref, stream)
+            self.calls.append((dref._obj.tile, rc))
+            return rc
+        return call
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_a_call_tile_70_cannot_serve_is_not_sent_there(dt, monkeypatch):
+    """128 x 960 x 128 goes to the persistent tile 70 (three output tiles per block) — unless its residual is a [128, 960] view of a
+    [128, 964] buffer: rows 1928 bytes apart are not 16-byte aligned, tile 70 has no scalar epilogue, and the library's plan says so
+    (mf_gemm_conv_plan).  The call then takes the tuned / heuristic path like any other instead of raising."""
+    monkeypatch.setattr(hip, "PREFER_PERS", True)
+    monkeypatch.setattr(hip, "PERS_MIN_NLOOP", 2)
+    monkeypatch.setattr(hip, "AUTOTUNE", False)
+    m, n, k = 128, 960, 128
+    g = torch.Generator().manual_seed(70)
+    rnd = lambda t: t.to(dt).double()      # noqa: E731
+    x, w, res = rnd(torch.randn(m, k, generator=g)), rnd(torch.randn(n, k, generator=g) / math.sqrt(k)), rnd(torch.randn(m, 964, generator=g))
+    b = torch.randn(n, generator=g)
+    xd, wd, bd, resd = x.to(DEV, dt), w.to(DEV, dt), b.to(DEV), res.to(DEV, dt)
+    ref = (x @ w.T + b.double() + res[:, :n]).float()
+    spy = _GemmSpy(hip.load())
+    monkeypatch.setattr(hip, "_lib", spy)
+    tol = (2e-2, 1e-2) if dt == torch.bfloat16 else (6e-3, 4e-3)
+    for res0, ld, want_pers in ((resd[:, :n], 964, False), (resd[:, :n].contiguous(), n, True)):
+        out = torch.empty(m, n, dtype=dt, device=DEV)
+        hip.gemm_conv(xd, wd, out, dtype=dt, c0=k, lda0=k, batch=m, h_in=1, w_in=1, h_out=1, w_out=1, n=n, bias=bd, res0=res0, ld_res0=ld)
+        (tile, rc), = spy.calls
+        spy.calls.clear()
+        assert rc == 0 and (tile == hip.PERS_TILE) == want_pers, (tile, rc, ld)
+        check(f"gemm_conv[{dt},ld_res0={ld},tile{tile}]", out, ref, *tol)
+
+
 def test_persistent_short_k_gemm_is_refused_where_it_cannot_run():
     prec = ops.Precision.get("bf16")
     lw = ops.ConvWeight(torch.randn(320, 320), None, prec, DEV)

@@ -23,7 +23,8 @@
  * Appended since (no struct changed, so the version stays 23): mf_u8_to_planes (uint8 NHWC pixels -> fp32 NCHW planes in [0, 1], the
  * ingest of a host that decoded an image file) and the step-level entries mf_encode_prompt / mf_build_conditioning / mf_decode_image,
  * which with mf_denoise_step_fused run a whole inpainting call from step programs: token ids, pixels, mask and depth in, a uint8
- * image out (examples/c_host/inpaint_host.c).
+ * image out (examples/c_host/inpaint_host.c); and the training batch (csrc/train_batch.hip): mf_train_example_u8, mf_masked_image_u8,
+ * mf_fliplr, mf_train_batch_assemble.
  */
 #ifndef MFHIP_H
 #define MFHIP_H
@@ -572,6 +573,45 @@ int mf_hwc_to_chw_affine(const float* x, float* y, int64_t hw, int32_t channels,
  * into three equal channels with .convert("RGB")). */
 int mf_u8_to_planes(const void* src_u8_nhwc, float* dst_nchw, int32_t batch, int32_t channels_in, int32_t channels_out, int64_t hw,
                     void* stream);
+
+/* ---- the training batch on the device (csrc/train_batch.hip; examples/brushnet/dataset/dataset.py:61-96, 216-221 and
+ * examples/brushnet/train_brushnet_mirror.py:1351-1449 minus the networks).  Appended to ABI 23; not part of step programs. ---------
+ * mf_train_example_u8: one read of a decoded sample's bytes — image uint8 [B][H][W][3], mask uint8 [B][H][W] — gives the three fp32
+ * NCHW tensors the dataset hands to the collate function:
+ *   pixel_values[b][c][y][x]              = f(image[b][y][xs][c])
+ *   conditioning_pixel_values[b][c][y][x] = f(mask[b][y][xs] == 255 ? 0 : image[b][y][xs][c])    (get_masked_image, invert=True)
+ *   masks[b][0][y][x]                     = (float)mask[b][y][xs] / 255.0f
+ * xs = flips && flips[b] ? W - 1 - x : x (np.fliplr; flips: int32 [B] in DEVICE memory, or NULL).  f(p) = ((float)p / 255.0f - 0.5f)
+ * / 0.5f when normalize (Resize + CenterCrop are the identity at H == W == resolution), (float)p / 255.0f when not (the [0, 1] planes
+ * mf_bicubic_aa_resize_crop takes with a = 2, b = -1).  The division is a true fp32 division, as in mf_u8_to_planes. */
+int mf_train_example_u8(const void* image_u8, const void* mask_u8, const int32_t* flips, float* pixel_values,
+                        float* conditioning_pixel_values, float* masks, int32_t batch, int32_t height, int32_t width, int32_t normalize,
+                        void* stream);
+/* HDF5Dataset.get_masked_image on uint8 pixels [pixels][channels] and a uint8 mask [pixels]: out = image with the pixels zeroed where
+ * mask == 255 (invert = 1, the dataset's default) or where mask == 0 (invert = 0).  out may be image. */
+int mf_masked_image_u8(const void* image_u8, const void* mask_u8, void* out_u8, int64_t pixels, int32_t channels, int32_t invert,
+                       void* stream);
+/* np.fliplr of fp32 [rows][width][channels] (channels 1 or 3: a depth or a normals map): dst[r][x][c] = src[r][width - 1 - x][c] */
+int mf_fliplr(const float* src, float* dst, int64_t rows, int32_t width, int32_t channels, void* stream);
+/* One launch from the VAE moments to everything the model call and the loss read.
+ * moments / posterior_noise: HOST arrays of nsrc (2 .. 4) DEVICE pointers — image, conditioning image, depth, normals (entries 2 and
+ * 3 may be null: that source is absent).  Moments are in mf_vae_sample's layout, NHWC [batch][h * w][ld] of m_dtype (MF_F32 / MF_BF16 /
+ * MF_F16), mean = ch 0..c-1, logvar = ch c..2c-1, ld >= 2c; each posterior noise is fp32 [batch][c][h * w].
+ * noise fp32 [batch][c][h * w]; timesteps int64 [batch] in DEVICE memory, clamped to [0, T) before the gather; sqrt_alpha,
+ * sqrt_one_minus_alpha and (optional) loss_weight: fp32 device tables of T entries.  masks [batch][1][plane_h][plane_w], optional
+ * depths [batch][1][..][..] and normals [batch][3][..][..]: full-resolution fp32 planes, resized with mf_nearest_resize's rule.
+ * Writes, fp32 NCHW: latents = (mean + std * posterior noise) * scaling of source 0 (mf_vae_sample's arithmetic); noisy_latents =
+ * sqrt_alpha[t] latents + sqrt_one_minus_alpha[t] noise (mf_axpby_n's arithmetic); target = noise (prediction_type 0, epsilon) or
+ * sqrt_alpha[t] noise - sqrt_one_minus_alpha[t] latents (1, v); conditioning_latents [batch][ctot][h][w] = source 1's latents (c
+ * channels), the mask (1), the depth plane (1) or source 2's latents (c), the normals planes (3) or source 3's latents (c), in that
+ * order; timesteps_f32 [batch]; loss_weights [batch] = loss_weight[t] (both NULL or both given).  A source and its plane exclude
+ * each other. */
+int mf_train_batch_assemble(const void* const* moments, const float* const* posterior_noise, int32_t nsrc, int32_t m_dtype, int64_t ld,
+                            int32_t c, int32_t batch, int32_t h, int32_t w, float scaling, const float* noise, const int64_t* timesteps,
+                            const float* sqrt_alpha, const float* sqrt_one_minus_alpha, const float* loss_weight, int32_t T,
+                            const float* masks, const float* depths, const float* normals, int32_t plane_h, int32_t plane_w,
+                            int32_t prediction_type, float* latents, float* noisy_latents, float* target, float* conditioning_latents,
+                            float* timesteps_f32, float* loss_weights, void* stream);
 
 /* ---- image scoring on the device (metrics/metrics.py:51-67,108-165: torchmetrics' peak_signal_noise_ratio and
  * structural_similarity_index_measure with their defaults, on the images taken as floats 0 .. 255) --------------------------------

@@ -24,6 +24,7 @@ _LAZY = {
     "BrushNetOutput": "models", "DDIMScheduler": "schedulers", "PNDMScheduler": "schedulers", "UniPCMultistepScheduler": "schedulers", "DDPMScheduler": "schedulers",
     "MirrorFusionModel": "training", "compute_snr": "training", "training_loss": "training", "train_step": "training",
     "AdamW": "training", "save_state": "training", "load_state": "training", "run_sharded": "inference",
+    "BatchFrontEnd": "training", "PreparedBatch": "training", "train_step_prepared": "training", "GraphedTrainStep": "training",
     "MfhipAttnProcessor": "attn_processor", "MfhipIPAttnProcessor": "attn_processor", "StableDiffusionBrushNetPipeline": "pipeline", "StableDiffusionXLBrushNetPipeline": "pipeline", "StableDiffusionPipelineOutput": "pipeline",
     "VaeImageProcessor": "pipeline", "Precision": "ops", "CLIPTextModel": "text_encoder", "CLIPTextModelWithProjection": "text_encoder",
     "CLIPVisionModel": "image_encoder", "CLIPVisionModelWithProjection": "image_encoder", "CLIPModel": "image_encoder",

@@ -6,6 +6,8 @@
 sort), then torchvision's Resize(resolution, BICUBIC) + CenterCrop as ONE bicubic kernel evaluated inside the crop window.
 `apply_transforms_normals` (:168-192, the map-valued modes): HWC -> CHW, the same resize / crop, Normalize([0.5], [0.5]).
 All on the GPU (csrc/frontend.hip), no host round trip.
+`apply_transforms_rgb` / `apply_transforms_mask` / `get_masked_image` (:61-96) and `training_example` — `__getitem__` (:233-271) minus the
+tokeniser, flip (:216-221) included: a decoded sample to the dataset's tensors, the uint8 bytes read once (csrc/train_batch.hip).
 
 Bicubic: the reference pins torchvision 0.18 (MirrorFusion/README.md:34), where transforms.Resize defaults to
 antialias=True and, for a tensor, hands it to torch.nn.functional.interpolate at EVERY scale (torchvision/transforms/
@@ -86,6 +88,137 @@ def apply_transforms_normals(normals_map, resolution: int = 512, mask=None, norm
     if (h, w) == (resolution, resolution):
         return hip.hwc_to_chw_affine(x, 2.0, -1.0)                                                   # Normalize([0.5], [0.5])
     return _resize_crop(hip.hwc_to_chw_affine(x, 1.0, 0.0), resolution, antialias, 2.0, -1.0)
+
+
+# ---- the rest of HDF5Dataset.__getitem__ (dataset.py:61-96, 205-271): a decoded sample -> the tensors of one training example -------------
+def _u8_host_checked(a, what: str, ndims: Sequence[int]):
+    """A uint8 array / tensor as a tensor WHERE IT LIES; its dtype and rank are checked before anything is uploaded."""
+    t = torch.as_tensor(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: a numpy array or a tensor, got {type(a).__name__}")
+    if t.dtype != torch.uint8:
+        raise ValueError(f"{what} must be uint8 (the decoded pixels), got {t.dtype}")
+    if t.dim() not in ndims:
+        raise ValueError(f"{what}: {' or '.join(str(n) for n in ndims)} dimensions, got shape {tuple(t.shape)}")
+    return t
+
+
+def _image_and_mask(image, mask):
+    """-> (image [B, H, W, 3], mask [B, H, W], batched) as uint8 tensors where they lie, shapes checked."""
+    img = _u8_host_checked(image, "image", (3, 4))
+    if img.shape[-1] != 3:
+        raise ValueError(f"image: [H, W, 3] or [B, H, W, 3], got shape {tuple(img.shape)}")
+    m = _u8_host_checked(mask, "mask", (img.dim() - 1, img.dim()))
+    if m.dim() == img.dim():
+        if m.shape[-1] != 1:
+            raise ValueError(f"mask: one channel, got shape {tuple(m.shape)}")
+        m = m[..., 0]
+    if tuple(m.shape) != tuple(img.shape[:-1]):
+        raise ValueError(f"mask shape {tuple(m.shape)} does not match the image's {tuple(img.shape[:-1])}")
+    batched = img.dim() == 4
+    return (img if batched else img[None]), (m if batched else m[None]), batched
+
+
+def _flip_flags(flip, batch: int) -> list:
+    flags = [bool(flip)] * batch if isinstance(flip, (bool, int, np.bool_)) else [bool(f) for f in flip]
+    if len(flags) != batch:
+        raise ValueError(f"flip: one flag per sample ({batch}), got {len(flags)}")
+    return flags
+
+
+def _flips_on_device(flags: list, device) -> Optional[torch.Tensor]:
+    """The int32 device flags mf_train_example_u8 reads, or None when no sample is flipped."""
+    return torch.tensor(flags, dtype=torch.int32).to(device) if any(flags) else None
+
+
+def _example_planes(img: torch.Tensor, m: torch.Tensor, flips: Optional[torch.Tensor], resolution: int, antialias: Optional[bool]):
+    """uint8 device image [B, H, W, 3] / mask [B, H, W] -> (pixel_values, conditioning_pixel_values, masks) at `resolution`: one launch
+    when the sample already has that size, else the [0, 1] planes of that launch through the bicubic resize + crop (2x - 1 on the images)."""
+    b, h, w, _ = img.shape
+    (nh, nw), (top, left) = _resize_geometry(h, w, resolution)
+    if (nh, nw) == (h, w) == (resolution, resolution):
+        return hip.train_example_u8(img, m, flips, normalize=True)
+    pix, cond, masks = hip.train_example_u8(img, m, flips, normalize=False)
+    rs = lambda t, a, c: hip.bicubic_resize_crop(t.reshape(-1, h, w), (nh, nw), (top, left), (resolution, resolution), a, c,
+                                                 antialias=antialias is not False).reshape(b, -1, resolution, resolution)
+    return rs(pix, 2.0, -1.0), rs(cond, 2.0, -1.0), rs(masks, 1.0, 0.0)
+
+
+def get_masked_image(image, mask, invert: bool = True, device="cuda") -> torch.Tensor:
+    """dataset.py:61-68 on the device: uint8 [H, W, 3] (or [B, H, W, 3]) in, uint8 out; the pixels where mask == 255 (invert, the dataset's
+    call) or mask == 0 are zeroed.  training_example does not need it (its kernel blackens while it converts): a helper for callers."""
+    img, m, batched = _image_and_mask(image, mask)
+    out = hip.masked_image_u8(img.to(device), m.to(device), invert)
+    return out if batched else out[0]
+
+
+def apply_transforms_rgb(image, resolution: int = 512, flip: bool = False, device="cuda", antialias: Optional[bool] = None) -> torch.Tensor:
+    """dataset.py:71-83: uint8 [H, W, 3] -> fp32 [3, resolution, resolution] = Normalize([0.5], [0.5])(CenterCrop(Resize(x / 255))).
+    `flip`: np.fliplr first (extract_data_from_hdf5, :219-221)."""
+    img = _u8_host_checked(image, "image", (3,))
+    if img.shape[-1] != 3:
+        raise ValueError(f"image: [H, W, 3], got shape {tuple(img.shape)}")
+    img = img.to(device)[None]
+    return _example_planes(img, torch.zeros(img.shape[:3], dtype=torch.uint8, device=img.device), _flips_on_device([bool(flip)], device),
+                           resolution, antialias)[0][0]
+
+
+def apply_transforms_mask(mask, resolution: int = 512, flip: bool = False, device="cuda", antialias: Optional[bool] = None) -> torch.Tensor:
+    """dataset.py:85-96: uint8 [H, W] -> fp32 [1, resolution, resolution] = CenterCrop(Resize(mask / 255)) (no Normalize)."""
+    m = _u8_host_checked(mask, "mask", (2,)).to(device)
+    planes = hip.u8_to_planes(m[None, :, :, None])[0]                                                # [1, H, W], a true division
+    if flip:
+        planes = hip.fliplr(planes, channels=1)
+    return _resize_crop(planes, resolution, antialias)
+
+
+def training_example(data: dict, resolution: int = 512, flip=False, depth: bool = False, normals_conditioning_mode: Optional[str] = None,
+                     device="cuda", antialias: Optional[bool] = None, **depth_kwargs) -> dict:
+    """HDF5Dataset.__getitem__ (dataset.py:233-271) minus `input_ids`, on the device: `data` is what extract_data_from_hdf5 returns
+    BEFORE its flip ("image" uint8 [H, W, 3], "mask" uint8 [H, W], and — when asked for — "depth" [H, W], "normals" [H, W, 3]); the
+    result holds "pixel_values" [3, R, R], "conditioning_pixel_values" [3, R, R] (the image blackened where mask == 255), "masks"
+    [1, R, R], "depths" [1, R, R] (depth=True) and "normals" ([3, R, R], or the [1, 3] mean mirror normal for 'ip_adapter') as fp32 device
+    tensors.  `flip` stands for the dataset's flip_horizontal: every map is read right to left.  Batched form: "image" [B, H, W, 3],
+    "mask" [B, H, W], "depth" / "normals" with a leading B, `flip` one flag per sample; the results get a leading B.  `depth_kwargs`
+    are apply_transforms_depth's (normalization_method, max_scene_depth, norm_range, delta).
+    Host Python by design, the caller's concern: reading the HDF5 / PNG file, tokenising the caption (`input_ids`),
+    `proportion_empty_prompts`, and the flip coin (`random.random() < 0.5`)."""
+    if "image" not in data or "mask" not in data:
+        raise ValueError("training_example: data needs 'image' and 'mask'")
+    img, m, batched = _image_and_mask(data["image"], data["mask"])
+    if normals_conditioning_mode not in (None, False, "concat", "latents", "ip_adapter"):
+        raise ValueError(f"normals_conditioning_mode {normals_conditioning_mode!r}: 'concat', 'latents' or 'ip_adapter'")
+    b = img.shape[0]
+    for key, want in (("depth", depth), ("normals", normals_conditioning_mode)):
+        if want and key not in data:
+            raise ValueError(f"training_example: data has no {key!r}")
+    flags = _flip_flags(flip, b)
+    img, m = img.to(device), m.to(device)
+    pix, cond, masks = _example_planes(img, m, _flips_on_device(flags, device), resolution, antialias)
+    out = {"pixel_values": pix, "conditioning_pixel_values": cond, "masks": masks}
+    per_sample = lambda a: a if batched else [a]
+    as_f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a).to(device, torch.float32).contiguous()
+    if depth or normals_conditioning_mode:
+        # the mirror mask at the sample's own size, flipped with it: what the dataset hands apply_transforms_depth / _normals
+        mask_f = hip.u8_to_planes(m[..., None])[:, 0]
+        mask_f = [hip.fliplr(mask_f[i], channels=1) if flags[i] else mask_f[i] for i in range(b)]
+    if depth:
+        ds = []
+        for i, d in enumerate(per_sample(data["depth"])):
+            d = as_f32(d)
+            ds.append(apply_transforms_depth(hip.fliplr(d, channels=1) if flags[i] else d, mask=mask_f[i], resolution=resolution,
+                                             device=device, antialias=antialias, **depth_kwargs))
+        out["depths"] = torch.stack(ds)
+    if normals_conditioning_mode:
+        ns = []
+        for i, n in enumerate(per_sample(data["normals"])):
+            n = as_f32(n)
+            n = hip.fliplr(n, channels=3) if flags[i] else n
+            ns.append(mean_normal_over_mask(n, mask_f[i], device=device) if normals_conditioning_mode == "ip_adapter"
+                      else apply_transforms_normals(n, resolution=resolution, normals_conditioning_mode=normals_conditioning_mode,
+                                                    device=device, antialias=antialias))
+        out["normals"] = torch.stack(ns)
+    return out if batched else {k: v[0] for k, v in out.items()}
 
 
 # ---- CLIPImageProcessor on the device (mf_clip_preprocess) -------------------------------------------------------------------------------

@@ -188,6 +188,9 @@ SIGNATURES = {
     "mf_depth_normalize": "i:ppplffipp", "mf_select_ws_bytes": "l:", "mf_select_ranks": "i:plpippp", "mf_depth_percentile_normalize": "i:pplpffippp",
     "mf_bicubic_resize_crop": "i:ppiiiiiiiiiffp", "mf_bicubic_aa_resize_crop": "i:ppiiiiiiiiiffp", "mf_hwc_to_chw_affine": "i:ppliffp",
     "mf_u8_to_planes": "i:ppiiilp",
+    # the training batch (csrc/train_batch.hip)
+    "mf_train_example_u8": "i:ppppppiiiip", "mf_masked_image_u8": "i:pppliip", "mf_fliplr": "i:ppliip",
+    "mf_train_batch_assemble": "i:ppiiliiiifpppppipppiiippppppp",
     # image scoring (csrc/metrics.hip)
     "mf_sizeof_metrics_row": "i:", "mf_image_metrics_ws_bytes": "l:iiii", "mf_image_metrics": "i:pppiiiiifppp",
     # CLIP image side and score (csrc/clip_vision.hip)
@@ -1552,6 +1555,127 @@ def u8_to_planes(src: torch.Tensor, channels_out: Optional[int] = None) -> torch
     out = torch.empty(b, co, h, w, dtype=torch.float32, device=src.device)
     _launch("mf_u8_to_planes", src, out, b, ci, co, h * w)
     return out
+
+
+# ---- the training batch (csrc/train_batch.hip) ---------------------------------------------------------------------------------
+def train_example_u8(image: torch.Tensor, mask: torch.Tensor, flips: Optional[torch.Tensor] = None, normalize: bool = True):
+    """uint8 image [B, H, W, 3] and mask [B, H, W] -> (pixel_values [B, 3, H, W], conditioning_pixel_values [B, 3, H, W], masks
+    [B, 1, H, W]) fp32 from ONE read of the bytes (mf_train_example_u8): x / 255 (a true division), the image blackened where the
+    mask is 255 for the conditioning, (v - 0.5) / 0.5 on both images when `normalize`.  `flips`: int32 [B] on the device (non-zero:
+    that sample is read right to left, np.fliplr) or None."""
+    _req_cuda(image, mask, flips)
+    if image.dtype != torch.uint8 or image.dim() != 4 or image.shape[-1] != 3:
+        raise MfhipError("train_example_u8: a uint8 [batch, height, width, 3] image")
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(image.shape[:3]):
+        raise MfhipError(f"train_example_u8: a uint8 mask of shape {tuple(image.shape[:3])}, got {mask.dtype} {tuple(mask.shape)}")
+    b, h, w, _ = image.shape
+    if flips is not None and (flips.dtype != torch.int32 or flips.numel() != b):
+        raise MfhipError("train_example_u8: flips is an int32 tensor with one flag per image")
+    f32 = dict(dtype=torch.float32, device=image.device)
+    pix, cond, m = torch.empty(b, 3, h, w, **f32), torch.empty(b, 3, h, w, **f32), torch.empty(b, 1, h, w, **f32)
+    _launch("mf_train_example_u8", image.contiguous(), mask.contiguous(), None if flips is None else flips.contiguous(), pix, cond, m,
+            b, h, w, int(bool(normalize)))
+    return pix, cond, m
+
+
+def masked_image_u8(image: torch.Tensor, mask: torch.Tensor, invert: bool = True) -> torch.Tensor:
+    """HDF5Dataset.get_masked_image on the device: uint8 image [.., H, W, C] with the pixels zeroed where the uint8 mask [.., H, W] is 255
+    (invert, the dataset's default) or 0 (mf_masked_image_u8)."""
+    _req_cuda(image, mask)
+    if image.dtype != torch.uint8 or mask.dtype != torch.uint8 or image.dim() < 3 or tuple(mask.shape) != tuple(image.shape[:-1]):
+        raise MfhipError("masked_image_u8: a uint8 [.., H, W, C] image and a uint8 [.., H, W] mask")
+    image, mask = image.contiguous(), mask.contiguous()
+    out = torch.empty_like(image)
+    _launch("mf_masked_image_u8", image, mask, out, mask.numel(), image.shape[-1], int(bool(invert)))
+    return out
+
+
+def fliplr(x: torch.Tensor, channels: Optional[int] = None) -> torch.Tensor:
+    """np.fliplr of an fp32 map (mf_fliplr): [H, W, 3] (channels = 3, the default for a last dimension of 3 behind two others) or
+    [H, W] / planes [.., H, W] (channels = 1): the width axis is reversed, leading dimensions count as rows."""
+    _req_cuda(x)
+    if x.dtype != torch.float32 or x.dim() < 2:
+        raise MfhipError("fliplr: an fp32 [H, W] or [H, W, 3] map")
+    c = (3 if x.dim() >= 3 and x.shape[-1] == 3 else 1) if channels is None else int(channels)
+    if c not in (1, 3) or (c == 3 and (x.dim() < 3 or x.shape[-1] != 3)):
+        raise MfhipError("fliplr: channels is 1, or 3 for an [.., W, 3] tensor")
+    x = x.contiguous()
+    w = x.shape[-2] if c == 3 else x.shape[-1]
+    out = torch.empty_like(x)
+    _launch("mf_fliplr", x, out, x.numel() // (w * c), w, c)
+    return out
+
+
+ASSEMBLE_OUTPUTS = ("latents", "noisy_latents", "target", "conditioning_latents", "timesteps_f32", "loss_weights")
+
+
+def train_batch_assemble(moments, posterior_noise, c: int, scaling: float, noise: torch.Tensor, timesteps: torch.Tensor,
+                         sqrt_alpha: torch.Tensor, sqrt_one_minus_alpha: torch.Tensor, masks: torch.Tensor,
+                         depths: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+                         loss_weight: Optional[torch.Tensor] = None, v_prediction: bool = False, out: Optional[dict] = None) -> dict:
+    """train_brushnet_mirror.py:1351-1449 minus the networks in one launch (mf_train_batch_assemble; include/mfhip.h has the contract).
+    moments: 2 .. 4 NHWC [B, h, w, ld] tensors (image, conditioning image, depth, normals; the last two may be None), posterior_noise
+    their fp32 [B, c, h, w] draws.  timesteps: int64 [B]; a DEVICE tensor is trusted (the kernel clamps it to the tables, it cannot be
+    range-checked without a synchronise), a host tensor is range-checked here and uploaded.  sqrt_alpha / sqrt_one_minus_alpha /
+    loss_weight: fp32 device tables.  masks / depths / normals: full-resolution fp32 planes [B, 1 | 1 | 3, R, R'].  `out`: tensors to
+    write into, by name (ASSEMBLE_OUTPUTS); the rest are allocated.  Returns the dict of outputs ('loss_weights' only with a table)."""
+    moments, posterior_noise = list(moments), list(posterior_noise)
+    n = len(moments)
+    if not 2 <= n <= 4 or len(posterior_noise) != n:
+        raise MfhipError(f"train_batch_assemble: 2 .. 4 moment tensors with one posterior noise each, got {n} and {len(posterior_noise)}")
+    _req_cuda(*moments, *posterior_noise, noise, sqrt_alpha, sqrt_one_minus_alpha, loss_weight, masks, depths, normals)
+    if moments[0] is None or moments[1] is None:
+        raise MfhipError("train_batch_assemble: the image's and the conditioning image's moments are required")
+    b, h, w, ld = moments[0].shape
+    dev, dt = moments[0].device, moments[0].dtype
+    for m, pn in zip(moments, posterior_noise):
+        if (m is None) != (pn is None):
+            raise MfhipError("train_batch_assemble: a source is its moments and its posterior noise")
+        if m is None:
+            continue
+        if tuple(m.shape) != (b, h, w, ld) or m.dtype != dt or not m.is_contiguous():
+            raise MfhipError(f"train_batch_assemble: every moment tensor must be contiguous {dt} [{b}, {h}, {w}, {ld}], got {m.dtype} {tuple(m.shape)}")
+        if tuple(pn.shape) != (b, c, h, w) or pn.dtype != torch.float32 or not pn.is_contiguous():
+            raise MfhipError(f"train_batch_assemble: posterior noise must be contiguous fp32 [{b}, {c}, {h}, {w}], got {pn.dtype} {tuple(pn.shape)}")
+    if tuple(noise.shape) != (b, c, h, w) or noise.dtype != torch.float32 or not noise.is_contiguous():
+        raise MfhipError(f"train_batch_assemble: noise must be contiguous fp32 [{b}, {c}, {h}, {w}]")
+    t_len = sqrt_alpha.numel()
+    for tab in (sqrt_alpha, sqrt_one_minus_alpha, loss_weight):
+        if tab is not None and (tab.dtype != torch.float32 or tab.numel() != t_len or not tab.is_contiguous()):
+            raise MfhipError("train_batch_assemble: the schedule tables are contiguous fp32 tensors of one length")
+    if timesteps.dtype != torch.int64 or timesteps.numel() != b:
+        raise MfhipError(f"train_batch_assemble: timesteps is an int64 tensor of {b} entries")
+    if not timesteps.is_cuda:
+        if int(timesteps.min()) < 0 or int(timesteps.max()) >= t_len:
+            raise MfhipError(f"train_batch_assemble: timesteps outside [0, {t_len})")
+        timesteps = timesteps.to(dev)
+    timesteps = timesteps.contiguous()
+    ph, pw = masks.shape[-2:]
+    for name, pl, ch in (("masks", masks, 1), ("depths", depths, 1), ("normals", normals, 3)):
+        if pl is not None and (tuple(pl.shape) != (b, ch, ph, pw) or pl.dtype != torch.float32 or not pl.is_contiguous()):
+            raise MfhipError(f"train_batch_assemble: {name} must be contiguous fp32 [{b}, {ch}, {ph}, {pw}], got {pl.dtype} {tuple(pl.shape)}")
+    if (depths is not None and n > 2 and moments[2] is not None) or (normals is not None and n > 3 and moments[3] is not None):
+        raise MfhipError("train_batch_assemble: depth / normals come as latents or as planes, not both")
+    nlat = sum(1 for m in moments[2:] if m is not None)
+    ctot = c + 1 + nlat * c + (1 if depths is not None else 0) + (3 if normals is not None else 0)
+    shapes = {"latents": (b, c, h, w), "noisy_latents": (b, c, h, w), "target": (b, c, h, w), "conditioning_latents": (b, ctot, h, w),
+              "timesteps_f32": (b,), "loss_weights": (b,)}
+    res = {}
+    for name in ASSEMBLE_OUTPUTS:
+        if name == "loss_weights" and loss_weight is None:
+            continue
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shapes[name], dtype=torch.float32, device=dev)
+        elif not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shapes[name] or not t.is_contiguous():
+            raise MfhipError(f"train_batch_assemble: out[{name!r}] must be a contiguous fp32 device tensor of shape {shapes[name]}")
+        res[name] = t
+    arr = (C.c_void_p * n)(*[_ptr(m) for m in moments])
+    pna = (C.c_void_p * n)(*[_ptr(p) for p in posterior_noise])
+    _launch("mf_train_batch_assemble", arr, pna, n, dt_code(dt), ld, c, b, h, w, float(scaling), noise, timesteps, sqrt_alpha,
+            sqrt_one_minus_alpha, loss_weight, t_len, masks, depths, normals, ph, pw, int(bool(v_prediction)), res["latents"],
+            res["noisy_latents"], res["target"], res["conditioning_latents"], res["timesteps_f32"], res.get("loss_weights"))
+    return res
 
 
 def postprocess(x: torch.Tensor, denormalize: bool = True, uint8: bool = False) -> torch.Tensor:

@@ -1584,6 +1584,11 @@ class DiagonalGaussianDistribution:
     def parameters(self) -> torch.Tensor:
         return hip.unpack_nchw(self._m, 2 * self._c)
 
+    @property
+    def moments_nhwc(self) -> torch.Tensor:
+        """The moments where the encoder left them: NHWC [B, h, w, ld >= 2c] (what mf_vae_sample / mf_train_batch_assemble read)."""
+        return self._m
+
     def sample(self, generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         b, h, w, _ = self._m.shape
         if noise is None:

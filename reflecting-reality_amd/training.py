@@ -11,7 +11,12 @@ Forward and backward run on the libmfhip kernels: the backward pass is a tape of
 (one launch of mf_adamw per model, one mf_sumsq for the norm; the clip coefficient never leaves the device); with more
 than one rank the gradient arena is all-reduced in buckets over RCCL while the backward pass is still running
 (distributed.GradBuckets).
+
+`BatchFrontEnd` covers the lines between the data loader and the model call (:1347-1449 minus the networks' forward) on the device: a
+collated batch of pixels becomes a `PreparedBatch` with one launch after the VAE encodes, `train_step_prepared` steps from it, and
+`GraphedTrainStep(front_end=...).from_pixels` replays encodes + assemble + step from one graph.
 """
+import dataclasses
 import json
 import os
 import shutil
@@ -21,8 +26,8 @@ import torch
 
 from . import autograd, hip, ops
 
-__all__ = ["MirrorFusionModel", "compute_snr", "training_loss", "AdamW", "clip_grad_norm_", "train_step", "save_state",
-           "load_state"]
+__all__ = ["MirrorFusionModel", "compute_snr", "min_snr_weights", "training_loss", "AdamW", "clip_grad_norm_", "train_step",
+           "PreparedBatch", "EncodedBatch", "BatchFrontEnd", "train_step_prepared", "GraphedTrainStep", "save_state", "load_state"]
 
 
 class MirrorFusionModel:
@@ -73,6 +78,13 @@ def compute_snr(noise_scheduler, timesteps: torch.Tensor) -> torch.Tensor:
     return (alpha / sigma) ** 2
 
 
+def min_snr_weights(noise_scheduler, timesteps: torch.Tensor, snr_gamma: float) -> torch.Tensor:
+    """train_brushnet_mirror.py:1437-1449: min(snr, gamma) / snr (epsilon) or / (snr + 1) (v_prediction), one host value per timestep."""
+    snr = compute_snr(noise_scheduler, timesteps)
+    weights = torch.stack([snr, snr_gamma * torch.ones_like(snr)], dim=1).min(dim=1)[0]
+    return weights / snr if noise_scheduler.config["prediction_type"] == "epsilon" else weights / (snr + 1)
+
+
 def training_loss(model: MirrorFusionModel, noise_scheduler, latents: torch.Tensor, noise: torch.Tensor,
                   timesteps: torch.Tensor, encoder_hidden_states: torch.Tensor, conditioning_latents: torch.Tensor,
                   snr_gamma: Optional[float] = None, _return_weights: bool = False):
@@ -90,10 +102,7 @@ def training_loss(model: MirrorFusionModel, noise_scheduler, latents: torch.Tens
         raise ValueError(f"Unknown prediction type {ptype}")
     weights = None
     if snr_gamma is not None:                                                                        # :1437-1449
-        snr = compute_snr(noise_scheduler, timesteps)
-        weights = torch.stack([snr, snr_gamma * torch.ones_like(snr)], dim=1).min(dim=1)[0]
-        weights = weights / snr if ptype == "epsilon" else weights / (snr + 1)
-        weights = hip.h2d(weights.float().contiguous(), pred.device)
+        weights = hip.h2d(min_snr_weights(noise_scheduler, timesteps, snr_gamma).float().contiguous(), pred.device)
     loss, _ = hip.mse_loss(pred.float(), target.float(), weights)
     if _return_weights:
         return loss, pred, target, weights
@@ -208,6 +217,17 @@ def train_step(model: MirrorFusionModel, noise_scheduler, optimizer: AdamW, late
     schedule and zeroes the arena — the other calls return (loss, None).
     `lr_scheduler`: an optimization.LambdaLR (optimization.get_scheduler, :1257); stepped once per rank per optimizer step,
     as accelerate's scheduler wrapper does (which is why the script scales its warm-up by num_processes, :1260)."""
+    return _run_step(model, optimizer,
+                     lambda: training_loss(model, noise_scheduler, latents, noise, timesteps, encoder_hidden_states, conditioning_latents,
+                                           snr_gamma, _return_weights=True),
+                     max_grad_norm, grad_sync, check_overflow, gradient_accumulation_steps, lr_scheduler)
+
+
+def _run_step(model: MirrorFusionModel, optimizer: AdamW, loss_fn, max_grad_norm: float, grad_sync, check_overflow: bool,
+              gradient_accumulation_steps: int, lr_scheduler):
+    """The body train_step and train_step_prepared share: `loss_fn()` runs the forward pass under the tape and returns (loss, pred,
+    target, weights); everything around it — arena clearing, range guard, data-gradient prefetch, loss scale, backward, clip, AdamW —
+    is the same step."""
     mods = model.get_trainable_modules()
     if not mods:
         raise RuntimeError("train_step: call model.prepare_training() first")
@@ -250,8 +270,7 @@ def train_step(model: MirrorFusionModel, noise_scheduler, optimizer: AdamW, late
             dgrad_ready = side.record_event()
     ops.TAPE = tape
     try:
-        loss, pred, target, weights = training_loss(model, noise_scheduler, latents, noise, timesteps, encoder_hidden_states,
-                                                    conditioning_latents, snr_gamma, _return_weights=True)
+        loss, pred, target, weights = loss_fn()
     finally:
         ops.TAPE = None
     d_pred = hip.mse_grad(pred.contiguous(), target.contiguous(), weights)
@@ -317,6 +336,181 @@ def train_step(model: MirrorFusionModel, noise_scheduler, optimizer: AdamW, late
     return loss, norm
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the batch on the device: pixels -> the step's inputs (train_brushnet_mirror.py:1351-1449 minus the model call)
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class PreparedBatch:
+    """What BatchFrontEnd hands to train_step_prepared: device tensors only.  `noise`, `timesteps` are the draws, `latents` the scaled
+    VAE latents (kept for callers; the step reads `noisy_latents`, `target`, `timesteps_f32`, `encoder_hidden_states`,
+    `conditioning_latents` and — with snr_gamma — `loss_weights`)."""
+    latents: torch.Tensor
+    noise: torch.Tensor
+    timesteps: torch.Tensor
+    noisy_latents: torch.Tensor
+    target: torch.Tensor
+    timesteps_f32: torch.Tensor
+    encoder_hidden_states: Optional[torch.Tensor]
+    conditioning_latents: torch.Tensor
+    loss_weights: Optional[torch.Tensor]
+
+
+@dataclasses.dataclass
+class EncodedBatch:
+    """The inputs of the assemble launch (BatchFrontEnd.encode): VAE moments (NHWC, as the encoder left them) and posterior noise of
+    the image, the conditioning image and the 'latents'-mode depth / normals (None where absent), the draws, the full-resolution planes."""
+    moments: list
+    posterior_noise: list
+    noise: torch.Tensor
+    timesteps: torch.Tensor
+    masks: torch.Tensor
+    depths: Optional[torch.Tensor]
+    normals: Optional[torch.Tensor]
+    encoder_hidden_states: Optional[torch.Tensor]
+
+
+_MODES = (None, "concat", "latents")
+
+
+class BatchFrontEnd:
+    """A collated batch of frontend.training_example results -> a PreparedBatch, as the script does it (:1351-1449): each tensor goes
+    through `vae.encode` on its own (image, conditioning image, then the 3x replicated depth and the normals in their 'latents' modes;
+    the moments stay NHWC), the draws are torch's (`rng.randn_tensor` on the generator's device for the posterior noise and the
+    noise, `torch.randint` on the device for the timesteps), the text encoder runs when the batch has `input_ids`, and ONE launch
+    (mf_train_batch_assemble) does the rest: posterior sampling x scaling_factor, the nearest resize of mask / depth / normals,
+    the channel concatenation, add_noise, the epsilon / v target, the float timesteps and the min-SNR weights.  The per-timestep
+    coefficients come from device tables filled once, on the host, with the very expressions add_noise / get_velocity / training_loss
+    evaluate per step — a gather reproduces their values bit for bit.  Nothing after the argument checks reads a device value back."""
+
+    def __init__(self, vae, noise_scheduler, text_encoder=None, depth_conditioning_mode: Optional[str] = None,
+                 normals_conditioning_mode: Optional[str] = None, snr_gamma: Optional[float] = None):
+        if normals_conditioning_mode == "ip_adapter":
+            raise NotImplementedError("normals_conditioning_mode='ip_adapter' is not trained (MirrorFusionModel.forward(normal=...))")
+        if depth_conditioning_mode not in _MODES or normals_conditioning_mode not in _MODES:
+            raise ValueError(f"conditioning modes are None, 'concat' or 'latents', got {depth_conditioning_mode!r} / {normals_conditioning_mode!r}")
+        ptype = noise_scheduler.config["prediction_type"]
+        if ptype not in ("epsilon", "v_prediction"):
+            raise ValueError(f"Unknown prediction type {ptype}")
+        self.vae, self.ns, self.text_encoder = vae, noise_scheduler, text_encoder
+        self.depth_mode, self.normals_mode, self.snr_gamma, self.ptype = depth_conditioning_mode, normals_conditioning_mode, snr_gamma, ptype
+        self._tables: dict = {}
+
+    @property
+    def latent_channels(self) -> int:
+        return int(self.vae.config["latent_channels"])
+
+    def conditioning_channels(self) -> int:
+        c = self.latent_channels
+        return c + 1 + {None: 0, "concat": 1, "latents": c}[self.depth_mode] + {None: 0, "concat": 3, "latents": c}[self.normals_mode]
+
+    def tables(self, device):
+        """(sqrt_alpha, sqrt_one_minus_alpha, loss_weight or None): fp32 device tables over every training timestep."""
+        key = str(torch.device(device))
+        ent = self._tables.get(key)
+        if ent is None:
+            ts = torch.arange(len(self.ns.alphas_cumprod))
+            a = self.ns.alphas_cumprod[ts]
+            sa, sb = a ** 0.5, (1 - a) ** 0.5                                    # add_noise / get_velocity
+            w = None if self.snr_gamma is None else min_snr_weights(self.ns, ts, self.snr_gamma)
+            ent = self._tables[key] = tuple(None if t is None else t.float().contiguous().to(device) for t in (sa, sb, w))
+        return ent
+
+    def image_keys(self) -> list:
+        """The tensors of a collated batch the front end reads (besides input_ids / encoder_hidden_states)."""
+        return ["pixel_values", "conditioning_pixel_values", "masks"] + (["depths"] if self.depth_mode else []) + (["normals"] if self.normals_mode else [])
+
+    def encode_images(self, batch: dict):
+        """The VAE encodes, as the script orders them, and the full-resolution planes: -> (moments [image, conditioning image, depth,
+        normals] with None where absent, masks, depths, normals).  No draw, no host read: capturable after an eager warm-up."""
+        vae, dev = self.vae, self.vae.device
+        missing = [k for k in self.image_keys() if k not in batch]
+        if missing:
+            raise ValueError(f"BatchFrontEnd: the batch lacks {missing}")
+        plane = lambda k: hip.h2d(batch[k], dev).float().contiguous()
+        images = [batch["pixel_values"], batch["conditioning_pixel_values"], None, None]
+        depths = normals = None
+        if self.depth_mode == "latents":
+            d = plane("depths")
+            images[2] = hip.concat_channels([d, d, d], d.shape[0])                # depths.repeat(1, 3, 1, 1), :1381
+        elif self.depth_mode == "concat":
+            depths = plane("depths")
+        if self.normals_mode == "latents":
+            images[3] = batch["normals"]
+        elif self.normals_mode == "concat":
+            normals = plane("normals")
+        return [None if x is None else vae.encode(x).latent_dist.moments_nhwc for x in images], plane("masks"), depths, normals
+
+    def draw(self, batch: dict, latent_shape, noise=None, timesteps=None, posterior_noise=None, generator=None):
+        """The script's random draws (given ones are taken as they are) and the text encoder: -> (posterior noise [4, None where the
+        source is absent], noise, timesteps int64 [B] on the device, encoder_hidden_states or None)."""
+        from .rng import randn_tensor
+        dev = self.vae.device
+        shape = tuple(latent_shape)
+        b = shape[0]
+        used = [True, True, self.depth_mode == "latents", self.normals_mode == "latents"]
+        given = list(posterior_noise) if posterior_noise is not None else []
+        given += [None] * (4 - len(given))
+        on_dev = lambda t: hip.h2d(t, dev).float().contiguous()
+        pns = [None if not u else (on_dev(g) if g is not None else randn_tensor(shape, generator, dev)) for u, g in zip(used, given)]
+        noise = on_dev(noise) if noise is not None else randn_tensor(shape, generator, dev)                   # :1408
+        if timesteps is None:                                                                                  # :1411-1412
+            gen = generator if isinstance(generator, torch.Generator) and generator.device.type == "cuda" else None
+            timesteps = torch.randint(0, self.ns.config["num_train_timesteps"], (b,), device=dev, generator=gen).long()
+        elif not timesteps.is_cuda:
+            t_len = len(self.ns.alphas_cumprod)
+            if timesteps.numel() != b or int(timesteps.min()) < 0 or int(timesteps.max()) >= t_len:
+                raise ValueError(f"BatchFrontEnd: {b} timesteps in [0, {t_len}) needed")
+            timesteps = timesteps.long().to(dev)
+        ehs = batch.get("encoder_hidden_states")
+        if "input_ids" in batch and self.text_encoder is not None:
+            ehs = self.text_encoder(batch["input_ids"], return_dict=False)[0]                                  # :1419
+        return pns, noise, timesteps.reshape(-1), ehs
+
+    def encode(self, batch: dict, noise=None, timesteps=None, posterior_noise=None, generator=None) -> EncodedBatch:
+        """Everything ahead of the assemble launch: the VAE encodes, the draws, the text encoder."""
+        moments, masks, depths, normals = self.encode_images(batch)
+        b, h, w, _ = moments[0].shape
+        pns, noise, timesteps, ehs = self.draw(batch, (b, self.latent_channels, h, w), noise, timesteps, posterior_noise, generator)
+        return EncodedBatch(moments, pns, noise, timesteps, masks, depths, normals, ehs)
+
+    def assemble(self, enc: EncodedBatch, out: Optional[dict] = None) -> dict:
+        """The one launch (capturable: no allocation when `out` names every output, no host read).  `out`: hip.ASSEMBLE_OUTPUTS names."""
+        sa, sb, lw = self.tables(enc.noise.device)
+        return hip.train_batch_assemble(enc.moments, enc.posterior_noise, self.latent_channels, self.vae.config["scaling_factor"], enc.noise,
+                                        enc.timesteps, sa, sb, enc.masks, depths=enc.depths, normals=enc.normals, loss_weight=lw,
+                                        v_prediction=self.ptype == "v_prediction", out=out)
+
+    def __call__(self, batch: dict, noise=None, timesteps=None, posterior_noise=None, generator=None, out: Optional[dict] = None) -> PreparedBatch:
+        """`noise` [B, c, h, w], `timesteps` int64 [B] and `posterior_noise` (a list: image, conditioning image, depth, normals; None
+        entries are drawn) may be passed for reproducibility.  `out`: caller-owned static buffers by name (hip.ASSEMBLE_OUTPUTS, and
+        "encoder_hidden_states", which receives a copy of the text encoder's output)."""
+        enc = self.encode(batch, noise, timesteps, posterior_noise, generator)
+        res = self.assemble(enc, out)
+        ehs = enc.encoder_hidden_states
+        if out is not None and out.get("encoder_hidden_states") is not None and ehs is not None:
+            out["encoder_hidden_states"].copy_(ehs)
+            ehs = out["encoder_hidden_states"]
+        return PreparedBatch(res["latents"], enc.noise, enc.timesteps, res["noisy_latents"], res["target"], res["timesteps_f32"], ehs,
+                             res["conditioning_latents"], res.get("loss_weights"))
+
+
+def _prepared_loss(model: MirrorFusionModel, prepared: PreparedBatch):
+    """training_loss from a PreparedBatch: the model call and the loss (:1422-1449); the rest is already in the batch."""
+    if prepared.encoder_hidden_states is None:
+        raise ValueError("train_step_prepared: the batch has no encoder_hidden_states (pass input_ids and a text_encoder, or the states)")
+    pred = model(prepared.noisy_latents, prepared.timesteps_f32, prepared.encoder_hidden_states, prepared.conditioning_latents)
+    loss, _ = hip.mse_loss(pred.float(), prepared.target, prepared.loss_weights)
+    return loss, pred, prepared.target, prepared.loss_weights
+
+
+def train_step_prepared(model: MirrorFusionModel, noise_scheduler, optimizer: AdamW, prepared: PreparedBatch, max_grad_norm: float = 1.0,
+                        grad_sync=None, check_overflow: bool = True, gradient_accumulation_steps: int = 1, lr_scheduler=None):
+    """train_step from a PreparedBatch (BatchFrontEnd): the same body, the same results.  The min-SNR weighting is the front end's
+    (`BatchFrontEnd(snr_gamma=...)`: `prepared.loss_weights`); `noise_scheduler` is kept for the call surface."""
+    return _run_step(model, optimizer, lambda: _prepared_loss(model, prepared), max_grad_norm, grad_sync, check_overflow,
+                     gradient_accumulation_steps, lr_scheduler)
+
+
 class GraphedTrainStep:
     """train_step() with zero_grad + forward + loss + backward + clip captured ONCE in a hipGraph and replayed every step.
 
@@ -335,8 +529,11 @@ class GraphedTrainStep:
     Memory: the graph keeps one step's activations resident between calls (they are reused, not reallocated)."""
 
     def __init__(self, model: MirrorFusionModel, noise_scheduler, optimizer: AdamW, snr_gamma: Optional[float] = None,
-                 max_grad_norm: float = 1.0, check_overflow: bool = True, warmup: int = 2, lr_scheduler=None, grad_sync=None):
+                 max_grad_norm: float = 1.0, check_overflow: bool = True, warmup: int = 2, lr_scheduler=None, grad_sync=None,
+                 front_end: Optional["BatchFrontEnd"] = None):
         self.model, self.ns, self.opt = model, noise_scheduler, optimizer
+        # a BatchFrontEnd: from_pixels() then runs the step from a collated batch of pixels (its own capture, the assemble launch first)
+        self.front_end, self._px = front_end, None
         # a distributed.GradBuckets: the step is then captured as a CHAIN of graphs cut wherever the backward pass releases a
         # gradient bucket, and the bucket's all-reduce is issued eagerly between two replays (RCCL calls are never captured)
         self.grad_sync = grad_sync
@@ -367,10 +564,7 @@ class GraphedTrainStep:
         self.ehs.copy_(ehs.to(dev, torch.float32))
         self.cond.copy_(cond.to(dev, torch.float32))
         if self.snr_gamma is not None:                                                                   # :1437-1449
-            snr = compute_snr(self.ns, timesteps)
-            w = torch.stack([snr, self.snr_gamma * torch.ones_like(snr)], dim=1).min(dim=1)[0]
-            w = w / snr if ptype == "epsilon" else w / (snr + 1)
-            self.weights.copy_(hip.h2d(w.float().contiguous(), dev))
+            self.weights.copy_(hip.h2d(min_snr_weights(self.ns, timesteps, self.snr_gamma).float().contiguous(), dev))
 
     def _body(self):
         model, prec = self.model, self.model.brushnet.prec
@@ -475,6 +669,14 @@ class GraphedTrainStep:
             return train_step(model, self.ns, self.opt, latents, noise, timesteps, encoder_hidden_states, conditioning_latents,
                               snr_gamma=self.snr_gamma, max_grad_norm=self.max_grad_norm, check_overflow=self.check_overflow,
                               lr_scheduler=self.lr_scheduler, grad_sync=self.grad_sync)
+        return self._replay(latents.shape, encoder_hidden_states.shape, conditioning_latents.shape,
+                            lambda: self._stage(latents, noise, timesteps, encoder_hidden_states, conditioning_latents))
+
+    def _replay(self, latents_shape, ehs_shape, cond_shape, stage):
+        """Capture on the first call (static buffers of these shapes, staged once, then the body under capture), stage + replay on the
+        others; then the range guard and the optimizer, eagerly."""
+        model = self.model
+        mods = model.get_trainable_modules()
         dev = mods[0].device
         prec = model.brushnet.prec
         if self.graph is not None and self._arenas() != self._arena_key:
@@ -482,11 +684,11 @@ class GraphedTrainStep:
             self.graph, self.segments = None, None
         if self.graph is None:
             f32 = dict(dtype=torch.float32, device=dev)
-            self.noisy, self.target = torch.empty(latents.shape, **f32), torch.empty(latents.shape, **f32)
-            self.t_dev = torch.empty(latents.shape[0], **f32)
-            self.ehs, self.cond = torch.empty(encoder_hidden_states.shape, **f32), torch.empty(conditioning_latents.shape, **f32)
-            self.weights = torch.ones(latents.shape[0], **f32)
-            self._stage(latents, noise, timesteps, encoder_hidden_states, conditioning_latents)
+            self.noisy, self.target = torch.empty(latents_shape, **f32), torch.empty(latents_shape, **f32)
+            self.t_dev = torch.empty(latents_shape[0], **f32)
+            self.ehs, self.cond = torch.empty(ehs_shape, **f32), torch.empty(cond_shape, **f32)
+            self.weights = torch.ones(latents_shape[0], **f32)
+            stage()
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
             # The per-step re-layouts of the weights that train (ConvWeight.operand: split-pack; autograd._dgrad_weight:
@@ -505,10 +707,10 @@ class GraphedTrainStep:
                 ops.CAPTURE_TOKEN = None
             self._arena_key = self._arenas()
         else:
-            for t, ref in ((latents, self.noisy), (encoder_hidden_states, self.ehs), (conditioning_latents, self.cond)):
-                if tuple(t.shape) != tuple(ref.shape):
-                    raise ValueError(f"GraphedTrainStep: input shape {tuple(t.shape)} != the captured {tuple(ref.shape)}")
-            self._stage(latents, noise, timesteps, encoder_hidden_states, conditioning_latents)
+            for shape, ref in ((latents_shape, self.noisy), (ehs_shape, self.ehs), (cond_shape, self.cond)):
+                if tuple(shape) != tuple(ref.shape):
+                    raise ValueError(f"GraphedTrainStep: input shape {tuple(shape)} != the captured {tuple(ref.shape)}")
+            stage()
         guard = self.check_overflow and (prec.code == hip.MF_F16X3 or (prec.code == hip.MF_BF16X1 and self.split_kernels > 0))
         if guard:
             hip.split_overflow(reset=True)
@@ -533,6 +735,66 @@ class GraphedTrainStep:
             for _ in range(max(int(getattr(self.grad_sync, "world", 1) or 1), 1) if self.grad_sync is not None else 1):
                 self.lr_scheduler.step()
         return self.loss, self.norm
+
+    def from_pixels(self, batch: dict, noise=None, timesteps=None, posterior_noise=None, generator=None):
+        """The step from a collated batch of pixels (frontend.training_example) through the BatchFrontEnd given at construction.
+        Eager ahead of the replay: the random draws and the text encoder; they and the batch's pixel tensors are copied into static inputs.
+        Captured, at the head of the step's first graph: the VAE encodes and the assemble launch — which writes the step's static
+        buffers directly — then the step as __call__ captures it.  The capture is this path's own (a second graph on the same model, optimizer and buffers of
+        its own): __call__ on prepared latents keeps its graph and its results.  The first `warmup` calls run train_step_prepared."""
+        if self.front_end is None:
+            raise RuntimeError("GraphedTrainStep.from_pixels: construct the step with front_end=BatchFrontEnd(...)")
+        if self._px is None:
+            self._px = _PixelTrainStep(self)
+        return self._px.run(batch, noise, timesteps, posterior_noise, generator)
+
+
+class _PixelTrainStep(GraphedTrainStep):
+    """GraphedTrainStep.from_pixels' capture: the VAE encodes of the batch (they capture cleanly once an eager call has tuned their
+    shapes; the warm-up calls are eager), mf_train_batch_assemble writing noisy / target / t_dev / cond / weights where the step reads
+    them, then the same body.  Static inputs: the batch's pixel tensors and planes, the draws, the text encoder's output."""
+
+    def __init__(self, outer: GraphedTrainStep):
+        super().__init__(outer.model, outer.ns, outer.opt, snr_gamma=outer.front_end.snr_gamma, max_grad_norm=outer.max_grad_norm,
+                         check_overflow=outer.check_overflow, warmup=outer.warmup, lr_scheduler=outer.lr_scheduler, grad_sync=outer.grad_sync)
+        self.fe, self.images, self.draws, self.latents, self._latent_shape = outer.front_end, None, None, None, None
+
+    def _stage_pixels(self, batch: dict, draws):
+        pns, noise, timesteps, ehs = draws
+        if ehs is None:
+            raise ValueError("from_pixels: the batch has no encoder_hidden_states (pass input_ids and a text_encoder, or the states)")
+        dev = self.noisy.device
+        if self.images is None:
+            self.images = {k: torch.empty(batch[k].shape, dtype=torch.float32, device=dev) for k in self.fe.image_keys()}
+            self.draws = [None if p is None else torch.empty_like(p) for p in pns] + [torch.empty_like(noise), torch.empty_like(timesteps)]
+            self.latents = torch.empty_like(noise)
+        for dst, src in list(zip(self.images.values(), (batch[k] for k in self.images))) + list(zip(self.draws, pns + [noise, timesteps])):
+            if (dst is None) != (src is None) or (dst is not None and tuple(dst.shape) != tuple(src.shape)):
+                raise ValueError("from_pixels: the batch does not match the captured one (shapes, conditioning modes)")
+            if dst is not None:
+                dst.copy_(src)
+        self.ehs.copy_(ehs.to(dev, torch.float32))
+
+    def _body(self):
+        moments, masks, depths, normals = self.fe.encode_images(self.images)
+        enc = EncodedBatch(moments, self.draws[:4], self.draws[4], self.draws[5], masks, depths, normals, None)
+        self.fe.assemble(enc, out=dict(latents=self.latents, noisy_latents=self.noisy, target=self.target, conditioning_latents=self.cond,
+                                       timesteps_f32=self.t_dev, loss_weights=self.weights))
+        return super()._body()
+
+    def run(self, batch, noise, timesteps, posterior_noise, generator):
+        if not self.model.get_trainable_modules():
+            raise RuntimeError("GraphedTrainStep: call model.prepare_training() first")
+        if self.graph is None and self.calls < self.warmup:
+            self.calls += 1
+            prepared = self.fe(batch, noise, timesteps, posterior_noise, generator)
+            self._latent_shape = tuple(prepared.latents.shape)
+            return train_step_prepared(self.model, self.ns, self.opt, prepared, max_grad_norm=self.max_grad_norm,
+                                       check_overflow=self.check_overflow, lr_scheduler=self.lr_scheduler, grad_sync=self.grad_sync)
+        b, c, h, w = self._latent_shape
+        draws = self.fe.draw(batch, self._latent_shape, noise, timesteps, posterior_noise, generator)
+        ehs_shape = draws[3].shape if draws[3] is not None else (b, 0, 0)
+        return self._replay(self._latent_shape, ehs_shape, (b, self.fe.conditioning_channels(), h, w), lambda: self._stage_pixels(batch, draws))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

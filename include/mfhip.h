@@ -24,7 +24,8 @@
  * ingest of a host that decoded an image file) and the step-level entries mf_encode_prompt / mf_build_conditioning / mf_decode_image,
  * which with mf_denoise_step_fused run a whole inpainting call from step programs: token ids, pixels, mask and depth in, a uint8
  * image out (examples/c_host/inpaint_host.c); and the training batch (csrc/train_batch.hip): mf_train_example_u8, mf_masked_image_u8,
- * mf_fliplr, mf_train_batch_assemble.
+ * mf_fliplr, mf_train_batch_assemble; and the two ends of a tile of the tiled VAE (csrc/vae_tile.hip): mf_crop_pack_nhwc,
+ * mf_vae_tile_blend.
  */
 #ifndef MFHIP_H
 #define MFHIP_H
@@ -612,6 +613,30 @@ int mf_train_batch_assemble(const void* const* moments, const float* const* post
                             const float* masks, const float* depths, const float* normals, int32_t plane_h, int32_t plane_w,
                             int32_t prediction_type, float* latents, float* noisy_latents, float* target, float* conditioning_latents,
                             float* timesteps_f32, float* loss_weights, void* stream);
+
+/* ---- tiled VAE encode / decode (csrc/vae_tile.hip; models/autoencoders/autoencoder_kl.py:311-423).  Appended to ABI 23; not part
+ * of step programs. -----------------------------------------------------------------------------------------------------------------
+ * mf_crop_pack_nhwc: mf_pack_nhwc with a window.  src is NCHW fp32 [batch][c][h][w]; its window [y0, y0 + th) x [x0, x0 + tw) goes to
+ * NHWC [batch][th][tw][c_pad] of dst_dtype (MF_F32 / MF_BF16 / MF_F16), channels c .. c_pad - 1 zero, written at sample `batch_offset`
+ * of dst = [dst_batch][th][tw][c_pad]: one launch takes one tile (x[:, :, i : i + tile, j : j + tile]) into its slot range of a
+ * stacked group buffer.  The window must lie inside the source and the samples inside the buffer. */
+int mf_crop_pack_nhwc(const float* src, int32_t batch, int32_t c, int32_t h, int32_t w, int32_t y0, int32_t x0, int32_t th, int32_t tw,
+                      void* dst, int32_t dst_dtype, int32_t c_pad, int32_t dst_batch, int32_t batch_offset, void* stream);
+/* mf_vae_tile_blend: blend_v, blend_h, the crop and the two torch.cat of tiled_decode / tiled_encode (autoencoder_kl.py:311-321,
+ * 357-369, 407-419) for ONE tile; launch once per tile in raster order on one stream.  tile: fp32 NHWC [batch][th][tw][ld] (ld % 4 == 0,
+ * 16-byte aligned), blended IN PLACE; above: the finished tile of the previous row, [batch][above_h][above_w][ld] with above_w == tw,
+ * or NULL in row 0; left: the finished previous tile of this row, [batch][left_h][left_w][ld] with left_h == th, or NULL in column 0.
+ * With ev = min(above_h, th, blend_extent) and eh = min(left_w, tw, blend_extent), every pixel is finished in the reference's order:
+ *   y < ev:  t[y][x] = above[above_h - ev + y][x] * (float)(1.0 - (double)y / ev) + t[y][x] * (float)((double)y / ev)
+ *   x < eh:  t[y][x] = left[y][left_w - eh + x]   * (float)(1.0 - (double)x / eh) + t[y][x] * (float)((double)x / eh)
+ * each product and each sum rounded to fp32 on its own (ATen's arithmetic for those lines; no FMA), over all ld floats of the pixel.
+ * The strips are written back into `tile` (the tiles below and to the right read them, the parts outside the crop included) and the
+ * crop [:min(th, row_limit), :min(tw, row_limit)] goes to `out` at (out_y, out_x): NCHW fp32 [batch][c][out_h][out_w] (out_nhwc = 0,
+ * the first c channels: the decoder's image) or NHWC fp32 [batch][out_h][out_w][ld] (out_nhwc = 1, 16-byte aligned: the encoder's
+ * moments).  A neighbour whose shared dimension differs, or a crop that leaves the output, is refused. */
+int mf_vae_tile_blend(float* tile, const float* above, const float* left, int32_t batch, int32_t th, int32_t tw, int32_t above_h,
+                      int32_t above_w, int32_t left_h, int32_t left_w, int64_t ld, int32_t c, int32_t blend_extent, int32_t row_limit,
+                      float* out, int32_t out_nhwc, int32_t out_h, int32_t out_w, int32_t out_y, int32_t out_x, void* stream);
 
 /* ---- image scoring on the device (metrics/metrics.py:51-67,108-165: torchmetrics' peak_signal_noise_ratio and
  * structural_similarity_index_measure with their defaults, on the images taken as floats 0 .. 255) --------------------------------

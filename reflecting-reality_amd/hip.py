@@ -191,6 +191,8 @@ SIGNATURES = {
     # the training batch (csrc/train_batch.hip)
     "mf_train_example_u8": "i:ppppppiiiip", "mf_masked_image_u8": "i:pppliip", "mf_fliplr": "i:ppliip",
     "mf_train_batch_assemble": "i:ppiiliiiifpppppipppiiippppppp",
+    # tiled VAE encode / decode (csrc/vae_tile.hip)
+    "mf_crop_pack_nhwc": "i:piiiiiiiipiiiip", "mf_vae_tile_blend": "i:pppiiiiiiiliiipiiiiip",
     # image scoring (csrc/metrics.hip)
     "mf_sizeof_metrics_row": "i:", "mf_image_metrics_ws_bytes": "l:iiii", "mf_image_metrics": "i:pppiiiiifppp",
     # CLIP image side and score (csrc/clip_vision.hip)
@@ -1100,6 +1102,49 @@ def unpack_nchw(src: torch.Tensor, c: int) -> torch.Tensor:
     out = torch.empty(b, c, h, w, dtype=torch.float32, device=src.device)
     _launch("mf_unpack_nchw", src, dt_code(src.dtype), ld, out, c, b, h * w)
     return out
+
+
+def _not_replayable(entry: str) -> None:
+    if _RECORDER is not None:
+        raise MfhipError(f"{entry} is not part of step programs: a tiled VAE pass cannot be recorded")
+
+
+def crop_pack_nhwc(src: torch.Tensor, y0: int, x0: int, th: int, tw: int, out: torch.Tensor, batch_offset: int = 0) -> torch.Tensor:
+    """src[:, :, y0 : y0 + th, x0 : x0 + tw] of an NCHW fp32 tensor -> NHWC with zero pad channels, written at sample `batch_offset` of
+    out = [n * B, th, tw, c_pad] (a stacked group buffer of the tiled VAE; its dtype is the destination dtype)."""
+    _not_replayable("mf_crop_pack_nhwc")
+    _req_cuda(src, out)
+    if src.dtype != torch.float32 or src.dim() != 4 or not src.is_contiguous():
+        raise MfhipError(f"crop_pack_nhwc: src is a contiguous NCHW fp32 tensor, got {src.dtype} {tuple(src.shape)}")
+    if out.dim() != 4 or not out.is_contiguous() or tuple(out.shape[1:3]) != (th, tw):
+        raise MfhipError(f"crop_pack_nhwc: out is a contiguous [n, {th}, {tw}, c_pad] buffer, got {tuple(out.shape)}")
+    b, c, h, w = src.shape
+    _launch("mf_crop_pack_nhwc", src, b, c, h, w, y0, x0, th, tw, out, dt_code(out.dtype), out.shape[3], out.shape[0], batch_offset)
+    return out
+
+
+def vae_tile_blend(tile: torch.Tensor, above: Optional[torch.Tensor], left: Optional[torch.Tensor], blend_extent: int, row_limit: int,
+                   c: int, out: torch.Tensor, out_y: int, out_x: int, nhwc: bool) -> None:
+    """blend_v / blend_h / crop / cat of tiled_decode and tiled_encode for one tile (mf_vae_tile_blend): `tile` [B, th, tw, ld] fp32 is
+    blended in place against the finished tiles `above` and `left` (None at the first row / column) and its crop is written into `out`
+    at (out_y, out_x) — NCHW [B, c, H, W] or, with `nhwc`, NHWC [B, H, W, ld].  Call per tile in raster order."""
+    _not_replayable("mf_vae_tile_blend")
+    _req_cuda(tile, above, left, out)
+    for name, t in (("tile", tile), ("above", above), ("left", left), ("out", out)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous()):
+            raise MfhipError(f"vae_tile_blend: {name} is a contiguous 4-d fp32 tensor, got {t.dtype} {tuple(t.shape)}")
+    b, th, tw, ld = tile.shape
+    for name, t in (("above", above), ("left", left)):
+        if t is not None and (t.shape[0] != b or t.shape[3] != ld):
+            raise MfhipError(f"vae_tile_blend: {name} {tuple(t.shape)} does not go with the tile {tuple(tile.shape)}")
+    want = (b, out.shape[1], out.shape[2], ld) if nhwc else (b, c, out.shape[2], out.shape[3])
+    if tuple(out.shape) != want:
+        raise MfhipError(f"vae_tile_blend: out {tuple(out.shape)} is not {'NHWC' if nhwc else 'NCHW'} {want}")
+    ah, aw = (above.shape[1], above.shape[2]) if above is not None else (0, 0)
+    lh, lw = (left.shape[1], left.shape[2]) if left is not None else (0, 0)
+    oh, ow = (out.shape[1], out.shape[2]) if nhwc else (out.shape[2], out.shape[3])
+    _launch("mf_vae_tile_blend", tile, above, left, b, th, tw, ah, aw, lh, lw, ld, c, blend_extent, row_limit, out, int(bool(nhwc)), oh, ow,
+            out_y, out_x)
 
 
 def add(a: torch.Tensor, b: torch.Tensor, out_dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:

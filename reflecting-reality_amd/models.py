@@ -1573,6 +1573,48 @@ class UNet2DConditionModel(_UNetCore):
 
 
 # =================================================================================================
+def vae_tile_plan(H: int, W: int, tile: int, overlap_factor: float, scale_num: int, scale_den: int, out_tile: Optional[int] = None) -> dict:
+    """The grid of tiled_encode / tiled_decode (autoencoder_kl.py:342-369, 391-419) in the reference's own integers, for an H x W
+    input cut into `tile`-sized tiles whose results are scale_num / scale_den times as large (decode: 2^levels / 1 on the latents,
+    encode: 1 / 2^levels on the pixels — every stride-2 conv of the encoder floors, and nested floors are one floor).  `out_tile` is
+    the tile size on the output side (tile_sample_min_size for decode, tile_latent_min_size for encode; default: the scaled `tile`).
+    Returns overlap_size, blend_extent, row_limit, the tile starts and sizes per axis (`rows`, `cols` as (start, size)), the tiles
+    in raster order — grid position i / j, window y0 / x0 / h / w, result out_h / out_w, crop crop_h / crop_w and its place oy / ox
+    in the output — and the output size out_h / out_w, which is the SUM of the crops (not the scaled input size).  Pure Python."""
+    if min(H, W, tile, scale_num, scale_den) < 1:
+        raise ValueError(f"vae_tile_plan: sizes must be positive (H {H}, W {W}, tile {tile}, scale {scale_num} / {scale_den})")
+    if out_tile is None:
+        out_tile = tile * scale_num // scale_den
+    overlap_size = int(tile * (1 - overlap_factor))
+    blend_extent = int(out_tile * overlap_factor)
+    row_limit = out_tile - blend_extent
+    if overlap_size < 1 or row_limit < 1:
+        raise ValueError(f"vae_tile_plan: a tile of {tile} -> {out_tile} with overlap factor {overlap_factor} gives the stride "
+                         f"{overlap_size} and the row limit {row_limit}: the reference's loops do not advance")
+
+    def axis(n):
+        out = []
+        for s in range(0, n, overlap_size):
+            size = min(tile, n - s)
+            res = size * scale_num // scale_den
+            if res < 1:
+                raise ValueError(f"vae_tile_plan: the tile at {s} has {size} rows / columns, which the network maps to {res}: the "
+                                 "reference fails on such a tile too (choose a size whose last tile is larger)")
+            out.append((s, size, res, min(res, row_limit)))
+        return out
+
+    rows, cols = axis(H), axis(W)
+    tiles, oy = [], 0
+    for i, (y0, th, rh, ch) in enumerate(rows):
+        ox = 0
+        for j, (x0, tw, rw, cw) in enumerate(cols):
+            tiles.append(dict(i=i, j=j, y0=y0, x0=x0, h=th, w=tw, out_h=rh, out_w=rw, crop_h=ch, crop_w=cw, oy=oy, ox=ox))
+            ox += cw
+        oy += ch
+    return dict(overlap_size=overlap_size, blend_extent=blend_extent, row_limit=row_limit, rows=[(s, n) for s, n, _, _ in rows],
+                cols=[(s, n) for s, n, _, _ in cols], tiles=tiles, out_h=oy, out_w=sum(cw for _, _, _, cw in cols))
+
+
 class DiagonalGaussianDistribution:
     """vae.py:769-822, moments kept NHWC on the device; `sample` needs explicit or generator noise."""
 
@@ -1614,10 +1656,52 @@ class AutoencoderKL(HipModel):
         cfg.setdefault("norm_num_groups", 32); cfg.setdefault("scaling_factor", 0.18215)
         cfg["block_out_channels"] = tuple(cfg["block_out_channels"])
         super().__init__(cfg, precision, device)
+        # autoencoder_kl.py:115-126 (only relevant once tiling is enabled); the config itself is left as it was given
+        self.use_slicing = False
+        self.use_tiling = False
+        sample_size = cfg.get("sample_size", 32)
+        sample_size = sample_size[0] if isinstance(sample_size, (list, tuple)) else sample_size
+        self.tile_sample_min_size = sample_size
+        self.tile_latent_min_size = int(sample_size / (2 ** (len(cfg["block_out_channels"]) - 1)))
+        self.tile_overlap_factor = 0.25
+        # tiles of one shape are stacked on the batch axis and run as one pass; at most this many tiles per pass (GroupNorm and the
+        # attention are per sample, so the cap changes the schedule and the memory held; the GEMMs may pick another tile for another M)
+        self.tile_batch = 16
 
     def prepare_training(self, requires_grad=None):
         raise NotImplementedError("the VAE is frozen in MirrorFusion training (train_brushnet_mirror.py:1072) and outside the "
                                   "loss graph: it has no training layout")
+
+    # ---- the memory switches (autoencoder_kl.py:132-159) ----------------------------------------------
+    def enable_tiling(self, use_tiling: bool = True):
+        """Inputs larger than the tile threshold (config sample_size pixels / the latent size that goes with it) are encoded and
+        decoded as overlapping tiles blended with linear ramps, as the reference does — which CHANGES the result."""
+        self.use_tiling = use_tiling
+
+    def disable_tiling(self):
+        self.enable_tiling(False)
+
+    def enable_slicing(self):
+        """Batches are encoded / decoded one sample at a time (the same result: every layer of the VAE is per sample)."""
+        self.use_slicing = True
+
+    def disable_slicing(self):
+        self.use_slicing = False
+
+    def _tiles_pixels(self, h: int, w: int) -> bool:
+        return bool(self.use_tiling) and (w > self.tile_sample_min_size or h > self.tile_sample_min_size)       # :253
+
+    def _tiles_latents(self, h: int, w: int) -> bool:
+        return bool(self.use_tiling) and (w > self.tile_latent_min_size or h > self.tile_latent_min_size)       # :271
+
+    def refuse_export(self, what: str, batch: int, h: int, w: int, latents: bool) -> None:
+        """A step program holds one untiled pass; a tiled or sliced one is a host loop over launches that are not replayable."""
+        if self._tiles_latents(h, w) if latents else self._tiles_pixels(h, w):
+            raise NotImplementedError(f"{what}: VAE tiling is enabled and applies at {h} x {w} {'latents' if latents else 'pixels'}; a "
+                                      "tiled pass is not part of step programs (disable_tiling() before exporting)")
+        if self.use_slicing and batch > 1:
+            raise NotImplementedError(f"{what}: VAE slicing is enabled and applies to a batch of {batch}; a sliced pass is not part of "
+                                      "step programs (disable_slicing() before exporting)")
 
     def _convert_deprecated_keys(self, sd):
         # modeling_utils.py:929-971: query/key/value/proj_attn -> to_q/to_k/to_v/to_out.0
@@ -1713,6 +1797,16 @@ class AutoencoderKL(HipModel):
         self.P["decoder.conv_in"] = self._conv(sd, "decoder.conv_in", cin_pad=self.lat_pad)
         self.P["decoder.conv_norm_out"] = self._norm(sd, "decoder.conv_norm_out")
         self.P["decoder.conv_out"] = self._conv(sd, "decoder.conv_out")
+        # the tiled decode blends conv_out's fp32 result as 16-byte vectors (mf_vae_tile_blend: ld % 4 == 0): its tiles go through a
+        # copy of conv_out with N padded to a multiple of 4 by zero rows; the untiled path keeps the weight it always had
+        w, b = sd["decoder.conv_out.weight"], sd["decoder.conv_out.bias"]
+        oc_pad = (w.shape[0] + 3) // 4 * 4
+        if oc_pad != w.shape[0]:
+            wp = torch.zeros(oc_pad, *w.shape[1:]); wp[: w.shape[0]] = w
+            bp = torch.zeros(oc_pad); bp[: w.shape[0]] = b
+            self.P["decoder.conv_out.tiles"] = ConvWeight(wp, bp, self.prec, self.device)
+        else:
+            self.P["decoder.conv_out.tiles"] = self.P["decoder.conv_out"]
 
     # ---- blocks -------------------------------------------------------------------------------------
     def _resnet(self, p, x):
@@ -1740,11 +1834,11 @@ class AutoencoderKL(HipModel):
         x = ops.linear(o, P[a + "to_out.0"], res0=x.view(b, s, c)).view(b, hh, ww, c)
         return self._resnet(p + "resnets.1.", x)
 
-    def _moments(self, x: torch.Tensor) -> torch.Tensor:
+    def _encode_body(self, h: torch.Tensor) -> torch.Tensor:
+        """Encoder + quant_conv on packed pixels: NHWC [B, H, W, cin_pad] in the activation dtype -> fp32 NHWC moments."""
         c = self.config
         n = len(c["block_out_channels"])
         hip.TUNE_CTX = None                                      # the VAE's tune keys carry no position tag
-        h = from_nchw(hip.h2d(x, self.device).float(), self.prec, self.cin_pad)
         h = ops.conv2d(h, self.P["encoder.conv_in"], gn_part=self.config["norm_num_groups"])
         for i in range(n):
             for j in range(c["layers_per_block"]):
@@ -1757,17 +1851,109 @@ class AutoencoderKL(HipModel):
         h = ops.conv2d(h, self.P["encoder.conv_out"])
         return ops.conv2d(h, self.P["quant_conv"], padding=0, out_dtype=F32)
 
+    def _moments(self, x: torch.Tensor) -> torch.Tensor:
+        """encode (autoencoder_kl.py:238-268) up to the moments, fp32 NHWC: tiled above the threshold when tiling is enabled, one
+        sample at a time when slicing is, else one pass."""
+        if self._tiles_pixels(x.shape[-2], x.shape[-1]):
+            return self._tiled(x, encode=True)
+        if self.use_slicing and x.shape[0] > 1:                  # :256-258
+            return torch.cat([self._moments_once(x[i:i + 1]) for i in range(x.shape[0])])
+        return self._moments_once(x)
+
+    def _moments_once(self, x: torch.Tensor) -> torch.Tensor:
+        hip.TUNE_CTX = None
+        return self._encode_body(from_nchw(hip.h2d(x, self.device).float(), self.prec, self.cin_pad))
+
     @_scoped_tune_ctx
     def encode(self, x: torch.Tensor, return_dict: bool = True):
         d = DiagonalGaussianDistribution(self._moments(x), self.config["latent_channels"])
         return AutoencoderKLOutput(latent_dist=d) if return_dict else (d,)
 
     @_scoped_tune_ctx
+    def tiled_encode(self, x: torch.Tensor, return_dict: bool = True):
+        """autoencoder_kl.py:323-375, whatever the input's size (encode() calls it above the threshold)."""
+        d = DiagonalGaussianDistribution(self._tiled(x, encode=True), self.config["latent_channels"])
+        return AutoencoderKLOutput(latent_dist=d) if return_dict else (d,)
+
+    @_scoped_tune_ctx
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
+        if self.use_slicing and z.shape[0] > 1:                  # :300-302
+            img = torch.cat([self._decode(z[i:i + 1]) for i in range(z.shape[0])])
+        else:
+            img = self._decode(z)
+        return DecoderOutput(sample=img) if return_dict else (img,)
+
+    @_scoped_tune_ctx
+    def tiled_decode(self, z: torch.Tensor, return_dict: bool = True):
+        """autoencoder_kl.py:377-423, whatever the input's size (decode() calls it above the threshold)."""
+        img = self._tiled(z, encode=False)
+        return DecoderOutput(sample=img) if return_dict else (img,)
+
+    def _decode(self, z: torch.Tensor) -> torch.Tensor:
+        if self._tiles_latents(z.shape[-2], z.shape[-1]):        # :271-272
+            return self._tiled(z, encode=False)
+        hip.TUNE_CTX = None
+        y = self._decode_body(from_nchw(z.to(self.device).float(), self.prec, self.lat_pad))
+        return hip.unpack_nchw(y, self.config["out_channels"])
+
+    def _tiled(self, x: torch.Tensor, encode: bool) -> torch.Tensor:
+        """tiled_encode / tiled_decode.  The reference runs its tiles one at a time; here the tiles of one shape (at most four
+        shapes: interior, right edge, bottom edge, corner) are cropped into ONE stacked buffer (mf_crop_pack_nhwc) and go through
+        the encoder / decoder body as one pass — GroupNorm and the attention are per sample, so a tile is exactly a sample.  The
+        blends then run per tile in raster order (mf_vae_tile_blend), in place in the stacked fp32 results like the reference's
+        blend_v / blend_h in its stored tiles, each launch also writing its tile's crop into the output.
+        Returns the image NCHW fp32 (decode) or the moments NHWC fp32 (encode)."""
+        c = self.config
+        levels = len(c["block_out_channels"]) - 1
+        x = (hip.h2d(x, self.device) if encode else x.to(self.device)).float().contiguous()
+        b, _, hh, ww = x.shape
+        if encode:
+            plan = vae_tile_plan(hh, ww, self.tile_sample_min_size, self.tile_overlap_factor, 1, 2 ** levels, self.tile_latent_min_size)
+            body, c_pad, widest, c_out = self._encode_body, self.cin_pad, c["block_out_channels"][0], 2 * c["latent_channels"]
+        else:
+            plan = vae_tile_plan(hh, ww, self.tile_latent_min_size, self.tile_overlap_factor, 2 ** levels, 1, self.tile_sample_min_size)
+            body = lambda stack: self._decode_body(stack, "decoder.conv_out.tiles")
+            c_pad, widest, c_out = self.lat_pad, c["block_out_channels"][0], c["out_channels"]
+        hip.TUNE_CTX = None
+        groups: "OrderedDict[Tuple[int, int], list]" = OrderedDict()
+        for t in plan["tiles"]:
+            groups.setdefault((t["h"], t["w"]), []).append(t)
+        done = {}
+        for (th, tw), tiles in groups.items():
+            # the largest activation of a tile: block_out_channels[0] channels at the pixel resolution; a chunk keeps it addressable
+            # with the 31-bit byte offsets of the GEMM family's fast paths (and under mf_gemm_conv's M < 2^31)
+            pix = th * tw if encode else tiles[0]["out_h"] * tiles[0]["out_w"]
+            per_tile = b * pix * widest * 4
+            chunk = max(1, min(int(self.tile_batch), ((1 << 31) - (1 << 20)) // max(per_tile, 1)))
+            for s in range(0, len(tiles), chunk):
+                part = tiles[s:s + chunk]
+                stack = torch.empty(len(part) * b, th, tw, c_pad, dtype=self.prec.act, device=self.device)
+                for k, t in enumerate(part):
+                    hip.crop_pack_nhwc(x, t["y0"], t["x0"], th, tw, stack, k * b)
+                y = body(stack)
+                for k, t in enumerate(part):
+                    done[(t["i"], t["j"])] = y[k * b:(k + 1) * b]
+        ld = next(iter(done.values())).shape[-1]
+        if encode:
+            out = torch.empty(b, plan["out_h"], plan["out_w"], ld, dtype=F32, device=self.device)
+        else:
+            out = torch.empty(b, c_out, plan["out_h"], plan["out_w"], dtype=F32, device=self.device)
+        for t in plan["tiles"]:
+            i, j = t["i"], t["j"]
+            tile = done[(i, j)]
+            if tuple(tile.shape[1:3]) != (t["out_h"], t["out_w"]):
+                raise RuntimeError(f"tile ({i}, {j}): the {'encoder' if encode else 'decoder'} returned {tuple(tile.shape[1:3])}, "
+                                   f"the plan says {(t['out_h'], t['out_w'])}")
+            hip.vae_tile_blend(tile, done.get((i - 1, j)), done.get((i, j - 1)), plan["blend_extent"], plan["row_limit"], c_out, out,
+                               t["oy"], t["ox"], nhwc=encode)
+        return out
+
+    def _decode_body(self, h: torch.Tensor, conv_out: str = "decoder.conv_out") -> torch.Tensor:
+        """post_quant_conv + decoder on packed latents: NHWC [B, h, w, lat_pad] in the activation dtype -> fp32 NHWC image
+        (`conv_out`: the tiled path's padded copy of the last conv, see _prepare)."""
         c = self.config
         n = len(c["block_out_channels"])
         hip.TUNE_CTX = None                                      # the VAE's tune keys carry no position tag
-        h = from_nchw(z.to(self.device).float(), self.prec, self.lat_pad)
         h = ops.conv2d(h, self.P["post_quant_conv"], padding=0)
         h = ops.conv2d(h, self.P["decoder.conv_in"], gn_part=self.config["norm_num_groups"])
         h = self._mid("decoder.mid_block.", h)
@@ -1778,6 +1964,4 @@ class AutoencoderKL(HipModel):
                 h = ops.conv2d(h, self.P[f"decoder.up_blocks.{i}.upsamplers.0.conv"], upsample=True, gn_part=self.config["norm_num_groups"])
         h = ops.groupnorm(h, self.P["decoder.conv_norm_out"], groups=c["norm_num_groups"], eps=1e-6, silu=True,
                           out_dtype=self.prec.act)
-        y = ops.conv2d(h, self.P["decoder.conv_out"], out_dtype=F32)
-        img = hip.unpack_nchw(y, c["out_channels"])
-        return DecoderOutput(sample=img) if return_dict else (img,)
+        return ops.conv2d(h, self.P[conv_out], out_dtype=F32)

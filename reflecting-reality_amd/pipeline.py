@@ -14,6 +14,7 @@ the pipeline a transformers `text_encoder` + `tokenizer` pair.
 """
 from __future__ import annotations
 
+import gc
 import os
 import time
 
@@ -272,9 +273,9 @@ class StableDiffusionBrushNetPipeline:
     def set_progress_bar_config(self, **kwargs):
         self._progress_bar_config = kwargs
 
-    # Memory-saving switches of DiffusionPipeline (pipelines/pipeline_utils.py:940-1683).  None of them changes a result in
-    # the reference; with 288 GB of HBM per GPU the modules simply stay resident, so they are accepted and do nothing
-    # (test_brushnet.py:160 carries a commented-out enable_model_cpu_offload()).
+    # Memory-saving switches of DiffusionPipeline (pipelines/pipeline_utils.py:940-1683).  The offload, attention-slicing and
+    # xformers ones never change a result in the reference; with 288 GB of HBM per GPU the modules simply stay resident, so they
+    # are accepted and do nothing (test_brushnet.py:160 carries a commented-out enable_model_cpu_offload()).
     def enable_model_cpu_offload(self, gpu_id=None, device="cuda"):
         return None
 
@@ -287,17 +288,24 @@ class StableDiffusionBrushNetPipeline:
     def disable_attention_slicing(self):
         return None
 
+    # The two VAE switches are forwarded (pipeline_utils / pipeline_brushnet.py enable_vae_slicing .. disable_vae_tiling call the
+    # VAE's): tiling changes the result above the VAE's tile threshold, exactly as in the reference.
+    def _vae_switch(self, name: str) -> None:
+        fn = getattr(self.vae, name, None)
+        if callable(fn):
+            fn()
+
     def enable_vae_slicing(self):
-        return None
+        self._vae_switch("enable_slicing")
 
     def disable_vae_slicing(self):
-        return None
+        self._vae_switch("disable_slicing")
 
     def enable_vae_tiling(self):
-        return None
+        self._vae_switch("enable_tiling")
 
     def disable_vae_tiling(self):
-        return None
+        self._vae_switch("disable_tiling")
 
     def enable_xformers_memory_efficient_attention(self, attention_op=None):
         return None
@@ -842,6 +850,12 @@ class StableDiffusionBrushNetPipeline:
                     # export_denoise_step(): the captured pass is ALSO written down as a step program (program.py)
                     rec = self._export_recorder(st, lat, coef_cur, temb_u, temb_b, cond, coefs, fused_ddim, plan) if export is not None else None
                     self._overlap(True)                      # the side stream forks from / joins the capture stream
+                    # No automatic garbage collection inside the capture: a collection that falls into it runs the destructors of
+                    # whatever cyclic garbage the process holds (graphs, memory pools, events of earlier calls), and a HIP call made
+                    # from one of them while the stream captures ends the process.  torch.cuda.graph collects once on entry; what
+                    # becomes garbage during the capture waits until it has ended.
+                    gc_was_enabled = gc.isenabled()
+                    gc.disable()
                     try:
                         # (thread_local: with an initialised process group its watchdog thread may poll events while this thread captures)
                         with torch.cuda.graph(graph, capture_error_mode="thread_local" if (torch.distributed.is_available() and torch.distributed.is_initialized()) else "global"):
@@ -855,6 +869,8 @@ class StableDiffusionBrushNetPipeline:
                             raise rec.error                  # (not the "unjoined work" the aborted capture reports on top of it)
                         raise
                     finally:
+                        if gc_was_enabled:
+                            gc.enable()
                         self._overlap(False)
                     st["graph"] = graph                      # capture does not execute: replay below runs this step
                     if rec is not None:                      # (so the buffers still hold what they held BEFORE the recorded step)
@@ -939,6 +955,15 @@ class StableDiffusionBrushNetPipeline:
         return self._export_info
 
     # ---- the two ends of a call as step programs (program.py; include/mfhip.h "step programs") --------------------------------
+    def _refuse_vae_switches(self, what: str, batch: int, height: int, width: int, decode: bool = True) -> None:
+        """NotImplementedError if VAE tiling / slicing is on and would apply to the exported encode (pixels) or decode (latents)."""
+        refuse = getattr(self.vae, "refuse_export", None)
+        if refuse is None:
+            return
+        refuse(what, batch, int(height), int(width), latents=False)
+        if decode:
+            refuse(what, batch, int(height) // self.vae_scale_factor, int(width) // self.vae_scale_factor, latents=True)
+
     def _u8_pixels(self, x, name: str) -> torch.Tensor:
         from . import program
         t = torch.as_tensor(np.asarray(x)) if not torch.is_tensor(x) else x
@@ -970,6 +995,7 @@ class StableDiffusionBrushNetPipeline:
             raise program.ProgramError(f"image {tuple(image_u8.shape)} and mask {tuple(mask_u8.shape)} differ in shape")
         nb = image_u8.shape[0] * int(num_images_per_prompt)
         height, width = height or int(image_u8.shape[1]), width or int(image_u8.shape[2])
+        self._refuse_vae_switches("export_conditioning", nb, height, width, decode=False)
         noise = conditioning_noise.to(self.device, torch.float32).contiguous()
         if noise.shape[0] not in (nb, 2 * nb):
             raise ValueError(f"conditioning_noise must have batch {nb} (one draw shared by both guidance halves) or {2 * nb}")
@@ -1020,6 +1046,12 @@ class StableDiffusionBrushNetPipeline:
         kw = dict(call_kwargs)
         if float(kw.get("guidance_scale", 7.5)) <= 1:
             raise program.ProgramError("export_call: the exported call runs under classifier-free guidance (guidance_scale > 1)")
+        px = kw.get("image")
+        if px is not None:                                   # before any file is written: no partial export
+            shape = tuple(px.shape) if torch.is_tensor(px) else np.asarray(px).shape
+            if len(shape) in (3, 4):
+                self._refuse_vae_switches("export_call", (1 if len(shape) == 3 else shape[0]) * int(kw.get("num_images_per_prompt", 1) or 1),
+                                          kw.get("height") or shape[-3], kw.get("width") or shape[-2])
         if not isinstance(self.text_encoder, CLIPTextModel) or self.tokenizer is None or kw.get("prompt") is None:
             raise program.ProgramError("export_call needs the HIP text encoder (text_encoder.CLIPTextModel), a tokenizer and `prompt`")
         prompt, nipp = kw.pop("prompt"), int(kw.get("num_images_per_prompt", 1) or 1)

@@ -695,6 +695,7 @@ def export_vae_decode(vae, path: str, z: torch.Tensor, postprocess: bool = False
     "latents"); the program divides them by the scaling factor (:1342), decodes, and appends VaeImageProcessor.postprocess
     (mf_postprocess: denormalise, clamp, round to uint8 NHWC) into the io buffer "image_u8" [B][H][W][3]."""
     import json
+    vae.refuse_export("export_vae_decode", z.shape[0], z.shape[-2], z.shape[-1], latents=True)
     z = z.to(vae.device).float().contiguous()
     if postprocess:
         sf = float(vae.config["scaling_factor"])
@@ -724,6 +725,7 @@ def export_vae_encode(vae, path: str, image: torch.Tensor) -> dict:
     """AutoencoderKL.encode up to the moments (autoencoder_kl.py:256-291) as a program for mf_vae_encode_moments: io buffers "image" (NCHW
     fp32) and "moments" (NHWC fp32 mean | logvar; mf_vae_sample draws the posterior sample from it, pipeline_brushnet.py:1188)."""
     import json
+    vae.refuse_export("export_vae_encode", image.shape[0], image.shape[-2], image.shape[-1], latents=False)
     image = image.to(vae.device).float().contiguous()
     vae._moments(image)
     with Recorder(dict(image=image)) as rec:

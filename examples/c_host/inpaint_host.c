@@ -14,11 +14,14 @@
  *   gcc -O2 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude examples/c_host/inpaint_host.c \
  *       -Lreflecting-reality_amd/lib -lmfhip -L/opt/rocm/lib -lamdhip64 -o inpaint_host
  *   LD_LIBRARY_PATH=reflecting-reality_amd/lib:/opt/rocm/lib ./inpaint_host call_dir --ids ids.bin --image image.bin --mask mask.bin
- *       [--depth depth.bin] --noise noise.bin --latents latents.bin --out image_out.bin [--latents-out latents_out.bin] [--graph]
+ *       [--depth depth.bin] (--noise noise.bin --latents latents.bin | --seed N) --out image_out.bin [--latents-out latents_out.bin] [--graph]
  *
  * Raw files, each exactly the size of its io buffer: ids int32; image / mask uint8 HWC; depth fp32 in [-1, 1]; noise fp32 (the VAE
  * posterior noise, B or 2B images as exported: manifest key cond_noise_batch); latents fp32 (the initial noise).  Tokenising, decoding
- * image files and drawing random numbers stay the caller's.  Everything that can be checked on the host — the manifest, the five
+ * image files stay the caller's; so do the random numbers, unless --seed N draws them here: the library's own stream (mfhip.h, "random
+ * numbers") from generator (N, 0), in the order pipe(generator=PhiloxGenerator(N)) draws — the posterior noise (cond_noise_batch samples,
+ * mf_philox_normal straight into "cond_noise"), then the latents (batch samples, scale init_noise_sigma, straight into "latents") at the
+ * offset the first draw ends on — so the image is that call's, bit for bit.  Everything that can be checked on the host — the manifest, the five
  * headers, every input's size — is checked BEFORE the device is touched; after that every mf_* and hip* status is checked and the
  * first failure ends the process with a non-zero status.  --graph: the step is captured into a hipGraph once and replayed. */
 #include <hip/hip_runtime_api.h>
@@ -180,21 +183,26 @@ static int prog_close(host_prog* h) {
 
 int main(int argc, char** argv) {
     const char *ids_path = NULL, *image_path = NULL, *mask_path = NULL, *depth_path = NULL, *noise_path = NULL, *lat_path = NULL, *out_path = NULL,
-               *lat_out_path = NULL;
+               *lat_out_path = NULL, *seed_s = NULL;
     int use_graph = 0, a;
     if (argc < 2) {
-        fprintf(stderr, "usage: %s call_dir --ids F --image F --mask F [--depth F] --noise F --latents F --out F [--latents-out F] [--graph]\n", argv[0]);
+        fprintf(stderr, "usage: %s call_dir --ids F --image F --mask F [--depth F] (--noise F --latents F | --seed N) --out F [--latents-out F] [--graph]\n", argv[0]);
         return 2;
     }
     for (a = 2; a < argc; ++a) {
         const char** dst = !strcmp(argv[a], "--ids") ? &ids_path : !strcmp(argv[a], "--image") ? &image_path : !strcmp(argv[a], "--mask") ? &mask_path
                          : !strcmp(argv[a], "--depth") ? &depth_path : !strcmp(argv[a], "--noise") ? &noise_path : !strcmp(argv[a], "--latents") ? &lat_path
-                         : !strcmp(argv[a], "--out") ? &out_path : !strcmp(argv[a], "--latents-out") ? &lat_out_path : NULL;
+                         : !strcmp(argv[a], "--out") ? &out_path : !strcmp(argv[a], "--latents-out") ? &lat_out_path
+                         : !strcmp(argv[a], "--seed") ? &seed_s : NULL;
         if (!strcmp(argv[a], "--graph")) use_graph = 1;
         else if (dst && a + 1 < argc) *dst = argv[++a];
         else { fprintf(stderr, "unknown or incomplete argument %s\n", argv[a]); return 2; }
     }
     if (!out_path) { fprintf(stderr, "--out image_out.bin is needed\n"); return 2; }
+    if (seed_s && (noise_path || lat_path)) { fprintf(stderr, "--seed draws the noise and the latents: give it OR --noise / --latents\n"); return 2; }
+    char* seed_end = NULL;
+    const int64_t seed = seed_s ? (int64_t)strtoull(seed_s, &seed_end, 0) : 0;        /* any 64 bits: the library reads them unsigned */
+    if (seed_s && (seed_end == seed_s || *seed_end)) { fprintf(stderr, "--seed %s is not an integer\n", seed_s); return 2; }
 
     /* ---- host only: manifest, headers, inputs ---------------------------------------------------------------------------------- */
     static mf_manifest man;
@@ -234,10 +242,25 @@ int main(int argc, char** argv) {
     TRY(read_input(mask_path, &cond, "mask_u8", &h_mask, &n_mask));
     if (has_depth) TRY(read_input(depth_path, &cond, "depth", &h_depth, &n_depth));
     else if (depth_path) { fprintf(stderr, "--depth given, but the call was exported without depth conditioning\n"); return 1; }
-    TRY(read_input(noise_path, &cond, "cond_noise", &h_noise, &n_noise));
-    TRY(read_input(lat_path, &step, "latents", &h_lat, &n_lat));
+    long long nb = 0, noise_b = 0;
+    if (seed_s) {
+        /* the draws are per sample: the sample counts come from the manifest, the sample sizes from the io buffers */
+        h_noise = NULL;
+        n_noise = io_bytes(&cond, "cond_noise");
+        n_lat = io_bytes(&step, "latents");
+        if (mf_manifest_int(&man, "batch", &nb) != 0 || mf_manifest_int(&man, "cond_noise_batch", &noise_b) != 0 || nb < 1 || noise_b < 1 ||
+            n_noise <= 0 || n_noise % (4 * noise_b) || n_lat % (4 * nb)) {
+            fprintf(stderr, "%s: keys batch / cond_noise_batch missing, or they do not divide the cond_noise / latents buffers\n", mpath);
+            return 1;
+        }
+        h_lat = malloc((size_t)n_lat);               /* the final latents come back through it (--latents-out) */
+        if (!h_lat) return 1;
+    } else {
+        TRY(read_input(noise_path, &cond, "cond_noise", &h_noise, &n_noise));
+        TRY(read_input(lat_path, &step, "latents", &h_lat, &n_lat));
+    }
     if (n_out <= 0) { fprintf(stderr, "%s: no io buffer image_u8\n", dec.path); return 1; }
-    if (sigma != 1.0f) {                      /* prepare_latents (pipeline_brushnet.py:777-791): latents * scheduler.init_noise_sigma */
+    if (!seed_s && sigma != 1.0f) {                      /* prepare_latents (pipeline_brushnet.py:777-791): latents * scheduler.init_noise_sigma */
         int64_t i;
         for (i = 0; i < n_lat / 4; ++i) ((float*)h_lat)[i] *= sigma;
     }
@@ -278,7 +301,8 @@ int main(int argc, char** argv) {
     HIP_OK(hipMemcpyAsync(io_ptr(&cond, "image_u8"), h_image, (size_t)n_image, hipMemcpyHostToDevice, stream));
     HIP_OK(hipMemcpyAsync(io_ptr(&cond, "mask_u8"), h_mask, (size_t)n_mask, hipMemcpyHostToDevice, stream));
     if (has_depth) HIP_OK(hipMemcpyAsync(io_ptr(&cond, "depth"), h_depth, (size_t)n_depth, hipMemcpyHostToDevice, stream));
-    HIP_OK(hipMemcpyAsync(io_ptr(&cond, "cond_noise"), h_noise, (size_t)n_noise, hipMemcpyHostToDevice, stream));
+    if (seed_s) MF_OKAY(mf_philox_normal((float*)io_ptr(&cond, "cond_noise"), noise_b, n_noise / (4 * noise_b), 1.0f, 0, noise_b, seed, 0, NULL, stream));
+    else HIP_OK(hipMemcpyAsync(io_ptr(&cond, "cond_noise"), h_noise, (size_t)n_noise, hipMemcpyHostToDevice, stream));
     /* NULL arguments: the bindings made by prog_place stay */
     MF_OKAY(mf_encode_prompt(enc.p, NULL, NULL, stream));
     MF_OKAY(mf_program_run(bind.p, stream));
@@ -296,7 +320,10 @@ int main(int argc, char** argv) {
         HIP_OK(hipStreamEndCapture(stream, &graph));
         HIP_OK(hipGraphInstantiateWithFlags(&exec, graph, hipGraphInstantiateFlagAutoFreeOnLaunch));
     }
-    HIP_OK(hipMemcpyAsync(io_ptr(&step, "latents"), h_lat, (size_t)n_lat, hipMemcpyHostToDevice, stream));
+    if (seed_s)
+        MF_OKAY(mf_philox_normal((float*)io_ptr(&step, "latents"), nb, n_lat / (4 * nb), sigma, 0, nb, seed,
+                                 mf_philox_normal_blocks(noise_b, n_noise / (4 * noise_b)), NULL, stream));
+    else HIP_OK(hipMemcpyAsync(io_ptr(&step, "latents"), h_lat, (size_t)n_lat, hipMemcpyHostToDevice, stream));
     int s;
     for (s = 0; s < steps; ++s) {
         for (a = 0; a < ntab; ++a)

@@ -936,6 +936,52 @@ int mf_decode_image(mf_program* decoder, const void* latents, void* image_u8, vo
 int mf_memcpy2d(void* dst, int64_t dpitch, const void* src, int64_t spitch, int64_t width_bytes, int64_t height, void* stream);
 int mf_memset(void* dst, int32_t value, int64_t bytes, void* stream);
 
+/* ---- random numbers: one counter-based stream, the same from Python and from C (csrc/rng.hip; appended, ABI stays 23) -----------
+ * GENERATOR  Philox4x32-10 with the standard constants: multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85,
+ *            10 rounds.  Key = (seed low 32 bits, seed high 32 bits) of a 64-bit seed; counter = (block low 32, block high 32, 0, 0)
+ *            of a 64-bit block index.  A generator is the pair (seed, offset), offset counted in blocks; one block yields four uint32
+ *            values x0..x3, the lanes.  Nothing else enters: not the grid, the device or the number of ranks.  (seed and offset
+ *            travel as int64_t and are read as the same 64 bits unsigned: seed 2^63 + 1 is passed as -(2^63 - 1).)
+ * BITS       Element i of a draw that starts at offset o is lane i % 4 of block o + i / 4; n elements advance the offset by
+ *            ceil(n / 4).
+ * NORMALS    Lanes (0, 1) give one Box-Muller pair, lanes (2, 3) the next.  u = ((xa >> 9) + 0.5f) * 2^-23 and
+ *            phi = ((xb >> 9) + 0.5f) * 2^-23, both exact in fp32, u in (0, 1); s = sqrtf(-2.0f * logf(u)); the pair is
+ *            (s * cospif(2 * phi), s * sinpif(2 * phi)), then times `scale`, each product rounded once.  The accurate math functions,
+ *            fp32 out; the largest magnitude is sqrt(-2 ln 2^-24) = 5.768 (times scale).  A tensor [B, ...] is drawn PER SAMPLE: with
+ *            `per` elements to a sample, sample s starts at block o + s * ceil(per / 4), and the draw advances the offset by
+ *            B * ceil(per / 4).  So a rank that owns the samples [first, first + b) of a global batch G draws exactly those rows
+ *            (first_sample = first, samples = b, global_batch = G), and every rank advances by G * ceil(per / 4).
+ * INTEGERS   below T, 0 < T <= 2^31: element i takes its lane x as for bits and yields (uint64(x) * T) >> 32, as int64.  There is no
+ *            rejection step: a value's probability differs from 1 / T by at most 2^-32, a relative bias of at most T / 2^32.
+ *            [first, first + n) of a draw of `total` elements is a rank's slice; the draw advances by ceil(total / 4).
+ * STATE      Every draw takes (seed, offset) as host values and an optional `state` in device memory, uint64 {seed, offset}; a
+ *            non-null state overrides the host values (a captured graph reads it at every replay).  A draw never writes the state
+ *            (all its blocks read it): mf_philox_advance, one tiny launch on the same stream, follows the draws.
+ * Normals are device-only (the host's libm would not match the device bit for bit); bits are also computed on the host. */
+/* blocks a [samples, per_sample] normal draw / an n-element integer or bits draw consumes; -1 (mf_last_error) for a negative count */
+int64_t mf_philox_normal_blocks(int64_t samples, int64_t per_sample);
+int64_t mf_philox_int_blocks(int64_t n);
+/* the raw bits on the host, from the very block function the kernels run (no GPU, no HIP call) */
+int mf_philox_bits_host(uint32_t* out, int64_t n, int64_t seed, int64_t offset);
+int mf_philox_bits(uint32_t* out, int64_t n, int64_t seed, int64_t offset, const uint64_t* state, void* stream);
+/* out: fp32 [samples][per_sample], the rows [first_sample, first_sample + samples) of a draw of global_batch rows */
+int mf_philox_normal(float* out, int64_t samples, int64_t per_sample, float scale, int64_t first_sample, int64_t global_batch,
+                     int64_t seed, int64_t offset, const uint64_t* state, void* stream);
+/* out: int64 [n], the elements [first, first + n) of a draw of `total` integers below T */
+int mf_philox_randint(int64_t* out, int64_t n, int64_t T, int64_t first, int64_t total, int64_t seed, int64_t offset,
+                      const uint64_t* state, void* stream);
+/* state[1] += blocks, on the stream (after the draws that read the state) */
+int mf_philox_advance(uint64_t* state, int64_t blocks, void* stream);
+/* Everything mf_train_batch_assemble reads as random input, in ONE launch: the posterior noises of the present sources
+ * (posterior_noise: a host array of nsrc device pointers in the order image, conditioning image, depth, normals; entries 2 and 3 may be
+ * NULL), then `noise` — each fp32 [samples][per_sample], per_sample = c * h * w — then `timesteps` (int64 [samples], below T).  The
+ * offsets are consecutive, as if mf_philox_normal had been called once per present source and once for the noise, then
+ * mf_philox_randint(first = first_sample, total = global_batch): the launch consumes
+ * (present sources + 1) * mf_philox_normal_blocks(global_batch, per_sample) + mf_philox_int_blocks(global_batch) blocks. */
+int mf_train_batch_draw(float* const* posterior_noise, int32_t nsrc, float* noise, int64_t* timesteps, int64_t samples,
+                        int64_t per_sample, int64_t T, int64_t first_sample, int64_t global_batch, int64_t seed, int64_t offset,
+                        const uint64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

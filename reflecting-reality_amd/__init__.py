@@ -16,6 +16,7 @@ Sub-modules:
   text_encoder  CLIPTextModel, CLIPTextModelWithProjection (the prompt encoders of both pipelines)
   image_encoder  CLIPVisionModel, CLIPVisionModelWithProjection, CLIPModel (the scorer of CLIP_Similarity)
   lpips      LPIPS (net_type="squeeze": squeezenet1_1.features and the seven layer distances)
+  rng        randn_tensor (torch generators, as the reference draws) and PhiloxGenerator, the library's own counter-based stream
 """
 __version__ = "0.1.0"
 
@@ -28,7 +29,7 @@ _LAZY = {
     "MfhipAttnProcessor": "attn_processor", "MfhipIPAttnProcessor": "attn_processor", "StableDiffusionBrushNetPipeline": "pipeline", "StableDiffusionXLBrushNetPipeline": "pipeline", "StableDiffusionPipelineOutput": "pipeline",
     "VaeImageProcessor": "pipeline", "Precision": "ops", "CLIPTextModel": "text_encoder", "CLIPTextModelWithProjection": "text_encoder",
     "CLIPVisionModel": "image_encoder", "CLIPVisionModelWithProjection": "image_encoder", "CLIPModel": "image_encoder",
-    "LPIPS": "lpips",
+    "LPIPS": "lpips", "PhiloxGenerator": "rng", "randn_tensor": "rng",
 }
 
 

@@ -215,6 +215,10 @@ SIGNATURES = {
     "mf_brushnet_forward": "i:pppppip", "mf_vae_decode": "i:pppp", "mf_vae_encode_moments": "i:pppp",
     # the two ends of a call as step programs (program.export_encode_prompt / pipeline.export_conditioning / export_vae_decode(postprocess=True))
     "mf_encode_prompt": "i:pppp", "mf_build_conditioning": "i:ppppppp", "mf_decode_image": "i:pppp",
+    # random numbers (csrc/rng.hip)
+    "mf_philox_normal_blocks": "l:ll", "mf_philox_int_blocks": "l:l", "mf_philox_bits_host": "i:plll", "mf_philox_bits": "i:plllpp",
+    "mf_philox_normal": "i:pllfllllpp", "mf_philox_randint": "i:pllllllpp", "mf_philox_advance": "i:plp",
+    "mf_train_batch_draw": "i:pipplllllllpp",
 }
 EXPORTS = list(SIGNATURES)
 # (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
@@ -1721,6 +1725,126 @@ def train_batch_assemble(moments, posterior_noise, c: int, scaling: float, noise
             sqrt_one_minus_alpha, loss_weight, t_len, masks, depths, normals, ph, pw, int(bool(v_prediction)), res["latents"],
             res["noisy_latents"], res["target"], res["conditioning_latents"], res["timesteps_f32"], res.get("loss_weights"))
     return res
+
+
+# ---- random numbers (csrc/rng.hip; include/mfhip.h states the stream; rng.PhiloxGenerator keeps the (seed, offset) pair) ---------------
+def _s64(v: int) -> int:
+    """A 64-bit value as the int64_t the ABI carries it in (2^63 + 1 -> -(2^63 - 1)): the library reads the same 64 bits unsigned."""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >> 63 else v
+
+
+def _philox_state(state: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if state is not None and (not state.is_cuda or state.dtype != torch.int64 or state.numel() != 2 or not state.is_contiguous()):
+        raise MfhipError("a Philox device state is a contiguous int64 device tensor {seed, offset}")
+    return state
+
+
+def _count(what: str, **counts) -> None:
+    """Counts are checked here, before an empty tensor's null address could speak for them; an empty draw launches nothing."""
+    bad = {k: v for k, v in counts.items() if int(v) < 0}
+    if bad:
+        raise MfhipError(f"{what}: {', '.join(f'{k} = {v}' for k, v in bad.items())} must not be negative")
+
+
+def philox_normal_blocks(samples: int, per_sample: int) -> int:
+    n = load().mf_philox_normal_blocks(samples, per_sample)
+    _check(-1 if n < 0 else 0, "mf_philox_normal_blocks")
+    return n
+
+
+def philox_int_blocks(n: int) -> int:
+    r = load().mf_philox_int_blocks(n)
+    _check(-1 if r < 0 else 0, "mf_philox_int_blocks")
+    return r
+
+
+def philox_bits_host(n: int, seed: int, offset: int = 0) -> torch.Tensor:
+    """The stream's raw bits computed on the host (mf_philox_bits_host): an int32 host tensor holding the uint32 bit patterns."""
+    _count("philox_bits_host", n=n)
+    out = torch.empty(int(n), dtype=torch.int32)
+    if n:
+        _check(load().mf_philox_bits_host(out.data_ptr(), n, _s64(seed), _s64(offset)), "mf_philox_bits_host")
+    return out
+
+
+def philox_bits(n: int, seed: int, offset: int, device, state: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """n raw uint32 of the stream as an int32 device tensor (the bit patterns); `state` overrides (seed, offset)."""
+    _count("philox_bits", n=n)
+    out = torch.empty(int(n), dtype=torch.int32, device=device)
+    _req_cuda(out, state)
+    if n:
+        _launch("mf_philox_bits", out, n, _s64(seed), _s64(offset), _philox_state(state))
+    return out
+
+
+def philox_normal(shape, seed: int, offset: int, device, scale: float = 1.0, first_sample: int = 0, global_batch: Optional[int] = None,
+                  state: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 normals of shape [B, ...], drawn per sample: the rows [first_sample, first_sample + B) of a draw of global_batch rows."""
+    shape = tuple(int(d) for d in shape)
+    if not shape:
+        raise MfhipError("philox_normal: a shape [B, ...] is needed (the draw is per sample)")
+    b = shape[0]
+    per = 1
+    for d in shape[1:]:
+        per *= d
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise MfhipError(f"philox_normal: out must be a contiguous fp32 tensor of shape {shape}")
+    _req_cuda(out, state)
+    g = b + first_sample if global_batch is None else int(global_batch)
+    _count("philox_normal", first_sample=first_sample)
+    if g < first_sample + b:
+        raise MfhipError(f"philox_normal: global_batch {g} < first_sample {first_sample} + samples {b}")
+    if out.numel():
+        _launch("mf_philox_normal", out, b, per, float(scale), first_sample, g, _s64(seed), _s64(offset), _philox_state(state))
+    return out
+
+
+def philox_randint(high: int, n: int, seed: int, offset: int, device, first: int = 0, total: Optional[int] = None,
+                   state: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [n] below `high`: the elements [first, first + n) of a draw of `total` integers."""
+    _count("philox_randint", n=n, first=first)
+    total = first + n if total is None else int(total)
+    if not 0 < high <= 1 << 31 or total < first + n:
+        raise MfhipError(f"philox_randint: high = {high} outside (0, 2^31], or total {total} < first {first} + n {n}")
+    if out is None:
+        out = torch.empty(int(n), dtype=torch.int64, device=device)
+    elif out.dtype != torch.int64 or out.numel() != n or not out.is_contiguous():
+        raise MfhipError(f"philox_randint: out must be a contiguous int64 tensor of {n} entries")
+    _req_cuda(out, state)
+    if n:
+        _launch("mf_philox_randint", out, n, high, first, total, _s64(seed), _s64(offset), _philox_state(state))
+    return out
+
+
+def philox_advance(state: torch.Tensor, blocks: int) -> None:
+    _req_cuda(state)
+    _launch("mf_philox_advance", _philox_state(state), blocks)
+
+
+def train_batch_draw(posterior_noise, noise: torch.Tensor, timesteps: torch.Tensor, high: int, seed: int, offset: int, first_sample: int = 0,
+                     global_batch: Optional[int] = None, state: Optional[torch.Tensor] = None) -> int:
+    """Everything train_batch_assemble reads as random input in one launch (mf_train_batch_draw): posterior_noise is 2 .. 4 fp32
+    [B, c, h, w] tensors to fill (image, conditioning image, depth, normals; the last two may be None), then noise, then timesteps
+    (int64 [B], below `high`).  Returns the blocks the draw consumes (what the generator advances by)."""
+    pns = list(posterior_noise)
+    if not 2 <= len(pns) <= 4 or pns[0] is None or pns[1] is None:
+        raise MfhipError("train_batch_draw: 2 .. 4 posterior noise tensors, the image's and the conditioning image's present")
+    b = noise.shape[0]
+    per = noise.numel() // max(b, 1)
+    for t in (*pns, noise):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != tuple(noise.shape) or not t.is_contiguous()):
+            raise MfhipError(f"train_batch_draw: every noise tensor must be contiguous fp32 {tuple(noise.shape)}")
+    if timesteps.dtype != torch.int64 or timesteps.numel() != b or not timesteps.is_contiguous():
+        raise MfhipError(f"train_batch_draw: timesteps is a contiguous int64 tensor of {b} entries")
+    _req_cuda(*pns, noise, timesteps, state)
+    g = b + first_sample if global_batch is None else global_batch
+    if noise.numel():
+        arr = (C.c_void_p * len(pns))(*[_ptr(p) for p in pns])
+        _launch("mf_train_batch_draw", arr, len(pns), noise, timesteps, b, per, high, first_sample, g, _s64(seed), _s64(offset), _philox_state(state))
+    return (sum(1 for p in pns if p is not None) + 1) * philox_normal_blocks(g, per) + philox_int_blocks(g)
 
 
 def postprocess(x: torch.Tensor, denormalize: bool = True, uint8: bool = False) -> torch.Tensor:

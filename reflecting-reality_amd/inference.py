@@ -33,12 +33,17 @@ def run_sharded(pipe, samples: Sequence[Dict], *, seed: int = 0, num_images_per_
     """Runs this rank's share of `samples` (dicts of pipeline kwargs: image, mask, depth / normals, prompt_embeds, ...).
     Returns {sample index: [images]} for the samples this rank owns; `on_result(index, images)` is called as each sample
     finishes (the script saves its image grid there), `on_image(index, k, image)` as each of its images is produced
-    (validate() scores it there)."""
+    (validate() scores it there).  generator_device: "cuda" / "cpu" for a torch.Generator there (default: the pipeline's device), or
+    "philox" for a rng.PhiloxGenerator: conditioning noise and latents then both come from it, on the device."""
     if rank is None or world is None:
         rank, world, _ = D.env_rank_world()
     lo, hi = D.shard_range(len(samples), rank, world)
     gdev = generator_device or (str(pipe.device) if torch.device(pipe.device).type == "cuda" else "cpu")
-    generator = torch.Generator(gdev).manual_seed(seed)                      # one generator per rank, drawn from in sequence
+    if gdev == "philox":                                                     # the library's own stream (rng.PhiloxGenerator), drawn on the device
+        from .rng import PhiloxGenerator
+        generator = PhiloxGenerator(seed, pipe.device)
+    else:
+        generator = torch.Generator(gdev).manual_seed(seed)                  # one generator per rank, drawn from in sequence
     out: Dict[int, List] = {}
     for i in range(lo, hi):
         kw = dict(samples[i])

@@ -26,7 +26,7 @@ import torch
 
 from . import hip
 from .models import AutoencoderKL, BrushNetModel, UNet2DConditionModel
-from .rng import randn_tensor
+from .rng import PhiloxGenerator, is_philox, randn_tensor
 from .schedulers import DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler, device_plan
 
 try:
@@ -422,6 +422,11 @@ class StableDiffusionBrushNetPipeline:
         if isinstance(generator, list) and len(generator) != batch_size:
             raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an "
                              f"effective batch size of {batch_size}. Make sure the batch size matches the length of the generators.")
+        if latents is None and isinstance(generator, PhiloxGenerator):
+            # the library's stream: drawn on the device, init_noise_sigma applied by the draw itself (one rounding, as axpby_n's)
+            generator.device = generator.device or torch.device(self.device)
+            noise = generator.randn(shape, scale=float(self.scheduler.init_noise_sigma))
+            return noise, noise
         if latents is None:
             noise = randn_tensor(shape, generator, self.device)      # on the generator's device, like randn_tensor
         else:
@@ -432,10 +437,11 @@ class StableDiffusionBrushNetPipeline:
         return noise.contiguous(), noise
 
     def build_conditioning(self, image, mask, depth, height, width, batch, num_images_per_prompt, do_cfg,
-                           conditioning_noise=None, normals=None):
+                           conditioning_noise=None, normals=None, generator=None):
         """pipeline_brushnet.py:1116-1215: [masked-image latents | mask | depth | normals] at latent resolution.
         `conditioning_noise`: the VAE posterior noise of the CFG-duplicated batch — one tensor (image) or a sequence
-        (image, depth, normals) for the 'latents' modes; None draws them in the reference's order from the global RNG."""
+        (image, depth, normals) for the 'latents' modes; None draws them in the reference's order from the global RNG, or, with a
+        rng.PhiloxGenerator (or a list of them, one per sample) as `generator`, from it on the device."""
         img = self.prepare_image(image, width, height, batch, num_images_per_prompt)
         m3 = self.prepare_image(mask, width, height, batch, num_images_per_prompt)
         original_mask = hip.mask_keep(m3) if m3.is_cuda else (m3.sum(1)[:, None, :, :] < 0).to(torch.float32)   # :1139 (1 = keep)
@@ -451,7 +457,17 @@ class StableDiffusionBrushNetPipeline:
             """vae.encode(x).latent_dist.sample() * scaling_factor for the CFG-duplicated batch: B images are encoded
             once and sampled once per CFG half (the reference encodes the duplicated batch, :1188)."""
             moments = self.vae._moments(x_host)
-            if noise is None:
+            if noise is None and philox:
+                # the same shapes and order as the global-RNG draws below; a list of generators draws each half sample by sample
+                if dup == 2 and self.cfg_shared_conditioning_sample:
+                    noise = randn_tensor((batch, lat_c, hl, wl), generator, self.device).repeat(2, 1, 1, 1)
+                elif isinstance(generator, (list, tuple)) and len(generator) > 1:
+                    noise = torch.cat([randn_tensor((batch, lat_c, hl, wl), generator, self.device) for _ in range(dup)])
+                    self._cond_halves_identical = False
+                else:
+                    noise = randn_tensor((dup * batch, lat_c, hl, wl), generator, self.device)
+                    self._cond_halves_identical = False
+            elif noise is None:
                 if dup == 2 and self.cfg_shared_conditioning_sample:
                     noise = torch.randn(batch, lat_c, hl, wl, dtype=torch.float32).repeat(2, 1, 1, 1)
                 else:
@@ -468,6 +484,7 @@ class StableDiffusionBrushNetPipeline:
             noise = noise.to(self.device, torch.float32)
             return [hip.vae_sample(moments, noise[i * batch:(i + 1) * batch].contiguous(), lat_c, sf) for i in range(dup)]
 
+        philox = is_philox(generator)
         self._cond_halves_identical = dup == 2
         halves = encode_sample(img, noises[0])
         parts = [[h] for h in halves]
@@ -566,7 +583,7 @@ class StableDiffusionBrushNetPipeline:
             height, width = height or int(hh), width or int(ww)
         # guess_mode (:771-772, 1260-1264): the conditioning is NOT doubled, BrushNet sees the conditional batch only
         cond = self.build_conditioning(image, mask, depth, height, width, nb, num_images_per_prompt, do_cfg and not guess_mode,
-                                       conditioning_noise, normals)
+                                       conditioning_noise, normals, generator=generator)
         self._brushnet_once = (not guess_mode) and self._brushnet_shareable(cond, nb, do_cfg)
 
         self.scheduler.set_timesteps(num_inference_steps, device=self.device)                       # :1171
@@ -714,9 +731,19 @@ class StableDiffusionBrushNetPipeline:
     def _overlap(self, on: bool):
         """Turn the BrushNet || UNet stream overlap (models._RESIDUAL_EVENTS) on or off for the next forward calls."""
         if on and self.overlap_brushnet and self.device.type == "cuda":
-            if self._side_stream is None or self._side_stream.device != self.device:
-                self._side_stream = torch.cuda.Stream(device=self.device)
-                self._aux_stream = torch.cuda.Stream(device=self.device)
+            # torch hands streams out of a pool of 32 per device, round robin: the 33rd torch.cuda.Stream of a process IS the first.
+            # A side stream that is the stream it forks from (torch.cuda.graph's capture stream is a pool stream too) would put
+            # BrushNet and the UNet back on one stream — no overlap, and a recorded step program with one stream — so pick again.
+            cur = torch.cuda.current_stream(self.device).cuda_stream
+            if self._side_stream is None or self._side_stream.device != self.device or cur in (self._side_stream.cuda_stream, self._aux_stream.cuda_stream):
+                taken = {cur}
+                for name in ("_side_stream", "_aux_stream"):
+                    for _ in range(64):
+                        stream = torch.cuda.Stream(device=self.device)
+                        if stream.cuda_stream not in taken:
+                            break
+                    taken.add(stream.cuda_stream)
+                    setattr(self, name, stream)
             self.brushnet.side_stream = self._side_stream
             # an auxiliary stream for UNet launches off its critical path (shortcut convs, V projections).  BrushNet
             # keeps a single stream: a fork of the already forked side stream segfaults in hipStreamEndCapture
@@ -859,6 +886,7 @@ class StableDiffusionBrushNetPipeline:
                     try:
                         # (thread_local: with an initialised process group its watchdog thread may poll events while this thread captures)
                         with torch.cuda.graph(graph, capture_error_mode="thread_local" if (torch.distributed.is_available() and torch.distributed.is_initialized()) else "global"):
+                            self._overlap(True)              # (again, now that the capture stream is current: never the side stream itself)
                             if rec is not None:
                                 with rec:
                                     one_step()

@@ -440,19 +440,59 @@ class BatchFrontEnd:
             normals = plane("normals")
         return [None if x is None else vae.encode(x).latent_dist.moments_nhwc for x in images], plane("masks"), depths, normals
 
-    def draw(self, batch: dict, latent_shape, noise=None, timesteps=None, posterior_noise=None, generator=None):
+    def sources_used(self) -> list:
+        """Which of (image, conditioning image, depth, normals) are VAE-encoded, so have posterior noise."""
+        return [True, True, self.depth_mode == "latents", self.normals_mode == "latents"]
+
+    def philox_shard(self, b: int, first_sample=None, global_batch=None):
+        """(first_sample, global_batch) of this rank's b samples: by default rank * b of world * b under `distributed`."""
+        if first_sample is None or global_batch is None:
+            from . import distributed as D
+            rank, world, _ = D.env_rank_world()
+            first_sample = rank * b if first_sample is None else first_sample
+            global_batch = max(world * b, first_sample + b) if global_batch is None else global_batch
+        return int(first_sample), int(global_batch)
+
+    def philox_draw(self, bufs, generator, first_sample: int, global_batch: int, state=None) -> int:
+        """The ONE launch (mf_train_batch_draw) that fills `bufs` = [posterior noise x 4 (None where absent), noise, timesteps] from a
+        rng.PhiloxGenerator: from its host (seed, offset), or from `state` (its device_state(), what a captured graph reads) followed
+        by the advance launch.  Returns the blocks consumed; moving the host offset is the caller's (generator.note_advanced)."""
+        blocks = hip.train_batch_draw(bufs[:4], bufs[4], bufs[5], int(self.ns.config["num_train_timesteps"]), generator.seed, generator.offset,
+                                      first_sample, global_batch, state=state)
+        if state is not None:
+            hip.philox_advance(state, blocks)
+        return blocks
+
+    def draw(self, batch: dict, latent_shape, noise=None, timesteps=None, posterior_noise=None, generator=None, first_sample=None,
+             global_batch=None):
         """The script's random draws (given ones are taken as they are) and the text encoder: -> (posterior noise [4, None where the
-        source is absent], noise, timesteps int64 [B] on the device, encoder_hidden_states or None)."""
-        from .rng import randn_tensor
+        source is absent], noise, timesteps int64 [B] on the device, encoder_hidden_states or None).  With a rng.PhiloxGenerator the
+        draws are one mf_train_batch_draw launch for the samples [first_sample, first_sample + B) of `global_batch` (philox_shard's
+        defaults); the generator advances by the whole draw whatever the caller passed, so given tensors do not shift the stream."""
+        from .rng import PhiloxGenerator, randn_tensor
         dev = self.vae.device
         shape = tuple(latent_shape)
         b = shape[0]
-        used = [True, True, self.depth_mode == "latents", self.normals_mode == "latents"]
+        used = self.sources_used()
         given = list(posterior_noise) if posterior_noise is not None else []
         given += [None] * (4 - len(given))
         on_dev = lambda t: hip.h2d(t, dev).float().contiguous()
-        pns = [None if not u else (on_dev(g) if g is not None else randn_tensor(shape, generator, dev)) for u, g in zip(used, given)]
-        noise = on_dev(noise) if noise is not None else randn_tensor(shape, generator, dev)                   # :1408
+        drawn = None
+        if isinstance(generator, PhiloxGenerator):
+            first, total = self.philox_shard(b, first_sample, global_batch)
+            if noise is not None and timesteps is not None and all(g is not None for u, g in zip(used, given) if u):
+                # everything is the caller's: nothing to launch, but the stream moves on as on the ranks that do draw
+                per = shape[1] * shape[2] * shape[3]
+                generator.note_advanced((sum(used) + 1) * hip.philox_normal_blocks(total, per) + hip.philox_int_blocks(total))
+            else:
+                f32 = dict(dtype=torch.float32, device=dev)
+                drawn = [torch.empty(shape, **f32) if u else None for u in used] + [torch.empty(shape, **f32), torch.empty(b, dtype=torch.int64, device=dev)]
+                generator.note_advanced(self.philox_draw(drawn, generator, first, total))
+                if timesteps is None:
+                    timesteps = drawn[5]
+        pick = lambda i: drawn[i] if drawn is not None else randn_tensor(shape, generator, dev)
+        pns = [None if not u else (on_dev(g) if g is not None else pick(i)) for i, (u, g) in enumerate(zip(used, given))]
+        noise = on_dev(noise) if noise is not None else pick(4)                                                # :1408
         if timesteps is None:                                                                                  # :1411-1412
             gen = generator if isinstance(generator, torch.Generator) and generator.device.type == "cuda" else None
             timesteps = torch.randint(0, self.ns.config["num_train_timesteps"], (b,), device=dev, generator=gen).long()
@@ -466,11 +506,13 @@ class BatchFrontEnd:
             ehs = self.text_encoder(batch["input_ids"], return_dict=False)[0]                                  # :1419
         return pns, noise, timesteps.reshape(-1), ehs
 
-    def encode(self, batch: dict, noise=None, timesteps=None, posterior_noise=None, generator=None) -> EncodedBatch:
+    def encode(self, batch: dict, noise=None, timesteps=None, posterior_noise=None, generator=None, first_sample=None,
+               global_batch=None) -> EncodedBatch:
         """Everything ahead of the assemble launch: the VAE encodes, the draws, the text encoder."""
         moments, masks, depths, normals = self.encode_images(batch)
         b, h, w, _ = moments[0].shape
-        pns, noise, timesteps, ehs = self.draw(batch, (b, self.latent_channels, h, w), noise, timesteps, posterior_noise, generator)
+        pns, noise, timesteps, ehs = self.draw(batch, (b, self.latent_channels, h, w), noise, timesteps, posterior_noise, generator,
+                                               first_sample, global_batch)
         return EncodedBatch(moments, pns, noise, timesteps, masks, depths, normals, ehs)
 
     def assemble(self, enc: EncodedBatch, out: Optional[dict] = None) -> dict:
@@ -480,11 +522,12 @@ class BatchFrontEnd:
                                         enc.timesteps, sa, sb, enc.masks, depths=enc.depths, normals=enc.normals, loss_weight=lw,
                                         v_prediction=self.ptype == "v_prediction", out=out)
 
-    def __call__(self, batch: dict, noise=None, timesteps=None, posterior_noise=None, generator=None, out: Optional[dict] = None) -> PreparedBatch:
+    def __call__(self, batch: dict, noise=None, timesteps=None, posterior_noise=None, generator=None, out: Optional[dict] = None,
+                 first_sample=None, global_batch=None) -> PreparedBatch:
         """`noise` [B, c, h, w], `timesteps` int64 [B] and `posterior_noise` (a list: image, conditioning image, depth, normals; None
         entries are drawn) may be passed for reproducibility.  `out`: caller-owned static buffers by name (hip.ASSEMBLE_OUTPUTS, and
         "encoder_hidden_states", which receives a copy of the text encoder's output)."""
-        enc = self.encode(batch, noise, timesteps, posterior_noise, generator)
+        enc = self.encode(batch, noise, timesteps, posterior_noise, generator, first_sample, global_batch)
         res = self.assemble(enc, out)
         ehs = enc.encoder_hidden_states
         if out is not None and out.get("encoder_hidden_states") is not None and ehs is not None:
@@ -736,17 +779,21 @@ class GraphedTrainStep:
                 self.lr_scheduler.step()
         return self.loss, self.norm
 
-    def from_pixels(self, batch: dict, noise=None, timesteps=None, posterior_noise=None, generator=None):
+    def from_pixels(self, batch: dict, noise=None, timesteps=None, posterior_noise=None, generator=None, first_sample=None,
+                    global_batch=None):
         """The step from a collated batch of pixels (frontend.training_example) through the BatchFrontEnd given at construction.
         Eager ahead of the replay: the random draws and the text encoder; they and the batch's pixel tensors are copied into static inputs.
         Captured, at the head of the step's first graph: the VAE encodes and the assemble launch — which writes the step's static
         buffers directly — then the step as __call__ captures it.  The capture is this path's own (a second graph on the same model, optimizer and buffers of
-        its own): __call__ on prepared latents keeps its graph and its results.  The first `warmup` calls run train_step_prepared."""
+        its own): __call__ on prepared latents keeps its graph and its results.  The first `warmup` calls run train_step_prepared.
+        With generator=rng.PhiloxGenerator the draws are captured too: mf_train_batch_draw reading the generator's device state and the
+        advance launch head the graph, so a replay copies in only the pixels and the text states and still draws fresh numbers.  A step
+        captured that way takes that generator and no given draws on later calls; one captured the other way takes no PhiloxGenerator."""
         if self.front_end is None:
             raise RuntimeError("GraphedTrainStep.from_pixels: construct the step with front_end=BatchFrontEnd(...)")
         if self._px is None:
             self._px = _PixelTrainStep(self)
-        return self._px.run(batch, noise, timesteps, posterior_noise, generator)
+        return self._px.run(batch, noise, timesteps, posterior_noise, generator, first_sample, global_batch)
 
 
 class _PixelTrainStep(GraphedTrainStep):
@@ -758,6 +805,8 @@ class _PixelTrainStep(GraphedTrainStep):
         super().__init__(outer.model, outer.ns, outer.opt, snr_gamma=outer.front_end.snr_gamma, max_grad_norm=outer.max_grad_norm,
                          check_overflow=outer.check_overflow, warmup=outer.warmup, lr_scheduler=outer.lr_scheduler, grad_sync=outer.grad_sync)
         self.fe, self.images, self.draws, self.latents, self._latent_shape = outer.front_end, None, None, None, None
+        self._philox = None         # (generator, its device state, first_sample, global_batch) of a capture that draws inside the graph
+        self._philox_blocks = 0     # what one replay's draw consumes (mf_train_batch_draw's count, known at capture)
 
     def _stage_pixels(self, batch: dict, draws):
         pns, noise, timesteps, ehs = draws
@@ -766,9 +815,12 @@ class _PixelTrainStep(GraphedTrainStep):
         dev = self.noisy.device
         if self.images is None:
             self.images = {k: torch.empty(batch[k].shape, dtype=torch.float32, device=dev) for k in self.fe.image_keys()}
-            self.draws = [None if p is None else torch.empty_like(p) for p in pns] + [torch.empty_like(noise), torch.empty_like(timesteps)]
-            self.latents = torch.empty_like(noise)
-        for dst, src in list(zip(self.images.values(), (batch[k] for k in self.images))) + list(zip(self.draws, pns + [noise, timesteps])):
+            f32 = dict(dtype=torch.float32, device=dev)
+            self.draws = ([torch.empty(self._latent_shape, **f32) if u else None for u in self.fe.sources_used()]
+                          + [torch.empty(self._latent_shape, **f32), torch.empty(self._latent_shape[0], dtype=torch.int64, device=dev)])
+            self.latents = torch.empty(self._latent_shape, **f32)
+        staged = [] if self._philox is not None else list(zip(self.draws, pns + [noise, timesteps]))     # (drawn inside the graph)
+        for dst, src in list(zip(self.images.values(), (batch[k] for k in self.images))) + staged:
             if (dst is None) != (src is None) or (dst is not None and tuple(dst.shape) != tuple(src.shape)):
                 raise ValueError("from_pixels: the batch does not match the captured one (shapes, conditioning modes)")
             if dst is not None:
@@ -776,36 +828,68 @@ class _PixelTrainStep(GraphedTrainStep):
         self.ehs.copy_(ehs.to(dev, torch.float32))
 
     def _body(self):
+        if self._philox is not None:
+            gen, state, first, total = self._philox
+            self._philox_blocks = self.fe.philox_draw(self.draws, gen, first, total, state=state)
         moments, masks, depths, normals = self.fe.encode_images(self.images)
         enc = EncodedBatch(moments, self.draws[:4], self.draws[4], self.draws[5], masks, depths, normals, None)
         self.fe.assemble(enc, out=dict(latents=self.latents, noisy_latents=self.noisy, target=self.target, conditioning_latents=self.cond,
                                        timesteps_f32=self.t_dev, loss_weights=self.weights))
         return super()._body()
 
-    def run(self, batch, noise, timesteps, posterior_noise, generator):
+    def run(self, batch, noise, timesteps, posterior_noise, generator, first_sample=None, global_batch=None):
+        from .rng import PhiloxGenerator
         if not self.model.get_trainable_modules():
             raise RuntimeError("GraphedTrainStep: call model.prepare_training() first")
+        philox = isinstance(generator, PhiloxGenerator)
+        given = noise is not None or timesteps is not None or (posterior_noise is not None and any(p is not None for p in posterior_noise))
         if self.graph is None and self.calls < self.warmup:
             self.calls += 1
-            prepared = self.fe(batch, noise, timesteps, posterior_noise, generator)
+            prepared = self.fe(batch, noise, timesteps, posterior_noise, generator, first_sample=first_sample, global_batch=global_batch)
             self._latent_shape = tuple(prepared.latents.shape)
             return train_step_prepared(self.model, self.ns, self.opt, prepared, max_grad_norm=self.max_grad_norm,
                                        check_overflow=self.check_overflow, lr_scheduler=self.lr_scheduler, grad_sync=self.grad_sync)
         b, c, h, w = self._latent_shape
-        draws = self.fe.draw(batch, self._latent_shape, noise, timesteps, posterior_noise, generator)
+        if philox and given:
+            raise ValueError("from_pixels: past the warm-up a PhiloxGenerator draws inside the graph, which leaves no place for given "
+                             "noise / timesteps / posterior_noise; pass them with a torch generator or none")
+        if self.graph is None:
+            if philox:      # this call captures: the draws go into the graph, reading the generator's state from device memory
+                self._philox = (generator, generator.device_state(), *self.fe.philox_shard(b, first_sample, global_batch))
+        elif self._philox is not None and generator is not self._philox[0]:
+            raise ValueError("from_pixels: this step was captured drawing from its PhiloxGenerator inside the graph; it takes that "
+                             f"generator and no given draws, got {type(generator).__name__}")
+        elif self._philox is None and philox:
+            raise ValueError("from_pixels: this step was captured with draws staged from outside the graph (a torch generator or "
+                             "given tensors); it cannot take a PhiloxGenerator")
+        if self._philox is not None:
+            if self.fe.philox_shard(b, first_sample, global_batch) != self._philox[2:]:
+                raise ValueError("from_pixels: first_sample / global_batch differ from the captured ones")
+            generator.device_state()                                  # level with the host pair (a copy only after eager draws in between)
+            ehs = batch.get("encoder_hidden_states")
+            if "input_ids" in batch and self.fe.text_encoder is not None:
+                ehs = self.fe.text_encoder(batch["input_ids"], return_dict=False)[0]
+            draws = ([None] * 4, None, None, ehs)
+        else:
+            draws = self.fe.draw(batch, self._latent_shape, noise, timesteps, posterior_noise, generator)
         ehs_shape = draws[3].shape if draws[3] is not None else (b, 0, 0)
-        return self._replay(self._latent_shape, ehs_shape, (b, self.fe.conditioning_channels(), h, w), lambda: self._stage_pixels(batch, draws))
+        out = self._replay(self._latent_shape, ehs_shape, (b, self.fe.conditioning_channels(), h, w), lambda: self._stage_pixels(batch, draws))
+        if self._philox is not None:
+            generator.note_advanced(self._philox_blocks, on_device=True)      # the replay's advance launch moved the device state
+        return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # checkpoints: accelerator.save_state with the script's hooks (:997-1069) and its rotation (:1474-1498)
 # ---------------------------------------------------------------------------------------------------------------------
 def save_state(output_dir: str, global_step: int, model: MirrorFusionModel, optimizer: Optional[AdamW] = None,
-               checkpoints_total_limit: Optional[int] = None, is_main_process: bool = True, lr_scheduler=None) -> Optional[str]:
+               checkpoints_total_limit: Optional[int] = None, is_main_process: bool = True, lr_scheduler=None,
+               generator=None) -> Optional[str]:
     """Writes `output_dir/checkpoint-<global_step>/{brushnet,unet}` (config.json + diffusion_pytorch_model.safetensors in
     the reference's layout; `unet` only when it trains), `optimizer.bin` and — when a schedule is passed — `scheduler.bin`
     (accelerate saves the prepared lr_scheduler with the state, train_brushnet_mirror.py:1267-1269, 1496); before that, removes
-    the oldest checkpoints so that at most `checkpoints_total_limit` remain — the script's order of operations."""
+    the oldest checkpoints so that at most `checkpoints_total_limit` remain — the script's order of operations.  `generator`: a
+    rng.PhiloxGenerator whose two integers go into trainer_state.json (key "philox"), so that a resumed run draws on from there."""
     if not is_main_process:
         return None
     os.makedirs(output_dir, exist_ok=True)
@@ -823,14 +907,19 @@ def save_state(output_dir: str, global_step: int, model: MirrorFusionModel, opti
     if lr_scheduler is not None:
         torch.save(lr_scheduler.state_dict(), os.path.join(path, "scheduler.bin"))
     with open(os.path.join(path, "trainer_state.json"), "w") as f:
-        json.dump(dict(global_step=global_step), f)
+        state = dict(global_step=global_step)
+        if generator is not None:
+            seed, offset = generator.get_state()
+            state["philox"] = dict(seed=seed, offset=offset)
+        json.dump(state, f)
     return path
 
 
-def load_state(path: str, model: MirrorFusionModel, optimizer: Optional[AdamW] = None, lr_scheduler=None) -> int:
+def load_state(path: str, model: MirrorFusionModel, optimizer: Optional[AdamW] = None, lr_scheduler=None, generator=None) -> int:
     """load_model_hook (:1035-1066): each trainable module reloads its weights from its sub-folder; returns the step.
     `lr_scheduler` (built BEFORE this call, like the script builds and prepares it before accelerator.load_state, :1232-1300)
-    continues from the saved epoch: without it a non-constant schedule would replay its warm-up after a resume."""
+    continues from the saved epoch: without it a non-constant schedule would replay its warm-up after a resume.  `generator`: a
+    rng.PhiloxGenerator set to the saved (seed, offset); a checkpoint without them is an error when one is passed."""
     from safetensors.torch import load_file
     for m in model.get_trainable_modules():
         sub = "brushnet" if m is model.brushnet else "unet"
@@ -853,7 +942,12 @@ def load_state(path: str, model: MirrorFusionModel, optimizer: Optional[AdamW] =
             warnings.warn(f"load_state: {path} has no scheduler.bin — the LR schedule restarts from its first step "
                           "(checkpoints written before round 5, or without lr_scheduler=, do not carry it)")
     with open(os.path.join(path, "trainer_state.json")) as f:
-        return int(json.load(f)["global_step"])
+        state = json.load(f)
+    if generator is not None:
+        if "philox" not in state:
+            raise ValueError(f"load_state: {path} carries no generator state (save_state(generator=...) writes it)")
+        generator.set_state((state["philox"]["seed"], state["philox"]["offset"]))
+    return int(state["global_step"])
 
 
 def latest_checkpoint(output_dir: str) -> Optional[str]:

@@ -14,7 +14,10 @@ the pipeline a transformers `text_encoder` + `tokenizer` pair.
 """
 from __future__ import annotations
 
+import contextlib
 import gc
+import inspect
+import json
 import os
 import time
 
@@ -117,6 +120,89 @@ class VaeImageProcessor:
         return [PIL.Image.fromarray(a) for a in arr]
 
 
+# ---- the scheduler update of ONE call: __call__ picks one of the three forms, once; the loops and the exporter only talk to the object ----
+# `eager`: a step of the eager loop.  For the captured step: `key` is the form's part of the graph-cache key, `attach` puts its static
+# buffers into the kept state, `load(i)` is the per-step copy before a replay, `launch` ends one_step, `after_replay` / `finish` are the
+# host's part, `export` gives a step program its io buffers and tables, and `result` is its meta's sentence about what a run leaves.
+class _FusedDDIM:
+    """DDIM with eta == 0 and no rescale: classifier-free guidance and the update are one kernel, reading the step's four
+    coefficients from a row of a [steps, 4] table."""
+    result = "latents (DDIM update inside)"
+
+    def __init__(self, pipe, g):
+        cfg = pipe.scheduler.config
+        self.sched, self.g = pipe.scheduler, float(g)
+        self.clip = float(cfg["clip_sample_range"]) if cfg["clip_sample"] else 0.0
+        self.ptype = 0 if cfg["prediction_type"] == "epsilon" else 1
+        self.key = ("ddim", self.ptype, self.clip)
+
+    def attach(self, st, lat, ts):
+        self.coef_cur = st.setdefault("coef_cur", torch.empty(4, dtype=torch.float32, device=lat.device))
+        self.coefs = torch.tensor([self.sched.step_coefficients(int(t))[:4] for t in ts], dtype=torch.float32).to(lat.device)
+
+    def eager(self, eu, ec, t, latents): return self.sched.step(None, t, latents, return_dict=False, _cfg=(eu, ec, self.g))[0]
+    def load(self, i): self.coef_cur.copy_(self.coefs[i])
+    def launch(self, eu, ec, lat): hip.cfg_ddim_step_dev(eu, ec, self.g, lat, self.coef_cur, self.ptype, self.clip, out=lat)
+    def after_replay(self, t, lat): pass
+    def finish(self): pass
+    def export(self): return dict(coef4=self.coef_cur), {"table.coef4": self.coefs.contiguous()}
+
+
+class _DevicePlan:
+    """PNDM / UniPC inside the captured step: mf_sched_step_dev runs the step's row of schedulers.device_plan (a trace of their own
+    step()) on a state buffer that keeps their history; the scheduler gets its end state from it after the loop."""
+
+    def __init__(self, pipe, g, nsteps):
+        self.sched, self.g = pipe.scheduler, float(g)
+        self.plan = device_plan(self.sched, steps=nsteps)
+        name = type(self.sched).__name__
+        self.key = (name, "device", self.plan.nslots)
+        self.result = f"latents ({name} update inside: mf_sched_step_dev; history in sched_state)"
+
+    def attach(self, st, lat, ts):
+        if "state" not in st:                     # the step's mf_sched_row, and the scheduler's history (persists between steps)
+            st["row_cur"] = torch.empty(self.plan.rows.shape[1], dtype=torch.int32, device=lat.device)
+            st["state"] = torch.empty((max(self.plan.nslots, 1),) + tuple(lat.shape), dtype=torch.float32, device=lat.device)
+        self.row_cur, self.state, self.rows = st["row_cur"], st["state"], self.plan.rows.to(lat.device)
+
+    def load(self, i): self.row_cur.copy_(self.rows[i])
+    def launch(self, eu, ec, lat): hip.sched_step_dev(eu, ec, self.g, lat, self.state, self.row_cur)
+    def after_replay(self, t, lat): pass
+    def finish(self): self.plan.finish(self.sched, self.state)    # the counters and history the host's step() would have left
+    # (the host copies the step's row in like coef4, and the history slots stay in "sched_state" between runs)
+    def export(self): return dict(sched_row=self.row_cur, sched_state=self.state), {"table.sched_row": self.rows.contiguous()}
+
+
+class _HostStep:
+    """Everything else: the guided noise prediction goes to the host's scheduler.step (a handful of mf_axpby_n launches; multistep
+    schedulers keep host-side state between steps, scheduling_pndm.py:321-390).  The captured step ends with it in `eps`."""
+    result = "eps (guided noise prediction; the scheduler update is the host's)"
+
+    def __init__(self, pipe, g, rescale, eta, generator):
+        self.pipe, self.g, self.rescale = pipe, float(g), rescale
+        params = inspect.signature(pipe.scheduler.step).parameters
+        self.extra = {k: v for k, v in (("eta", eta), ("generator", generator)) if k in params}
+        self.key = (type(pipe.scheduler).__name__, "host")
+
+    def eager(self, eu, ec, t, latents):
+        noise_pred = eu if ec is None else hip.cfg_combine(eu, ec, self.g)                          # :1310-1312
+        if ec is not None and self.rescale > 0.0:
+            # rescale_noise_cfg (pipeline_brushnet_sd_xl.py:1478-1480; pipeline_stable_diffusion.py:59-70): one standard
+            # deviation per image and two scalings — a non-default switch outside the timed path, on torch's device ops
+            dims, r = list(range(1, ec.ndim)), self.rescale
+            std_text, std_cfg = ec.float().std(dim=dims, keepdim=True), noise_pred.float().std(dim=dims, keepdim=True)
+            noise_pred = (r * (noise_pred.float() * (std_text / std_cfg)) + (1.0 - r) * noise_pred.float()).to(noise_pred.dtype)
+        return self.pipe._sched_step(noise_pred, t, latents, self.extra)
+
+    def attach(self, st, lat, ts): self.eps = st.setdefault("eps", torch.empty_like(lat))
+    def load(self, i): pass
+    def launch(self, eu, ec, lat): self.eps.copy_(hip.cfg_combine(eu, ec, self.g))                  # :1310-1312
+    # (multistep schedulers keep references to their inputs (ets, last_sample): hand them copies, not the graph's static buffers)
+    def after_replay(self, t, lat): lat.copy_(self.pipe._sched_step(self.eps.clone(), t, lat.clone(), self.extra))    # :1315
+    def finish(self): pass
+    def export(self): return dict(eps=self.eps), {}
+
+
 class StableDiffusionBrushNetPipeline:
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
 
@@ -169,10 +255,8 @@ class StableDiffusionBrushNetPipeline:
         # measured on MI355X (gpurun_out/r03c): 16.75 ms per step with it, 16.56 without — the fused K = 2C GEMM lands on the
         # UNet's stream (the critical one) while the zero-conv it replaces ran in BrushNet's slack: OFF by default
         self.fold_zero_convs = os.environ.get("MFHIP_ZC_FOLD") == "1"
-        self._added_cond = None          # SDXL: added_cond_kwargs of the (CFG-duplicated) batch, set by the XL subclass
-        self._graph_state = None
+        self._graph_state = None         # the captured step and its static buffers, kept across calls (_denoise_graph)
         self.normal_embedder = None      # 'ip_adapter' normals mode: a frontend.NormalEmbedder turns `normals=` [B, 1, 3] into the ip token
-        self._pe_unet = None             # ... and the UNet's prompt embeddings with that token appended (BrushNet keeps the text's 77)
 
     # ---- loading / saving (pipelines/pipeline_utils.py:148-296 save_pretrained, :465-919 from_pretrained) ---------
     _scheduler_classes = ("DDIMScheduler", "PNDMScheduler", "UniPCMultistepScheduler")
@@ -186,8 +270,6 @@ class StableDiffusionBrushNetPipeline:
         `text_encoder/` is loaded into the HIP CLIPTextModel (text_encoder.py) when the folder exists and no `text_encoder=` was
         passed.  The tokenizer is string processing and stays the caller's object; `tokenizer/` is loaded through
         transformers.CLIPTokenizer when transformers is importable, else left None."""
-        import json
-        import os
         from . import schedulers as S
         root = pretrained_model_name_or_path
         index = {}
@@ -235,8 +317,6 @@ class StableDiffusionBrushNetPipeline:
     def save_pretrained(self, save_directory: str, **unused):
         """`model_index.json` + one sub-folder per module in the reference's on-disk format (config.json +
         diffusion_pytorch_model.safetensors with the reference's key names; scheduler/scheduler_config.json)."""
-        import json
-        import os
         os.makedirs(save_directory, exist_ok=True)
         index = {"_class_name": type(self).__name__, "_diffusers_version": "0.27.0.dev0"}
         for name in ("vae", "unet", "brushnet"):
@@ -442,6 +522,13 @@ class StableDiffusionBrushNetPipeline:
         `conditioning_noise`: the VAE posterior noise of the CFG-duplicated batch — one tensor (image) or a sequence
         (image, depth, normals) for the 'latents' modes; None draws them in the reference's order from the global RNG, or, with a
         rng.PhiloxGenerator (or a list of them, one per sample) as `generator`, from it on the device."""
+        return self._conditioning(image, mask, depth, height, width, batch, num_images_per_prompt, do_cfg, conditioning_noise,
+                                  normals, generator)[0]
+
+    def _conditioning(self, image, mask, depth, height, width, batch, num_images_per_prompt, do_cfg, conditioning_noise=None,
+                      normals=None, generator=None, shared: Optional[bool] = None):
+        """build_conditioning, and with it whether both classifier-free-guidance halves got identical VAE posterior samples (what
+        _brushnet_shareable asks).  `shared`: the caller has decided that already (export_conditioning)."""
         img = self.prepare_image(image, width, height, batch, num_images_per_prompt)
         m3 = self.prepare_image(mask, width, height, batch, num_images_per_prompt)
         original_mask = hip.mask_keep(m3) if m3.is_cuda else (m3.sum(1)[:, None, :, :] < 0).to(torch.float32)   # :1139 (1 = keep)
@@ -456,6 +543,7 @@ class StableDiffusionBrushNetPipeline:
         def encode_sample(x_host, noise):
             """vae.encode(x).latent_dist.sample() * scaling_factor for the CFG-duplicated batch: B images are encoded
             once and sampled once per CFG half (the reference encodes the duplicated batch, :1188)."""
+            nonlocal identical
             moments = self.vae._moments(x_host)
             if noise is None and philox:
                 # the same shapes and order as the global-RNG draws below; a list of generators draws each half sample by sample
@@ -463,29 +551,28 @@ class StableDiffusionBrushNetPipeline:
                     noise = randn_tensor((batch, lat_c, hl, wl), generator, self.device).repeat(2, 1, 1, 1)
                 elif isinstance(generator, (list, tuple)) and len(generator) > 1:
                     noise = torch.cat([randn_tensor((batch, lat_c, hl, wl), generator, self.device) for _ in range(dup)])
-                    self._cond_halves_identical = False
+                    identical = False
                 else:
                     noise = randn_tensor((dup * batch, lat_c, hl, wl), generator, self.device)
-                    self._cond_halves_identical = False
+                    identical = False
             elif noise is None:
                 if dup == 2 and self.cfg_shared_conditioning_sample:
                     noise = torch.randn(batch, lat_c, hl, wl, dtype=torch.float32).repeat(2, 1, 1, 1)
                 else:
                     noise = torch.randn(dup * batch, lat_c, hl, wl, dtype=torch.float32)   # global RNG, like vae.py:782-791
-                    self._cond_halves_identical = False     # two independent draws: never identical
+                    identical = False     # two independent draws: never identical
             if noise.shape[0] != dup * batch:
                 raise ValueError(f"conditioning_noise must have batch {dup * batch}")
-            if dup == 2 and self._cond_halves_identical:
+            if dup == 2 and identical:
                 # whether both CFG halves get the same sample is decided HERE, from how the noise was made (a host compare of a
                 # host tensor; a device tensor costs one read-back) — not by comparing the built conditioning on the device
                 # (export_conditioning decides before it records: the compare is a torch kernel a program cannot hold)
-                decided = getattr(self, "_cond_shared_decided", None)
-                self._cond_halves_identical = bool(torch.equal(noise[:batch], noise[batch:])) if decided is None else bool(decided)
+                identical = bool(torch.equal(noise[:batch], noise[batch:])) if shared is None else bool(shared)
             noise = noise.to(self.device, torch.float32)
             return [hip.vae_sample(moments, noise[i * batch:(i + 1) * batch].contiguous(), lat_c, sf) for i in range(dup)]
 
         philox = is_philox(generator)
-        self._cond_halves_identical = dup == 2
+        identical = dup == 2
         halves = encode_sample(img, noises[0])
         parts = [[h] for h in halves]
         mask_l = hip.nearest_resize(hip.h2d(original_mask, self.device), hl, wl)                   # :1189-1195
@@ -510,7 +597,7 @@ class StableDiffusionBrushNetPipeline:
                 for ps, h in zip(parts, encode_sample(nrm, noises[2])):                            # :1213-1215
                     ps.append(h)
         # torch.cat along channels of each CFG half (:1196-1215) by the front-end kernel; stacking the halves is a copy
-        return torch.cat([hip.concat_channels(ps, batch) for ps in parts], 0).contiguous()
+        return torch.cat([hip.concat_channels(ps, batch) for ps in parts], 0).contiguous(), identical
 
     # ---- the call --------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -526,7 +613,10 @@ class StableDiffusionBrushNetPipeline:
                  control_guidance_end: Union[float, List[float]] = 1.0, clip_skip: Optional[int] = None,
                  callback_on_step_end: Optional[Callable] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"],
-                 conditioning_noise: Optional[torch.Tensor] = None, _timing: Optional[dict] = None, **kwargs):
+                 conditioning_noise: Optional[torch.Tensor] = None, _timing: Optional[dict] = None, _export: Optional[dict] = None,
+                 _added: Optional[dict] = None, _end: Optional[float] = None, _rescale: float = 0.0, **kwargs):
+        # private keywords, all call-scoped: `_timing` (bench.py), `_export` (export_denoise_step's request; its result comes back in it), and
+        # from the XL subclass `_added` (added_cond_kwargs of the CFG-duplicated batch), `_end` (denoising_end), `_rescale` (guidance_rescale)
         callback = kwargs.pop("callback", None)
         callback_steps = kwargs.pop("callback_steps", None)
         ip_mode = self.normals_conditioning_mode == "ip_adapter"
@@ -569,8 +659,8 @@ class StableDiffusionBrushNetPipeline:
         pe = torch.cat([negative_prompt_embeds, prompt_embeds]) if do_cfg else prompt_embeds         # :1103
         pe = pe.to(self.device)
         nb = batch_size * num_images_per_prompt
-        self._pe_unet = (self._append_normal_token(pe, batch_size, num_images_per_prompt, do_cfg, normals, ip_adapter_image_embeds)
-                         if ip_mode else None)
+        # what the UNet reads: the 'ip_adapter' normals mode appends its token (BrushNet keeps the text's 77)
+        pe_u = self._append_normal_token(pe, batch_size, num_images_per_prompt, do_cfg, normals, ip_adapter_image_embeds) if ip_mode else pe
         if ip_mode:
             normals = None                    # a [B, 1, 3] vector, consumed above: no normals map enters the conditioning
 
@@ -582,16 +672,15 @@ class StableDiffusionBrushNetPipeline:
                 ww, hh = first.size
             height, width = height or int(hh), width or int(ww)
         # guess_mode (:771-772, 1260-1264): the conditioning is NOT doubled, BrushNet sees the conditional batch only
-        cond = self.build_conditioning(image, mask, depth, height, width, nb, num_images_per_prompt, do_cfg and not guess_mode,
-                                       conditioning_noise, normals, generator=generator)
-        self._brushnet_once = (not guess_mode) and self._brushnet_shareable(cond, nb, do_cfg)
+        cond, identical = self._conditioning(image, mask, depth, height, width, nb, num_images_per_prompt, do_cfg and not guess_mode,
+                                             conditioning_noise, normals, generator)
+        once = self._brushnet_once = (not guess_mode) and self._brushnet_shareable(cond, nb, do_cfg, identical)
 
         self.scheduler.set_timesteps(num_inference_steps, device=self.device)                       # :1171
         ts = self.scheduler.timesteps
-        dend = getattr(self, "_denoising_end", None)
-        if dend is not None and isinstance(dend, float) and 0.0 < dend < 1.0:                        # pipeline_brushnet_sd_xl.py:1376-1391
+        if _end is not None and isinstance(_end, float) and 0.0 < _end < 1.0:                        # pipeline_brushnet_sd_xl.py:1376-1391
             ntrain = int(self.scheduler.config["num_train_timesteps"])
-            cutoff = int(round(ntrain - dend * ntrain))
+            cutoff = int(round(ntrain - _end * ntrain))
             num_inference_steps = len([t for t in ts.tolist() if t >= cutoff])
             ts = ts[:num_inference_steps]
         self._num_timesteps = len(ts)
@@ -599,63 +688,45 @@ class StableDiffusionBrushNetPipeline:
 
         keep = [1.0 - float(i / len(ts) < control_guidance_start or (i + 1) / len(ts) > control_guidance_end)
                 for i in range(len(ts))]                                                             # :1236-1242
-        rescale = float(getattr(self, "_guidance_rescale", 0.0) or 0.0)
-        fused_ddim = isinstance(self.scheduler, DDIMScheduler) and eta == 0.0 and rescale == 0.0
+        rescale = float(_rescale or 0.0)
         num_warmup = len(ts) - num_inference_steps * self.scheduler.order
         if _timing is not None:          # HIP events on the launch stream around the denoise loop (bench.py)
             _timing["host_before_denoise"] = time.perf_counter()
             _timing["denoise_start"] = torch.cuda.Event(enable_timing=True)
             _timing["denoise_end"] = torch.cuda.Event(enable_timing=True)
             _timing["denoise_start"].record()
+        fused_ddim = do_cfg and isinstance(self.scheduler, DDIMScheduler) and eta == 0.0 and rescale == 0.0
         use_graph = (self.use_hip_graph and do_cfg and callback is None and (fused_ddim or eta == 0.0) and rescale == 0.0
                      and all(k == 1.0 for k in keep) and len(ts) > 2 and not guess_mode)
+        # THE place that decides how a step ends.  PNDM / UniPC update on the device (one plan row per step) unless a callback may read
+        # the scheduler between steps, or an eps-form step program is being exported; the eager loop always steps them on the host
+        if fused_ddim:
+            update = _FusedDDIM(self, guidance_scale)
+        elif (use_graph and callback_on_step_end is None and not (_export is not None and _export["scheduler"] == "host")
+              and isinstance(self.scheduler, (PNDMScheduler, UniPCMultistepScheduler))):
+            update = _DevicePlan(self, guidance_scale, len(ts))
+        else:
+            update = _HostStep(self, guidance_scale, rescale, eta, generator)
+
+        def step_end(i, t, lat):           # callback_on_step_end: the latents to go on with (its own, if it returns some)
+            if callback_on_step_end is None:
+                return lat
+            avail = dict(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds)
+            new = (callback_on_step_end(self, i, t, {k: avail[k] for k in callback_on_step_end_tensor_inputs}) or {}).pop("latents", None)
+            return lat if new is None else new
+
         with self.progress_bar(total=num_inference_steps) as bar:
             if use_graph:
-                latents = self._denoise_graph(latents, ts, pe, cond, nb, guidance_scale, float(brushnet_conditioning_scale),
-                                              callback_on_step_end, callback_on_step_end_tensor_inputs, prompt_embeds,
-                                              negative_prompt_embeds, bar, fused_ddim, eta, generator)
+                latents = self._denoise_graph(latents, ts, pe, pe_u, cond, nb, guidance_scale, float(brushnet_conditioning_scale), once,
+                                              _added, update, step_end, bar, _export)
                 ts = []
             for i, t in enumerate(ts):                                                               # :1250 HOT LOOP
                 # step 0 autotunes GEMM tiles: keep its timings undisturbed; guess_mode re-packs the residuals on this
                 # stream (the per-residual events are keyed by the tensors BrushNet returned)
                 self._overlap(i > 0 and not guess_mode)
-                x_in = torch.cat([latents] * 2) if do_cfg else latents                               # :1256
-                x_in = self.scheduler.scale_model_input(x_in, t)
-                cond_scale = float(brushnet_conditioning_scale) * keep[i]
-                once = self._brushnet_once or (guess_mode and do_cfg)      # BrushNet on the conditional batch only
-                down, mid, up = self.brushnet(x_in[nb:] if (guess_mode and do_cfg) else x_in[:nb] if once else x_in, t,
-                                              encoder_hidden_states=pe[nb:] if (guess_mode and do_cfg) else pe[:nb] if once else pe,
-                                              brushnet_cond=cond[:nb] if once else cond,
-                                              conditioning_scale=cond_scale, added_cond_kwargs=self._added_cond,
-                                              guess_mode=guess_mode, return_dict=False)              # :1277
-                if guess_mode and do_cfg:           # zeros keep the unconditional half unchanged (:1287-1293); copies only
-                    down = [torch.cat([torch.zeros_like(d), d]) for d in down]
-                    mid = torch.cat([torch.zeros_like(mid), mid])
-                    up = [torch.cat([torch.zeros_like(u), u]) for u in up]
-                eps = self.unet(x_in, t, encoder_hidden_states=pe if self._pe_unet is None else self._pe_unet,
-                                down_block_add_samples=down,
-                                mid_block_add_sample=mid, up_block_add_samples=up, added_cond_kwargs=self._added_cond,
-                                return_dict=False)[0]                                                # :1296
-                if do_cfg:
-                    eu, ec = eps[:nb], eps[nb:]
-                    if fused_ddim:
-                        latents = self.scheduler.step(None, t, latents, return_dict=False, _cfg=(eu, ec, guidance_scale))[0]
-                    else:
-                        noise_pred = hip.cfg_combine(eu, ec, float(guidance_scale))                 # :1310-1312
-                        if rescale > 0.0:
-                            # rescale_noise_cfg (pipeline_brushnet_sd_xl.py:1478-1480; pipeline_stable_diffusion.py:59-70): one standard
-                            # deviation per image and two scalings — a non-default switch outside the timed path, on torch's device ops
-                            dims = list(range(1, ec.ndim))
-                            std_text, std_cfg = ec.float().std(dim=dims, keepdim=True), noise_pred.float().std(dim=dims, keepdim=True)
-                            noise_pred = (rescale * (noise_pred.float() * (std_text / std_cfg)) + (1.0 - rescale) * noise_pred.float()).to(noise_pred.dtype)
-                        latents = self._sched_step(noise_pred, t, latents, eta, generator)
-                else:
-                    latents = self._sched_step(eps, t, latents, eta, generator)                     # :1315
-                if callback_on_step_end is not None:
-                    avail = dict(latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds)
-                    cb_kwargs = {k: avail[k] for k in callback_on_step_end_tensor_inputs}
-                    outs = callback_on_step_end(self, i, t, cb_kwargs) or {}
-                    latents = outs.pop("latents", latents)
+                eu, ec = self._predict_noise(latents, t, pe, pe_u, cond, nb, float(brushnet_conditioning_scale) * keep[i], do_cfg, once,
+                                             guess_mode, _added)
+                latents = step_end(i, t, update.eager(eu, ec, t, latents))
                 if i == len(ts) - 1 or ((i + 1) > num_warmup and (i + 1) % self.scheduler.order == 0):
                     bar.update()
                     if callback is not None and callback_steps and i % callback_steps == 0:
@@ -711,7 +782,28 @@ class StableDiffusionBrushNetPipeline:
                              + (f" or the two guidance halves stacked ({2 * batch})" if do_cfg else ""))
         return torch.cat([pe, torch.cat([t.repeat_interleave(per_prompt, dim=0) for t in parts])], 1).contiguous()
 
-    def _brushnet_shareable(self, cond: torch.Tensor, nb: int, do_cfg: bool) -> bool:
+    def _predict_noise(self, latents, t, pe, pe_u, cond, nb, cond_scale, do_cfg, once, guess_mode, added, temb=(None, None), lazy=None):
+        """The body of a denoise step up to the scheduler update (pipeline_brushnet.py:1256-1296), for the eager loop and for the
+        captured step alike: BrushNet, the UNet with its residuals, and the noise prediction's (unconditional, conditional) halves —
+        (eps, None) without classifier-free guidance.  `once` / `guess_mode`: BrushNet sees one half of the batch (the halves are identical
+        / the conditional one, :1260-1264); `pe_u`: the UNet's own prompt embeddings; `temb`: the step's rows of the (UNet's, BrushNet's)
+        time-embedding tables; `lazy`: unet.lazy_injection_names()."""
+        x_in = torch.cat([latents] * 2) if do_cfg else latents                                       # :1256
+        x_in = self.scheduler.scale_model_input(x_in, t)          # (returns its input for DDIM / PNDM / UniPC: no launch)
+        cond_only = guess_mode and do_cfg
+        down, mid, up = self.brushnet(x_in[nb:] if cond_only else x_in[:nb] if once else x_in, t,
+                                      encoder_hidden_states=pe[nb:] if cond_only else pe[:nb] if once else pe,
+                                      brushnet_cond=cond[:nb] if (once or cond_only) else cond, conditioning_scale=cond_scale,
+                                      added_cond_kwargs=added, guess_mode=guess_mode, return_dict=False, _temb=temb[1], _lazy=lazy)   # :1277
+        if cond_only:                       # zeros keep the unconditional half unchanged (:1287-1293); copies only, eager loop only
+            down = [torch.cat([torch.zeros_like(d), d]) for d in down]
+            mid = torch.cat([torch.zeros_like(mid), mid])
+            up = [torch.cat([torch.zeros_like(u), u]) for u in up]
+        eps = self.unet(x_in, t, encoder_hidden_states=pe_u, down_block_add_samples=down, mid_block_add_sample=mid,
+                        up_block_add_samples=up, added_cond_kwargs=added, return_dict=False, _temb=temb[0])[0]                       # :1296
+        return (eps[:nb], eps[nb:]) if do_cfg else (eps, None)
+
+    def _brushnet_shareable(self, cond: torch.Tensor, nb: int, do_cfg: bool, identical: Optional[bool] = None) -> bool:
         """Under classifier-free guidance the reference feeds BrushNet the duplicated batch (pipeline_brushnet.py:1256-1277:
         torch.cat([latents] * 2), [negative | positive] prompt embeddings, the conditioning latents of the duplicated image
         batch).  The BrushNet built by from_unet is attention-free (brushnet.py:484-486), so it never reads the prompt
@@ -725,8 +817,9 @@ class StableDiffusionBrushNetPipeline:
                 and self.brushnet.config.get("class_embed_type") is None):
             return False
         # identical halves <=> every VAE posterior sample that went into `cond` was the same for both halves (mask, depth and
-        # normals maps are deterministic functions of the inputs): recorded by build_conditioning, no device compare / sync
-        return bool(getattr(self, "_cond_halves_identical", False))
+        # normals maps are deterministic functions of the inputs): `identical`, as _conditioning returned it with `cond` — no device
+        # compare / sync; a caller that holds the tensor alone pays for one
+        return bool(torch.equal(cond[:nb], cond[nb:]) if identical is None else identical)
 
     def _overlap(self, on: bool):
         """Turn the BrushNet || UNet stream overlap (models._RESIDUAL_EVENTS) on or off for the next forward calls."""
@@ -753,76 +846,45 @@ class StableDiffusionBrushNetPipeline:
             self.brushnet.side_stream = None
             self.unet.aux_stream = self.brushnet.aux_stream = None
 
-    def _denoise_graph(self, latents, ts, pe, cond, nb, guidance_scale, cond_scale, callback_on_step_end,
-                       cb_inputs, prompt_embeds, negative_prompt_embeds, bar, fused_ddim=True, eta=0.0, generator=None):
-        """The hot loop as ONE captured hipGraph replayed per timestep (BrushNet + UNet + CFG [+ DDIM update], ~800
+    def _denoise_graph(self, latents, ts, pe, pe_u, cond, nb, guidance_scale, cond_scale, once, added, update, step_end, bar, export=None):
+        """The hot loop as ONE captured hipGraph replayed per timestep (BrushNet + UNet + CFG + what `update` launches, ~800
         kernels on two streams): launch overhead disappears and the host only refreshes two tiny device buffers
-        (timestep, scheduler coefficients) between replays.  DDIM's update is inside the graph; so is that of the multistep
-        schedulers (PNDM, UniPC): mf_sched_step_dev runs the step's row of schedulers.device_plan (a trace of their own step()) on
-        a state buffer that keeps their history, and the scheduler gets its end state from it after the loop.  With a
-        callback_on_step_end (it may read the scheduler between steps) or while an eps-form step program is exported, they get
-        the guided noise prediction from the graph and step eagerly (a handful of mf_axpby_n launches).  The first step runs eagerly: it autotunes GEMM tiles,
+        (timestep, the update's row) between replays.  DDIM's update is inside the graph (_FusedDDIM); so is that of the multistep
+        schedulers (_DevicePlan), unless a callback_on_step_end may read the scheduler between steps or an eps-form step program is
+        exported: then they get the guided noise prediction from the graph and step eagerly (_HostStep).  `export`: the request of
+        export_denoise_step, the capture of step 1 is recorded as a program too.  The first step runs eagerly: it autotunes GEMM tiles,
         binds the prompt (cross-attention K/V cache) and sizes every scratch buffer before anything is captured."""
-        sched = self.scheduler
         dev = latents.device
         tvals = ts.to(torch.float32).to(dev)
-        plan = None
-        if fused_ddim:
-            coefs = torch.tensor([sched.step_coefficients(int(t))[:4] for t in ts], dtype=torch.float32).to(dev)
-            clip = float(sched.config["clip_sample_range"]) if sched.config["clip_sample"] else 0.0
-            ptype = 0 if sched.config["prediction_type"] == "epsilon" else 1
-        else:
-            coefs, clip, ptype = None, 0.0, type(sched).__name__
-            # PNDM / UniPC update on the device (mf_sched_step_dev, one row per step) unless a callback may read the scheduler between
-            # steps, or an eps-form step program is being exported
-            export_host = getattr(self, "_export_step_to", None) is not None and getattr(self, "_export_sched", "host") == "host"
-            if callback_on_step_end is None and not export_host and isinstance(sched, (PNDMScheduler, UniPCMultistepScheduler)):
-                plan = device_plan(sched, steps=len(ts))
-                coefs = plan.rows.to(dev)
-                ptype = (ptype, "device", plan.nslots)
+        ip = pe_u is not pe                                   # the 'ip_adapter' normals mode: the UNet reads its own embeddings
         # The captured graph (and every buffer it reads) is kept across calls with the same shapes and scalars:
         # new inputs are copied INTO the static buffers, so repeated calls pay no capture / instantiate cost.  The key
         # carries each model's weights generation: load_state_dict / .to() rebuild every weight tensor (and the UNet's
         # cross-attention K/V cache), so a graph captured before that points at freed buffers and must not be replayed.
-        added = self._added_cond
-        key = (tuple(latents.shape), tuple(pe.shape), tuple(cond.shape), float(guidance_scale), cond_scale, ptype, clip,
-               str(dev), id(self.unet), self.unet._weights_gen, id(self.brushnet), self.brushnet._weights_gen, self._brushnet_once,
+        key = (tuple(latents.shape), tuple(pe.shape), tuple(cond.shape), float(guidance_scale), cond_scale, update.key,
+               str(dev), id(self.unet), self.unet._weights_gen, id(self.brushnet), self.brushnet._weights_gen, once,
                tuple((k, tuple(v.shape)) for k, v in sorted(added.items())) if added else None,
-               tuple(self._pe_unet.shape) if self._pe_unet is not None else None, self.unet.ip_signature() if hasattr(self.unet, "ip_signature") else None)
+               tuple(pe_u.shape) if ip else None, self.unet.ip_signature() if hasattr(self.unet, "ip_signature") else None)
         st = self._graph_state if self._graph_state is not None and self._graph_state["key"] == key else None
         if st is None:
             st = dict(key=key, graph=None, lat=torch.empty_like(latents), pe=torch.empty_like(pe),
-                      cond=torch.empty_like(cond), t_cur=torch.empty(1, dtype=torch.float32, device=dev),
-                      coef_cur=torch.empty(4, dtype=torch.float32, device=dev))
+                      cond=torch.empty_like(cond), t_cur=torch.empty(1, dtype=torch.float32, device=dev))
             if added:
                 st["added"] = {k: torch.empty(v.shape, dtype=torch.float32, device=dev) for k, v in added.items()}
-            if self._pe_unet is not None:
-                st["pe_unet"] = torch.empty_like(self._pe_unet)
-            if plan is not None:                                 # the step's mf_sched_row, and the scheduler's history (persists between steps)
-                st["row_cur"] = torch.empty(plan.rows.shape[1], dtype=torch.int32, device=dev)
-                st["state"] = torch.empty((max(plan.nslots, 1),) + tuple(latents.shape), dtype=torch.float32, device=dev)
-            elif not fused_ddim:
-                st["eps"] = torch.empty_like(latents)            # guided noise prediction handed to scheduler.step
+            if ip:
+                st["pe_unet"] = torch.empty_like(pe_u)
             self._graph_state = st
-        if added:
-            for k, v in added.items():
-                st["added"][k].copy_(v)
-            added = st["added"]
-        lat, t_cur, coef_cur = st["lat"], st["t_cur"], st["coef_cur"]
-        lat.copy_(latents)
-        st["pe"].copy_(pe)
-        st["cond"].copy_(cond)
-        pe, cond = st["pe"], st["cond"]
-        pe_u = pe                                             # what the UNet reads: the 'ip_adapter' normals mode appends its token
-        if self._pe_unet is not None:
-            st["pe_unet"].copy_(self._pe_unet)
-            pe_u = st["pe_unet"]
+        lat, t_cur = st["lat"].copy_(latents), st["t_cur"]
+        update.attach(st, lat, ts)
+        added = {k: st["added"][k].copy_(v) for k, v in added.items()} if added else added      # (the static buffers, refilled)
+        pe, cond = st["pe"].copy_(pe), st["cond"].copy_(cond)
+        pe_u = st["pe_unet"].copy_(pe_u) if ip else pe
         # every timestep is known here (SURVEY.md §7): both nets' time embeddings and the fused time_emb_proj GEMM run ONCE for
         # the whole schedule (4 batched launches per net) instead of 8 dependent launches at the head of every step; the
         # graph reads one row block per step from a static buffer.  Kept across calls with the same schedule.
         tkey = (tuple(float(t) for t in ts.tolist()), self.unet._weights_gen, self.brushnet._weights_gen)
         if self.precompute_time_embedding and (st.get("temb_key") != tkey or added):
-            nrows_b = nb if self._brushnet_once else pe.shape[0]
+            nrows_b = nb if once else pe.shape[0]
             st["temb_tab"] = (self.unet.time_embedding_table(tvals, pe.shape[0], added),
                               self.brushnet.time_embedding_table(tvals, nrows_b, added))
             st["temb_key"] = tkey
@@ -833,127 +895,86 @@ class StableDiffusionBrushNetPipeline:
         temb_u, temb_b = st["temb_cur"] if self.precompute_time_embedding else (None, None)
 
         # residuals that land on a proj_out are never computed: their zero-conv becomes a second K segment of that GEMM
-        lazy = self.unet.lazy_injection_names() if (self.fold_zero_convs and not self._brushnet_once) else None
+        lazy = self.unet.lazy_injection_names() if (self.fold_zero_convs and not once) else None
 
         def one_step():
-            x_in = torch.cat([lat] * 2)
-            once = self._brushnet_once
-            down, mid, up = self.brushnet(lat if once else x_in, t_cur, encoder_hidden_states=pe[:nb] if once else pe,
-                                          brushnet_cond=cond[:nb] if once else cond,
-                                          conditioning_scale=cond_scale, added_cond_kwargs=added, return_dict=False, _temb=temb_b,
-                                          _lazy=lazy)
-            eps = self.unet(x_in, t_cur, encoder_hidden_states=pe_u, down_block_add_samples=down,
-                            mid_block_add_sample=mid, up_block_add_samples=up, added_cond_kwargs=added,
-                            return_dict=False, _temb=temb_u)[0]
-            if fused_ddim:
-                hip.cfg_ddim_step_dev(eps[:nb], eps[nb:], float(guidance_scale), lat, coef_cur, ptype, clip, out=lat)
-            elif plan is not None:
-                hip.sched_step_dev(eps[:nb], eps[nb:], float(guidance_scale), lat, st["state"], st["row_cur"])
-            else:
-                st["eps"].copy_(hip.cfg_combine(eps[:nb], eps[nb:], float(guidance_scale)))         # :1310-1312
+            eu, ec = self._predict_noise(lat, t_cur, pe, pe_u, cond, nb, cond_scale, True, once, False, added, (temb_u, temb_b), lazy)
+            update.launch(eu, ec, lat)
 
         # A graph captured by an earlier call with this key serves every step, the first included: what depends on the
         # prompt alone (its device copy, the cross-attention K / V^T) is recomputed into the buffers the graph reads.
-        export = getattr(self, "_export_step_to", None)           # export_denoise_step(): the capture of step 1 is recorded as a program
         if export is not None:
             st["graph"] = None                                    # (a graph kept from an earlier call is captured again)
         replay_all = (export is None and st["graph"] is not None and os.environ.get("MFHIP_EAGER_FIRST") != "1"      # A/B switch
                       and self.unet.bind_prompt(pe_u))
         for i in range(len(ts)):
             t_cur.copy_(tvals[i:i + 1])
-            if fused_ddim:
-                coef_cur.copy_(coefs[i])
-            elif plan is not None:
-                st["row_cur"].copy_(coefs[i])
+            update.load(i)
             if temb_u is not None:
                 temb_u.copy_(st["temb_tab"][0][i])
                 temb_b.copy_(st["temb_tab"][1][i])
             if i == 0 and not replay_all:
                 one_step()                                   # eager: tunes GEMMs, binds the prompt K/V, sizes scratch
             else:
-                if st["graph"] is None:
-                    torch.cuda.synchronize()
-                    graph = torch.cuda.CUDAGraph()
-                    # export_denoise_step(): the captured pass is ALSO written down as a step program (program.py)
-                    rec = self._export_recorder(st, lat, coef_cur, temb_u, temb_b, cond, coefs, fused_ddim, plan) if export is not None else None
-                    self._overlap(True)                      # the side stream forks from / joins the capture stream
-                    # No automatic garbage collection inside the capture: a collection that falls into it runs the destructors of
-                    # whatever cyclic garbage the process holds (graphs, memory pools, events of earlier calls), and a HIP call made
-                    # from one of them while the stream captures ends the process.  torch.cuda.graph collects once on entry; what
-                    # becomes garbage during the capture waits until it has ended.
-                    gc_was_enabled = gc.isenabled()
-                    gc.disable()
-                    try:
-                        # (thread_local: with an initialised process group its watchdog thread may poll events while this thread captures)
-                        with torch.cuda.graph(graph, capture_error_mode="thread_local" if (torch.distributed.is_available() and torch.distributed.is_initialized()) else "global"):
-                            self._overlap(True)              # (again, now that the capture stream is current: never the side stream itself)
-                            if rec is not None:
-                                with rec:
-                                    one_step()
-                            else:
-                                one_step()
-                    except Exception:
-                        if rec is not None and rec.error is not None:
-                            raise rec.error                  # (not the "unjoined work" the aborted capture reports on top of it)
-                        raise
-                    finally:
-                        if gc_was_enabled:
-                            gc.enable()
-                        self._overlap(False)
-                    st["graph"] = graph                      # capture does not execute: replay below runs this step
-                    if rec is not None:                      # (so the buffers still hold what they held BEFORE the recorded step)
-                        self._export_save(rec, graph, export, lat, temb_u, temb_b, len(ts), i, guidance_scale, cond_scale)
+                if st["graph"] is None:                      # capture does not execute: replay below runs this step
+                    st["graph"] = self._capture(one_step) if export is None else self._export_capture(
+                        one_step, export, update, st, lat, temb_u, temb_b, cond, len(ts), i, guidance_scale, cond_scale, once)
                 st["graph"].replay()
-            if not fused_ddim and plan is None:
-                # multistep schedulers keep references to their inputs (ets, last_sample): hand them copies, not the
-                # graph's static buffers
-                lat.copy_(self._sched_step(st["eps"].clone(), ts[i], lat.clone(), eta, generator))   # :1315
-            if callback_on_step_end is not None:
-                avail = dict(latents=lat, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds)
-                outs = callback_on_step_end(self, i, ts[i], {k: avail[k] for k in cb_inputs}) or {}
-                new = outs.pop("latents", None)
-                if new is not None and new is not lat:
-                    lat.copy_(new)
+            update.after_replay(ts[i], lat)
+            new = step_end(i, ts[i], lat)
+            if new is not lat:
+                lat.copy_(new)
             bar.update()
-        if plan is not None:
-            plan.finish(sched, st["state"])                  # the counters and history the host's step() would have left
+        update.finish()
         return lat.clone()
 
-    def _export_recorder(self, st, lat, coef_cur, temb_u, temb_b, cond, coefs, fused_ddim, plan=None):
-        """The recorder of ONE denoise step (the loop body of pipeline_brushnet.py:1250-1332), entered inside the hipGraph capture
-        of that step: the program carries the capture's forks and joins (BrushNet || UNet), replayed by mf_denoise_step_fused."""
+    def _capture(self, one_step, rec=None):
+        """Capture one_step() into a hipGraph (nothing executes) and return it.  `rec`: a program.Recorder(capture=True) that ALSO
+        writes the captured pass down as a step program (program.py)."""
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        self._overlap(True)                      # the side stream forks from / joins the capture stream
+        # No automatic garbage collection inside the capture: a collection that falls into it runs the destructors of
+        # whatever cyclic garbage the process holds (graphs, memory pools, events of earlier calls), and a HIP call made
+        # from one of them while the stream captures ends the process.  torch.cuda.graph collects once on entry; what
+        # becomes garbage during the capture waits until it has ended.
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            # (thread_local: with an initialised process group its watchdog thread may poll events while this thread captures)
+            with torch.cuda.graph(graph, capture_error_mode="thread_local" if (torch.distributed.is_available() and torch.distributed.is_initialized()) else "global"):
+                self._overlap(True)              # (again, now that the capture stream is current: never the side stream itself)
+                with rec if rec is not None else contextlib.nullcontext():
+                    one_step()
+        except Exception:
+            if rec is not None and rec.error is not None:
+                raise rec.error                  # (not the "unjoined work" the aborted capture reports on top of it)
+            raise
+        finally:
+            if gc_was_enabled:
+                gc.enable()
+            self._overlap(False)
+        return graph
+
+    def _export_capture(self, one_step, export, update, st, lat, temb_u, temb_b, cond, nsteps, step, guidance_scale, cond_scale, once):
+        """_capture with ONE denoise step (the loop body of pipeline_brushnet.py:1250-1332) recorded inside the hipGraph capture of that
+        step: the program carries the capture's forks and joins (BrushNet || UNet), replayed by mf_denoise_step_fused."""
         from . import program
         if temb_u is None:
             raise NotImplementedError("export_denoise_step needs precompute_time_embedding (the step reads one row block of the schedule's table)")
-        named = dict(latents=lat, temb_unet=temb_u, temb_brushnet=temb_b, cond=cond)
-        tables = {"table.temb_unet": st["temb_tab"][0].contiguous(), "table.temb_brushnet": st["temb_tab"][1].contiguous()}
-        if fused_ddim:
-            named["coef4"] = coef_cur
-            tables["table.coef4"] = coefs.contiguous()
-        elif plan is not None:
-            # export_denoise_step(scheduler="device"): the PNDM / UniPC update is inside (mf_sched_step_dev); the host copies the step's
-            # row in like coef4, and the history slots stay in "sched_state" between runs
-            named["sched_row"] = st["row_cur"]
-            named["sched_state"] = st["state"]
-            tables["table.sched_row"] = coefs.contiguous()
-        else:
-            # multistep schedulers (PNDM, UniPC: host-side state between steps, scheduling_pndm.py:321-390): the program ends with the
-            # guided noise prediction in the io buffer "eps"; the update of the latents is the host's (mf_axpby_n)
-            named["eps"] = st["eps"]
-        return program.Recorder(named, tables, capture=True)
-
-    def _export_save(self, rec, graph, path, lat, temb_u, temb_b, nsteps, step, guidance_scale, cond_scale):
-        import json
-        rec.finish(graph.pool())
+        io, tables = update.export()
+        rec = program.Recorder(dict(latents=lat, temb_unet=temb_u, temb_brushnet=temb_b, cond=cond, **io),
+                               {"table.temb_unet": st["temb_tab"][0].contiguous(), "table.temb_brushnet": st["temb_tab"][1].contiguous(), **tables},
+                               capture=True)
+        graph = self._capture(one_step, rec)
+        rec.finish(graph.pool())                  # (nothing ran: the buffers still hold what they held BEFORE the recorded step)
         meta = dict(entry="mf_denoise_step_fused", reference="pipelines/brushnet/pipeline_brushnet.py:1250-1332", precision=self.unet.prec.name,
-                    result="latents (DDIM update inside)" if "coef4" in rec.named else
-                    f"latents ({type(self.scheduler).__name__} update inside: mf_sched_step_dev; history in sched_state)" if "sched_row" in rec.named else
-                    "eps (guided noise prediction; the scheduler update is the host's)",
-                    latents=list(lat.shape), steps=nsteps, recorded_step=step, guidance_scale=float(guidance_scale),
+                    result=update.result, latents=list(lat.shape), steps=nsteps, recorded_step=step, guidance_scale=float(guidance_scale),
                     conditioning_scale=cond_scale if isinstance(cond_scale, (int, float)) else list(cond_scale),
-                    temb_unet=list(temb_u.shape), temb_brushnet=list(temb_b.shape), brushnet_once=bool(self._brushnet_once))
-        self._export_info = rec.save(path, meta=json.dumps(meta))
-        self._export_info["meta"] = meta
+                    temb_unet=list(temb_u.shape), temb_brushnet=list(temb_b.shape), brushnet_once=bool(once))
+        export["info"] = rec.save(export["path"], meta=json.dumps(meta))
+        export["info"]["meta"] = meta
+        return graph
 
     def export_denoise_step(self, path: str, scheduler: str = "host", **call_kwargs) -> dict:
         """Run the pipeline once and write the denoise step's program to `path` (see program.py / include/mfhip.h "step programs").
@@ -970,17 +991,14 @@ class StableDiffusionBrushNetPipeline:
             raise NotImplementedError(f"{type(self.scheduler).__name__} has no device update")
         from . import program
         program.refuse_ip_processors(self.unet)      # before anything is captured (the recorder would refuse in the middle of a two-stream capture)
-        self._export_step_to, self._export_sched, self._export_info = path, scheduler, None
-        try:
-            call_kwargs.setdefault("output_type", "latent")
-            out = self(**call_kwargs)
-        finally:
-            self._export_step_to, self._export_sched = None, "host"
-        if self._export_info is None:
+        request = dict(path=path, scheduler=scheduler, info=None)       # travels with the call; _denoise_graph leaves the result in it
+        call_kwargs.setdefault("output_type", "latent")
+        out = self(**call_kwargs, _export=request)
+        if request["info"] is None:
             raise hip.MfhipError("export_denoise_step: the call did not reach a second denoise step on the graph path (num_inference_steps >= 2, "
                                  "use_graph left on)")
-        self._export_info["result"] = out
-        return self._export_info
+        request["info"]["result"] = out
+        return request["info"]
 
     # ---- the two ends of a call as step programs (program.py; include/mfhip.h "step programs") --------------------------------
     def _refuse_vae_switches(self, what: str, batch: int, height: int, width: int, decode: bool = True) -> None:
@@ -1010,7 +1028,6 @@ class StableDiffusionBrushNetPipeline:
         otherwise "cond_noise" holds 2B.  The meta records which, and the `brushnet_once` a step exported from the same call carries.
         Whatever the recorder cannot express (another depth / normals mode, several images per prompt: torch kernels between the
         launches) raises ProgramError here, and no file is written."""
-        import json
         from . import program
         if self.device.type != "cuda":
             raise hip.MfhipError("export_conditioning needs the device: a program is a recording of real launches")
@@ -1036,19 +1053,15 @@ class StableDiffusionBrushNetPipeline:
             depth = torch.as_tensor(depth).to(self.device, torch.float32).contiguous()
             named["depth"] = depth
 
-        def run():
+        def run():                                # (`shared` is decided above: the compare is a torch kernel a program cannot hold)
             img, msk = hip.u8_to_planes(image_u8), hip.u8_to_planes(mask_u8)
-            return self.build_conditioning(img, msk, depth, height, width, nb, num_images_per_prompt, True,
-                                           torch.cat([noise, noise]) if shared else noise, None)
-        self._cond_shared_decided = shared
-        try:
-            run()                                 # warm: tiles tuned, scratch sized
-            with program.Recorder(named) as rec:
-                cond = run()
-                rec.output("cond", cond)
-        finally:
-            self._cond_shared_decided = None
-        once = self._brushnet_shareable(cond, nb, True)
+            return self._conditioning(img, msk, depth, height, width, nb, num_images_per_prompt, True,
+                                      torch.cat([noise, noise]) if shared else noise, None, shared=shared)
+        run()                                     # warm: tiles tuned, scratch sized
+        with program.Recorder(named) as rec:
+            cond, identical = run()
+            rec.output("cond", cond)
+        once = self._brushnet_shareable(cond, nb, True, identical)
         meta = dict(entry="mf_build_conditioning", reference="pipelines/brushnet/pipeline_brushnet.py:1116-1215", precision=self.vae.prec.name,
                     depth_conditioning_mode=self.depth_conditioning_mode, cond_noise_batch=int(noise.shape[0]), batch=nb,
                     shared_conditioning_sample=bool(shared), brushnet_once=bool(once), layouts=rec.layouts)
@@ -1063,7 +1076,6 @@ class StableDiffusionBrushNetPipeline:
         `call_kwargs`: what __call__ takes, with `prompt` (and optionally `negative_prompt`) as text for the pipeline's tokenizer,
         `image` / `mask` as uint8 pixels [B, H, W, 3], `depth` as the normalised fp32 map and `conditioning_noise` given (tokenisation,
         file decoding and random numbers stay the caller's).  examples/c_host/inpaint_host.c runs the directory without Python."""
-        import os
         from . import program
         from .text_encoder import CLIPTextModel
         program.refuse_ip_processors(self.unet)
@@ -1119,14 +1131,8 @@ class StableDiffusionBrushNetPipeline:
         program.write_manifest(directory, manifest)
         return dict(directory=directory, manifest=manifest, programs=infos, result=step["result"])
 
-    def _sched_step(self, noise_pred, t, latents, eta, generator):
-        import inspect
-        params = inspect.signature(self.scheduler.step).parameters
-        extra = {}
-        if "eta" in params:
-            extra["eta"] = eta
-        if "generator" in params:
-            extra["generator"] = generator
+    def _sched_step(self, noise_pred, t, latents, extra):
+        """The host's scheduler step.  `extra`: the eta / generator keywords its step() takes, decided once per call (_HostStep)."""
         return self.scheduler.step(noise_pred, t, latents, **extra, return_dict=False)[0]
 
 
@@ -1276,22 +1282,13 @@ class StableDiffusionXLBrushNetPipeline(StableDiffusionBrushNetPipeline):
         else:
             text = pooled
         ids = ids.repeat(nb, 1)                                              # :1372 (sic: interleaves neg/pos rows)
-        self._added_cond = dict(text_embeds=text.to(self.device), time_ids=ids.to(self.device))
         # denoising_end (pipeline_brushnet_sd_xl.py:1376-1391) and guidance_rescale (:1478-1480) are read by the shared loop
-        self._denoising_end, self._guidance_rescale = denoising_end, float(guidance_rescale or 0.0)
-        try:
-            return super().__call__(image=image, mask=mask, height=height, width=width,
-                                    num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                                    num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator,
-                                    latents=latents, prompt_embeds=prompt_embeds,
-                                    negative_prompt_embeds=negative_prompt_embeds, output_type=output_type,
-                                    return_dict=return_dict, cross_attention_kwargs=cross_attention_kwargs,
-                                    brushnet_conditioning_scale=brushnet_conditioning_scale, guess_mode=guess_mode,
-                                    control_guidance_start=control_guidance_start,
-                                    control_guidance_end=control_guidance_end, clip_skip=clip_skip,
-                                    callback_on_step_end=callback_on_step_end,
-                                    callback_on_step_end_tensor_inputs=list(callback_on_step_end_tensor_inputs),
-                                    conditioning_noise=conditioning_noise, **kwargs)
-        finally:
-            self._added_cond = None
-            self._denoising_end, self._guidance_rescale = None, 0.0
+        return super().__call__(image=image, mask=mask, height=height, width=width, num_inference_steps=num_inference_steps,
+                                guidance_scale=guidance_scale, num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator,
+                                latents=latents, prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+                                output_type=output_type, return_dict=return_dict, cross_attention_kwargs=cross_attention_kwargs,
+                                brushnet_conditioning_scale=brushnet_conditioning_scale, guess_mode=guess_mode,
+                                control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end, clip_skip=clip_skip,
+                                callback_on_step_end=callback_on_step_end, conditioning_noise=conditioning_noise,
+                                callback_on_step_end_tensor_inputs=list(callback_on_step_end_tensor_inputs), _end=denoising_end, _rescale=guidance_rescale,
+                                _added=dict(text_embeds=text.to(self.device), time_ids=ids.to(self.device)), **kwargs)

@@ -133,6 +133,36 @@ def test_tiny_pipeline_graph_with_the_device_update_equals_the_host_loop(name, p
     assert torch.equal(_run(pipe, inp, 6, 16, 16, noise), want)
 
 
+def test_a_kept_graph_is_never_replayed_under_another_scheduler_update():
+    """One pipeline object, _graph_state never reset, the scheduler (and with it the form of the update that ends the captured step)
+    switched between calls: DDIM (fused), PNDM (device plan), PNDM with a callback_on_step_end (host step), UniPC (device plan), DDIM.
+    The graph-cache key carries the update's own part, so every call equals the eager loop of a fresh scheduler bit for bit, and the
+    last one holds no buffer of another form."""
+    from reflecting_reality_amd import DDIMScheduler
+    pipe = _tiny_pipe("fp32")
+    base = pipe.scheduler.config
+    inp = synth.pipeline_inputs(2, 16, 16, seed=17, cross_dim=32, vae_scale=2)
+    noise = torch.randn(4, 4, 8, 8, generator=torch.Generator().manual_seed(4))
+    ddim = lambda: DDIMScheduler.from_config(base)
+    pndm = lambda: PNDMScheduler.from_config(base, skip_prk_steps=True)
+    unipc = lambda: UniPCMultistepScheduler.from_config(base)
+    cb = dict(callback_on_step_end=lambda p, i, t, k: {})
+    sequence = [("ddim", ddim, {}), ("pndm", pndm, {}), ("pndm + callback", pndm, cb), ("unipc", unipc, {}), ("ddim again", ddim, {})]
+    want = {}
+    pipe.use_hip_graph = False
+    for name, mk in (("ddim", ddim), ("pndm", pndm), ("unipc", unipc)):        # the eager loop, once per scheduler
+        pipe.scheduler = mk()
+        want[name] = _run(pipe, inp, 6, 16, 16, noise)
+    pipe.use_hip_graph, pipe._graph_state = True, None
+    for name, mk, kw in sequence:
+        pipe.scheduler = mk()
+        got = _run(pipe, inp, 6, 16, 16, noise, **kw)
+        assert pipe._graph_state is not None and pipe._graph_state["graph"] is not None, f"{name}: not on the graph path"
+        ref = want[name.split()[0]]
+        assert torch.equal(got, ref), f"{name}: differs from the eager loop by {(got - ref).abs().max()}"
+    assert "state" not in pipe._graph_state and "eps" not in pipe._graph_state, "the last DDIM call kept another update's graph state"
+
+
 @pytest.mark.parametrize("name", ["unipc", "pndm"])
 def test_config1_device_update_equals_the_host_update(name):
     """configs[1] (batch 4 x 512^2, bf16, 10 steps) under the schedulers the shipped scripts run: the device update gives the host

@@ -96,13 +96,19 @@ def test_xl_denoising_end_and_guidance_rescale():
     kw = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"], pooled_prompt_embeds=pooled,
               negative_pooled_prompt_embeds=npooled, image=inp["image"], mask=inp["mask"], guidance_scale=5.0, output_type="latent",
               height=16, width=16, conditioning_noise=inp["vae_noise"])
+    plain = pipe(latents=inp["latents"].clone(), num_inference_steps=10, **kw).images.float().cpu()
     steps = []
     pipe(latents=inp["latents"].clone(), num_inference_steps=10, denoising_end=0.5,
          callback_on_step_end=lambda p, i, t, k: steps.append(int(t)) or {}, **kw)
     full = DDIMScheduler(**SD_SCHED, clip_sample=False)
     full.set_timesteps(10)
     assert steps == [int(t) for t in full.timesteps if int(t) >= 500] and 0 < len(steps) < 10
-    assert pipe._denoising_end is None and pipe._guidance_rescale == 0.0                   # call-scoped
+    # call-scoped: a following call without denoising_end / guidance_rescale runs the whole schedule and gives the plain call's latents
+    steps = []
+    after = pipe(latents=inp["latents"].clone(), num_inference_steps=10,
+                 callback_on_step_end=lambda p, i, t, k: steps.append(int(t)) or {}, **kw).images.float().cpu()
+    assert steps == [int(t) for t in full.timesteps] and len(steps) == 10
+    assert torch.equal(after, plain)
     # guidance_rescale: record what reaches the scheduler
     from reflecting_reality_amd import hip
     seen = {}
@@ -117,6 +123,7 @@ def test_xl_denoising_end_and_guidance_rescale():
         seen["np"] = noise_pred.float().clone()
         return real_step(noise_pred, *a, **k)
 
+    plain2 = pipe(latents=inp["latents"].clone(), num_inference_steps=2, **kw).images.float().cpu()
     hip.cfg_combine, pipe._sched_step = cfg, step
     try:
         a = pipe(latents=inp["latents"].clone(), num_inference_steps=2, guidance_rescale=0.7, **kw).images.float().cpu()
@@ -128,6 +135,7 @@ def test_xl_denoising_end_and_guidance_rescale():
     assert (seen["np"] - want).abs().max().item() <= 1e-5 * max(1.0, want.abs().max().item())
     b = pipe(latents=inp["latents"].clone(), num_inference_steps=2, **kw).images.float().cpu()
     assert (a - b).abs().max().item() > 1e-4, "guidance_rescale changed nothing"
+    assert torch.equal(b, plain2), "guidance_rescale outlived its call"
 
 
 # ---- BASELINE.json configs[4] at its own size: SDXL-base + BrushNet-XL, batch 2 x 1024 x 1024, 30-step grid -------------------

@@ -855,7 +855,9 @@ __global__ __launch_bounds__(BWD_NW * 64, 1) void attn_bwd_kernel(const AttnBwdA
         wait_vmcnt<0>();
         __syncthreads();
     }
-    if constexpr (!B16) mf_raise_if_over(&g_split_ovf_attn, amax);
+    // a ghost column lane (ci >= sc: zero fragments, T = U = 0) still evaluates P = exp2(pshift - lse) and dS = -scale P D, huge on a
+    // row whose lse is very negative; nothing of it is ever stored, so it must not raise the flag either
+    if constexpr (!B16) mf_raise_if_over(&g_split_ovf_attn, ci < p.sc ? amax : 0.0f);
 
     // ---- epilogue: transpose through LDS, row-contiguous fp32 stores ----
     char* Os = smem + wave * 32 * RBO;

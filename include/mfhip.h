@@ -725,7 +725,8 @@ int mf_lpips_finish(const void* ws, int32_t batch, float* rows_out, void* stream
  * ========================================================================================== */
 
 /* Weight gradient of mf_gemm_conv's convolution (same geometry fields): dw[n][(ky*kw + kx)*(c0+c1) + c] (+)= sum over
- * output pixels m of dy[m][n] * A[pixel(m, ky, kx)][c].  dtype MF_F32 (fp32 MFMA) or MF_F16X3 (split precision).
+ * output pixels m of dy[m][n] * A[pixel(m, ky, kx)][c].  dtype MF_F32 (fp32 MFMA), MF_F16X3 (split precision), MF_BF16X1 (fp32
+ * operands rounded to bf16 while staged) or MF_BF16 (bf16 operands in memory); dw is fp32 in every one.
  * Replaces autograd's conv2d / linear weight gradients (torch/nn/grad.py conv2d_weight; linear: dy^T x). */
 typedef struct mf_wgrad_desc {
     /* MF_F32 / MF_F16X3 / MF_BF16X1: fp32 a0 / a1 / dy (rounded or split while staged).  MF_BF16: a0 / a1 / dy are bf16 tensors
@@ -746,8 +747,26 @@ typedef struct mf_wgrad_desc {
 int mf_sizeof_wgrad_desc(void);
 int64_t mf_conv_wgrad_ws_floats(const mf_wgrad_desc* d);
 int mf_conv_wgrad(const mf_wgrad_desc* d, void* stream);
+/* What mf_conv_wgrad would do with a descriptor, decided on the host: mf_conv_wgrad is this plan followed by its launches.
+ * mf_conv_wgrad_plan makes every check and every choice of the call (same return code, same mf_last_error text), launches nothing,
+ * needs no GPU and reads nothing behind the descriptor's pointers (their null-ness and alignment count).  It answers for the current
+ * value of mf_debug_set_wgrad_dma's switch. */
+typedef struct mf_wgrad_plan {
+    int32_t form;               /* 0 fp32, 1 128-wide register-staged, 2 160-wide, 3 128-wide LDS-DMA */
+    int32_t tile_w;             /* the tile is tile_w (n) x tile_w (channels of one tap): 128 or 160 */
+    int32_t tiles;              /* output tiles: ceil(n / tile_w) * ceil((c0 + c1) / tile_w) * kh * kw */
+    int32_t splitm;             /* slabs over the pixel dimension, after "no empty slabs" */
+    int32_t m_per_split;        /* pixels per slab, a multiple of 32 */
+    int32_t reduce_launch;      /* 1: the slabs go to the workspace and a slab-sum launch follows; 0: the kernel completes dw itself */
+    int32_t slabs_xcd;          /* the first slabs_xcd slabs (splitm rounded down to a multiple of 8) are pinned to XCDs */
+    int32_t blocks;             /* blocks of the main launch: tiles * splitm (form 0 launches them as a tiles x splitm grid) */
+    int32_t threads;            /* threads per block */
+    int32_t lds_bytes;          /* dynamic LDS bytes of the main launch */
+} mf_wgrad_plan;
+int mf_conv_wgrad_plan(const mf_wgrad_desc* d, mf_wgrad_plan* out);
+int mf_sizeof_wgrad_plan(void);
 /* Developer / test switch: 0 routes bf16-input weight gradients to the register-staged kernel instead of the LDS-DMA one (the two are
- * bit-identical; tests compare them).  Process-wide, not thread-safe against concurrent mf_conv_wgrad calls. */
+ * bit-identical; tests compare them).  On by default.  Process-wide, not thread-safe against concurrent mf_conv_wgrad calls. */
 void mf_debug_set_wgrad_dma(int on);
 
 /* base[offs[i] .. offs[i] + lens[i]) = 0 for i < count, one launch (offs / lens: DEVICE arrays of int64, element units).  The training

@@ -55,9 +55,7 @@ constexpr int WG_BN = 128, WG_BC = 128, WG_BP = 32, WG_PITCH = 132;   // LDS row
 // (register -> LDS, single buffered: correctness-first; the reduction over pixels is split over blockIdx.y).
 __device__ unsigned g_split_ovf_train;    // raised when an MF_F16X3 wgrad operand exceeded the fp16 range (mf_common.h)
 
-template <int DT>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs p) {
-    float wg_amax = 0.0f;
     __shared__ __attribute__((aligned(16))) float sY[WG_BP * WG_PITCH];
     __shared__ __attribute__((aligned(16))) float sA[WG_BP * WG_PITCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -113,65 +111,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs p) {
         __syncthreads();
         const float* py = sY + wn * 64 + r;
         const float* pa = sA + wk * 64 + r;
-        if constexpr (DT == MF_F32) {
 #pragma unroll
-            for (int s = 0; s < WG_BP / 2; ++s) {
-                const float y0 = py[(2 * s + h) * WG_PITCH], y1 = py[(2 * s + h) * WG_PITCH + 32];
-                const float a0 = pa[(2 * s + h) * WG_PITCH], a1 = pa[(2 * s + h) * WG_PITCH + 32];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(y0, a0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(y0, a1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(y1, a0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(y1, a1, acc[1][1], 0, 0, 0);
-            }
-        } else {
-            // fp32 -> (hi, lo) fp16 halves, three MFMAs per product (the split precision of mf_gemm_conv)
-#pragma unroll
-            for (int s = 0; s < WG_BP / 16; ++s) {
-                f16x8_t Yh[2], Yl[2], Ah[2], Al[2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    unsigned yh[4], yl[4], ah[4], al[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int pp = 16 * s + 8 * h + 2 * e;
-                        const float y0 = py[pp * WG_PITCH + 32 * t], y1 = py[(pp + 1) * WG_PITCH + 32 * t];
-                        const float a0 = pa[pp * WG_PITCH + 32 * t], a1 = pa[(pp + 1) * WG_PITCH + 32 * t];
-                        if constexpr (DT == MF_BF16X1) {       // one bf16 MFMA per product: operands rounded to nearest-even
-                            yh[e] = pack_bf16x2(y0, y1); ah[e] = pack_bf16x2(a0, a1);
-                            yl[e] = 0; al[e] = 0;
-                        } else {
-                            wg_amax = mf_amax3(mf_amax3(wg_amax, y0, y1), a0, a1);
-                            const auto hy = __builtin_amdgcn_cvt_pkrtz(y0, y1);
-                            const auto ly = __builtin_amdgcn_cvt_pkrtz(y0 - (float)hy[0], y1 - (float)hy[1]);
-                            const auto ha = __builtin_amdgcn_cvt_pkrtz(a0, a1);
-                            const auto la = __builtin_amdgcn_cvt_pkrtz(a0 - (float)ha[0], a1 - (float)ha[1]);
-                            yh[e] = __builtin_bit_cast(unsigned, hy); yl[e] = __builtin_bit_cast(unsigned, ly);
-                            ah[e] = __builtin_bit_cast(unsigned, ha); al[e] = __builtin_bit_cast(unsigned, la);
-                        }
-                    }
-                    Yh[t] = __builtin_bit_cast(f16x8_t, uint4{yh[0], yh[1], yh[2], yh[3]});
-                    Yl[t] = __builtin_bit_cast(f16x8_t, uint4{yl[0], yl[1], yl[2], yl[3]});
-                    Ah[t] = __builtin_bit_cast(f16x8_t, uint4{ah[0], ah[1], ah[2], ah[3]});
-                    Al[t] = __builtin_bit_cast(f16x8_t, uint4{al[0], al[1], al[2], al[3]});
-                }
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        if constexpr (DT == MF_BF16X1) {
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, Yh[i]),
-                                                                                __builtin_bit_cast(bf16x8_t, Ah[j]), acc[i][j], 0, 0, 0);
-                        } else {
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Yl[i], Ah[j], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Yh[i], Al[j], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Yh[i], Ah[j], acc[i][j], 0, 0, 0);
-                        }
-                    }
-            }
+        for (int s = 0; s < WG_BP / 2; ++s) {
+            const float y0 = py[(2 * s + h) * WG_PITCH], y1 = py[(2 * s + h) * WG_PITCH + 32];
+            const float a0 = pa[(2 * s + h) * WG_PITCH], a1 = pa[(2 * s + h) * WG_PITCH + 32];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(y0, a0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(y0, a1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(y1, a0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(y1, a1, acc[1][1], 0, 0, 0);
         }
         __syncthreads();
     }
-    if constexpr (DT == MF_F16X3) mf_raise_if_over(&g_split_ovf_train, wg_amax);
     // D[row = n (e & 3) + 8 (e >> 2) + 4 h][col = c r]
     float* out = p.out + (int64_t)blockIdx.y * p.slab;
 #pragma unroll
@@ -188,9 +138,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs p) {
         }
 }
 
-// ---- the 16-bit forms (MF_F16X3, MF_BF16X1), second version -------------------------------------------------------------
+// ---- the 16-bit forms (MF_F16X3, MF_BF16X1) ------------------------------------------------------------------------------
 // Same 128 (n) x 128 (c of one tap) tile and 64 x 64 per wave, but the operands are converted ONCE while they are staged
-// (above: every element is read from LDS as fp32 by two waves, one ds_read_b32 per element, and split in both) into 16-bit
+// (their first version staged fp32 as above: every element read from LDS by two waves, one ds_read_b32 each, and split in both) into 16-bit
 // planes [pixel][128 columns] (256-byte rows, 16-byte chunks XOR-swizzled), and the MFMA fragments — eight consecutive PIXELS of
 // one column — come out of two ds_read_b64_tr_b16 (the hardware's transposing read: a quarter of the read instructions, twice
 // the LDS bytes per clock of ds_read_b32).  Two LDS stages: the global loads of tile t+1 are in flight during the MFMAs of
@@ -1115,7 +1065,7 @@ __global__ __launch_bounds__(256) void groupnorm_bwd_kernel(const GnBwdArgs p) {
 // C: dx = rstd * (dz * gamma - m1 - xhat * m2)
 // One block per (image, group) as above leaves one block per CU and 40-byte runs per pixel at 320 channels (10 per group):
 // ~125 us on average over the step's GroupNorms; the sums are fp32 over the <= 64 pixels of a chunk, double across chunks.
-constexpr int GN_BWD_MAX_BATCH = 64;          // images per call of the fused parameter-gradient form (gn_bwd2_reduce_acc_kernel)
+constexpr int GN_BWD_MAX_BATCH = 64;          // images per call of the fused parameter-gradient form (dgamma_acc / dbeta_acc)
 struct GnBwd2Args {
     GnBwdArgs a;
     float* part;        // [batch][chunks][2][C]
@@ -1277,63 +1227,10 @@ __global__ __launch_bounds__(256) void gn_bwd2_reduce_kernel(const GnBwd2Args q2
     }
 }
 
-// R2 with the parameter gradients finished in the same launch: one block per GROUP, images in turn; dgamma / dbeta of a channel are
-// summed over the images in a register (fixed order) and ADDED to the gradient arena — the per-image partials and the two
-// mf_colsum calls (four launches) that used to follow every GroupNorm backward are gone.
-__global__ __launch_bounds__(256) void gn_bwd2_reduce_acc_kernel(const GnBwd2Args q2, float* dgamma_acc, float* dbeta_acc) {
-    const GnBwdArgs& p = q2.a;
-    __shared__ double red[2][4][GN_BWD_MAX_BATCH];
-    const int C = p.c0 + p.c1, cpg = C / p.groups;
-    const int g = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < 2 * 4 * GN_BWD_MAX_BATCH; i += 256) (&red[0][0][0])[i] = 0.0;
-    __syncthreads();
-    for (int cc = wave; cc < cpg; cc += 4) {
-        const int c = g * cpg + cc;
-        const double gm = (double)p.gamma[c];
-        double da = 0.0, db = 0.0;
-        // eight images per round: their partial loads are all in flight before the first reduction (one memory round trip per
-        // round instead of one per image — this kernel runs on `groups` blocks only and was latency-bound at ~50 us)
-        for (int b0 = 0; b0 < p.batch; b0 += 8) {
-            double a[8], bb[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                a[u] = 0.0; bb[u] = 0.0;
-                if (b0 + u < p.batch)
-                    for (int ch = lane; ch < q2.chunks; ch += 64) {
-                        const float* src = q2.part + (((int64_t)(b0 + u) * q2.chunks + ch) * 2) * C + c;
-                        a[u] += (double)src[0]; bb[u] += (double)src[C];
-                    }
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { a[u] += __shfl_xor(a[u], o, 64); bb[u] += __shfl_xor(bb[u], o, 64); }
-                if (b0 + u < p.batch) {
-                    da += a[u]; db += bb[u];
-                    if (lane == 0) { red[0][wave][b0 + u] += a[u] * gm; red[1][wave][b0 + u] += bb[u] * gm; }   // this wave's share of the image's group sums
-                }
-            }
-        }
-        if (lane == 0) {
-            dbeta_acc[c] += (float)da;
-            dgamma_acc[c] += (float)db;
-        }
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < p.batch; b += 256) {
-        const double s = (red[0][0][b] + red[0][1][b]) + (red[0][2][b] + red[0][3][b]);
-        const double ss = (red[1][0][b] + red[1][1][b]) + (red[1][2][b] + red[1][3][b]);
-        const double n = (double)p.hw * cpg;
-        float* st = q2.stats + ((int64_t)b * p.groups + g) * 4;
-        st[2] = (float)(s / n);
-        st[3] = (float)(ss / n);
-    }
-}
-
-// The fused parameter-gradient form, second version: the per-image partials of gn_bwd2_reduce_kernel<1> (batch x groups blocks)
-// summed over the batch in image order and ADDED to the arena — two short launches on many blocks instead of one block per group
-// walking every image and channel (51 us on 2560-channel inputs; now ~8 + 3).
+// The fused parameter-gradient form: the per-image partials of gn_bwd2_reduce_kernel<1> (batch x groups blocks) summed over the
+// batch in image order and ADDED to the arena — the per-image partials and the two mf_colsum calls (four launches) that used to
+// follow every GroupNorm backward are gone.  Two short launches on many blocks (~8 + 3 us on 2560-channel inputs; one block per
+// group walking every image and channel, the first version, took 51).
 __global__ __launch_bounds__(256) void gn_bwd2_batchsum_acc_kernel(const float* __restrict__ dg_part, const float* __restrict__ db_part,
                                                                    float* dgamma_acc, float* dbeta_acc, int batch, int C) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -1656,12 +1553,14 @@ unsigned* mf_ovf_flag_train() {
 extern "C" int mf_sizeof_wgrad_desc(void) { return (int)sizeof(mf_wgrad_desc); }
 extern "C" int mf_sizeof_groupnorm_bwd_desc(void) { return (int)sizeof(mf_groupnorm_bwd_desc); }
 
+// The most slabs the heuristic split of M output pixels takes: at least 256 pixels per slab, 64 slabs (wgrad_plan lowers it to the workspace).
+static inline int wgrad_split_cap(int64_t M) { return M / 256 < 1 ? 1 : (M / 256 > 64 ? 64 : (int)(M / 256)); }
+
 extern "C" int64_t mf_conv_wgrad_ws_floats(const mf_wgrad_desc* d) {
     if (!d) return 0;
     const int64_t M = (int64_t)d->batch * d->h_out * d->w_out;
     const int64_t K = (int64_t)d->kh * d->kw * (d->c0 + d->c1);
-    int64_t sm = d->splitm;
-    if (sm <= 0) sm = M / 256 > 64 ? 64 : (M / 256 < 1 ? 1 : M / 256);
+    const int64_t sm = d->splitm > 0 ? d->splitm : wgrad_split_cap(M);
     return sm * d->n * K;
 }
 
@@ -1688,10 +1587,21 @@ extern "C" int mf_zero_ranges(float* base, const int64_t* offs, const int64_t* l
     return MF_OK;
 }
 
-static int g_wgrad_dma = getenv("MFHIP_WGRAD_NO_DMA") ? 0 : 1;      // the LDS-DMA form of the bf16-input weight gradient
+static int g_wgrad_dma = 1;                                           // the LDS-DMA form of the bf16-input weight gradient
 extern "C" void mf_debug_set_wgrad_dma(int on) { g_wgrad_dma = on; }  // developer / test switch (the two forms are bit-identical)
 
-extern "C" int mf_conv_wgrad(const mf_wgrad_desc* d, void* stream) {
+// What one mf_conv_wgrad call launches.  wgrad_plan makes every check and every choice of the call on the host (no HIP call, nothing
+// behind the descriptor's pointers is read); mf_conv_wgrad is this plan, its WgradArgs, one launch and, where the plan says so, the slab sum.
+enum { WG_FORM_F32 = 0, WG_FORM_TR128 = 1, WG_FORM_TR160 = 2, WG_FORM_DMA128 = 3 };
+struct WgradPlan {
+    mf_wgrad_plan pub;                 // the part mf_conv_wgrad_plan reports
+    int M; int64_t K;                  // output pixels; taps * channels
+    int tiles_n, tiles_k_per_tap;
+    bool direct;                       // one slab and the kernel writes (or adds into) dW itself: no slab sum
+    int acc_out;                       // ... and adds
+};
+
+static int wgrad_plan(const mf_wgrad_desc* d, int dma_enabled, WgradPlan* p) {
     MF_CHECK_ARG(d != nullptr, "mf_conv_wgrad: null descriptor");
     MF_CHECK_ARG(d->dtype == MF_F32 || d->dtype == MF_F16X3 || d->dtype == MF_BF16X1 || d->dtype == MF_BF16,
                  "mf_conv_wgrad: dtype must be MF_F32, MF_F16X3, MF_BF16X1 or MF_BF16");
@@ -1709,37 +1619,28 @@ extern "C" int mf_conv_wgrad(const mf_wgrad_desc* d, void* stream) {
         mf_set_error("mf_conv_wgrad: a0/a1/dy must be 16-byte aligned, lddy a multiple of 4");
         return MF_EALIGN;
     }
-    static const bool wgrad_xcd = getenv("MFHIP_WGRAD_NO_XCD") == nullptr;            // developer A/B
-    WgradArgs a{};
-    a.a0 = d->a0; a.a1 = d->a1; a.C0 = d->c0; a.Ctot = d->c0 + d->c1; a.lda0 = d->lda0; a.lda1 = d->lda1;
-    a.Hin = d->h_in; a.Win = d->w_in; a.Ho = d->h_out; a.Wo = d->w_out; a.HoWo = d->h_out * d->w_out;
-    a.KW = d->kw; a.taps = d->kh * d->kw; a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.ups = d->upsample;
-    a.dy = d->dy; a.lddy = d->lddy;
-    wg_fastdiv_make((unsigned)a.HoWo, &a.mul_howo, &a.sh_howo);
-    wg_fastdiv_make((unsigned)a.Wo, &a.mul_wo, &a.sh_wo);
+    const int N = d->n, Ctot = d->c0 + d->c1, taps = d->kh * d->kw;
     const int64_t M64 = (int64_t)d->batch * d->h_out * d->w_out;
     MF_CHECK_ARG(M64 < (1ll << 31), "mf_conv_wgrad: M too large");
-    a.M = (int)M64; a.N = d->n;
-    const int64_t K = (int64_t)a.taps * a.Ctot;
+    const int M = (int)M64;
+    const int64_t K = (int64_t)taps * Ctot;
     MF_CHECK_ARG(d->lddw >= K, "mf_conv_wgrad: lddw < K");
-    const bool tr_form = d->dtype != MF_F32 && getenv("MFHIP_WGRAD_V1") == nullptr;
-    static const bool no160 = getenv("MFHIP_WGRAD_128") != nullptr;                   // developer A/B
+    const bool tr_form = d->dtype != MF_F32;
     // Tile form (128 x 128 / four waves, or 160 x 160 / five waves) and pixel split are chosen together by a cost model: rounds of
     // 512 resident blocks (2 per CU) x 32-pixel steps per block x the measured step time of the form (2.3 / 3.7 us: the 160 form
     // does 1.56 x the products per step and pads 320-multiples less, but has fewer, longer blocks to spread), plus the slabs'
     // write + read (N K floats each way per slab at ~4 TB/s) unless one slab adds into dW itself.
-    int cap = a.M / 256 < 1 ? 1 : a.M / 256;
-    if (cap > 64) cap = 64;
+    int cap = wgrad_split_cap(M);
     if (d->ws == nullptr) cap = 1;
-    else if ((int64_t)cap * a.N * K > d->ws_floats) cap = (int)(d->ws_floats / ((int64_t)a.N * K)) < 1 ? 1 : (int)(d->ws_floats / ((int64_t)a.N * K));
-    auto tiles_of = [&](int w) { return (int64_t)((a.N + w - 1) / w) * ((a.Ctot + w - 1) / w) * a.taps; };
+    else if ((int64_t)cap * N * K > d->ws_floats) cap = (int)(d->ws_floats / ((int64_t)N * K)) < 1 ? 1 : (int)(d->ws_floats / ((int64_t)N * K));
+    auto tiles_of = [&](int w) { return (int64_t)((N + w - 1) / w) * ((Ctot + w - 1) / w) * taps; };
     auto model = [&](int w, double step_us, int* best_c) {
         double best = 1e300;
         *best_c = 1;
         for (int c = 1; c <= cap; ++c) {
             const int64_t blocks = tiles_of(w) * c, rounds = (blocks + 511) / 512;
-            const int64_t steps = (((int64_t)a.M + c - 1) / c + WG_BP - 1) / WG_BP;
-            const double slab_us = c == 1 ? 0.0 : (double)c * a.N * K * 8.0 / 4.0e6 + 4.0;
+            const int64_t steps = (((int64_t)M + c - 1) / c + WG_BP - 1) / WG_BP;
+            const double slab_us = c == 1 ? 0.0 : (double)c * N * K * 8.0 / 4.0e6 + 4.0;
             const double cost = (double)rounds * steps * step_us + slab_us;
             if (cost < best * 0.98) { best = cost; *best_c = c; }                        // a larger split has to pay for itself
         }
@@ -1747,11 +1648,9 @@ extern "C" int mf_conv_wgrad(const mf_wgrad_desc* d, void* stream) {
     };
     int c128 = 1, c160 = 1;
     const double cost128 = model(WG_BN, 2.3, &c128);
-    const double cost160 = tr_form && !no160 ? model(W160, 3.7, &c160) : 1e300;
+    const double cost160 = tr_form ? model(W160, 3.7, &c160) : 1e300;
     const bool t160 = cost160 < cost128;
     const int tile_w = t160 ? W160 : WG_BN;
-    a.tiles_n = (a.N + tile_w - 1) / tile_w;
-    a.tiles_k_per_tap = (a.Ctot + tile_w - 1) / tile_w;
     const int64_t tiles = tiles_of(tile_w);
     int sm = d->splitm;
     if (sm <= 0) {
@@ -1762,57 +1661,114 @@ extern "C" int mf_conv_wgrad(const mf_wgrad_desc* d, void* stream) {
             sm = t160 ? c160 : c128;
         }
     }
-    MF_CHECK_ARG(sm == 1 || (d->ws && (int64_t)sm * a.N * K <= d->ws_floats), "mf_conv_wgrad: split-M=%d needs %lld workspace floats", sm,
-                 (long long)sm * a.N * K);
-    a.m_per_split = ((a.M + sm - 1) / sm + WG_BP - 1) / WG_BP * WG_BP;
-    a.splitm = (a.M + a.m_per_split - 1) / a.m_per_split;
+    MF_CHECK_ARG(sm == 1 || (d->ws && (int64_t)sm * N * K <= d->ws_floats), "mf_conv_wgrad: split-M=%d needs %lld workspace floats", sm,
+                 (long long)sm * N * K);
+    mf_wgrad_plan& q = p->pub;
+    q.tile_w = tile_w;
+    q.tiles = (int)tiles;
+    q.m_per_split = ((M + sm - 1) / sm + WG_BP - 1) / WG_BP * WG_BP;
+    q.splitm = (M + q.m_per_split - 1) / q.m_per_split;
     // one slab: the 16-bit kernel adds into dW itself (single writer per element: still deterministic)
-    const bool direct = a.splitm == 1 && (!d->accumulate || tr_form);
-    a.acc_out = direct && d->accumulate;
-    a.out = direct ? d->dw : d->ws;
-    a.ldo = direct ? d->lddw : K;
-    a.slab = (int64_t)a.N * K;
-    a.slabs_xcd = wgrad_xcd ? a.splitm / 8 * 8 : 0;
-    MF_CHECK_ARG(direct || d->ws, "mf_conv_wgrad: accumulate needs a workspace");
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)tiles, (unsigned)a.splitm);
-    const dim3 grid1((unsigned)(tiles * a.splitm));
-    static const bool old_form = getenv("MFHIP_WGRAD_V1") != nullptr;        // developer A/B: the first version of the 16-bit forms
-    if (d->dtype == MF_F32) hipLaunchKernelGGL(conv_wgrad_kernel<MF_F32>, grid, dim3(256), 0, s, a);
-    else if (old_form && !in16) {
-        if (d->dtype == MF_BF16X1) hipLaunchKernelGGL(conv_wgrad_kernel<MF_BF16X1>, grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(conv_wgrad_kernel<MF_F16X3>, grid, dim3(256), 0, s, a);
+    p->direct = q.splitm == 1 && (!d->accumulate || tr_form);
+    p->acc_out = p->direct && d->accumulate;
+    MF_CHECK_ARG(p->direct || d->ws, "mf_conv_wgrad: accumulate needs a workspace");
+    q.reduce_launch = !p->direct;
+    q.slabs_xcd = q.splitm / 8 * 8;
+    p->M = M; p->K = K;
+    p->tiles_n = (N + tile_w - 1) / tile_w;
+    p->tiles_k_per_tap = (Ctot + tile_w - 1) / tile_w;
+    const int planes = d->dtype == MF_F16X3 ? 2 * 4 : 2 * 2;          // two stages of (hi, lo) x 2 or of one 16-bit plane x 2
+    if (!tr_form) {
+        q.form = WG_FORM_F32; q.threads = 256; q.lds_bytes = 0;       // (its two staging tiles are static LDS)
     } else if (t160) {
-        static const bool attr160 = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_tr160_kernel<MF_F16X3, 2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * W160_PLANE);
-            return true;
-        }();
-        (void)attr160;
         // (one LDS stage + a second barrier per step measured the same as two stages: 383 vs 371 us on 8 x 64 x 64 320 -> 320 3x3)
-        if (in16) hipLaunchKernelGGL((conv_wgrad_tr160_kernel<MF_BF16X1, 2, true>), grid1, dim3(320), 2 * 2 * W160_PLANE, s, a);
-        else if (d->dtype == MF_BF16X1) hipLaunchKernelGGL((conv_wgrad_tr160_kernel<MF_BF16X1, 2>), grid1, dim3(320), 2 * 2 * W160_PLANE, s, a);
-        else hipLaunchKernelGGL((conv_wgrad_tr160_kernel<MF_F16X3, 2>), grid1, dim3(320), 2 * 4 * W160_PLANE, s, a);
-    } else if (in16 && g_wgrad_dma && (!a.a1 || a.C0 % WG_BC == 0) && (int64_t)a.M * a.lddy * 2 < 0x7fffffffll &&
-               (int64_t)(a.M / a.HoWo) * a.Hin * a.Win * (a.lda0 > a.lda1 ? a.lda0 : a.lda1) * 2 < 0x7fffffffll) {
-        hipLaunchKernelGGL(conv_wgrad_dma_kernel, grid1, dim3(256), WD_NST * 2 * WT_PLANE, s, a);
-    } else if (in16) {
-        hipLaunchKernelGGL((conv_wgrad_tr_kernel<MF_BF16X1, true>), grid1, dim3(256), 2 * 2 * WT_PLANE, s, a);
-    } else if (d->dtype == MF_BF16X1) {
-        hipLaunchKernelGGL(conv_wgrad_tr_kernel<MF_BF16X1>, grid1, dim3(256), 2 * 2 * WT_PLANE, s, a);
+        q.form = WG_FORM_TR160; q.threads = 320; q.lds_bytes = planes * W160_PLANE;
+    } else if (in16 && dma_enabled && (!d->a1 || d->c0 % WG_BC == 0) && (int64_t)M * d->lddy * 2 < 0x7fffffffll &&
+               (int64_t)d->batch * d->h_in * d->w_in * (d->lda0 > d->lda1 ? d->lda0 : d->lda1) * 2 < 0x7fffffffll) {
+        // one input segment per tile, and 32-bit byte offsets into dy and the inputs (buffer loads)
+        q.form = WG_FORM_DMA128; q.threads = 256; q.lds_bytes = WD_NST * 2 * WT_PLANE;
     } else {
-        static const bool attr = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_tr_kernel<MF_F16X3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      2 * 4 * WT_PLANE);
-            return true;
-        }();
-        (void)attr;
-        hipLaunchKernelGGL(conv_wgrad_tr_kernel<MF_F16X3>, grid1, dim3(256), 2 * 4 * WT_PLANE, s, a);
+        q.form = WG_FORM_TR128; q.threads = 256; q.lds_bytes = planes * WT_PLANE;
     }
+    q.blocks = (int)(tiles * q.splitm);       // forms 1-3: a 1-D grid; the fp32 kernel: tiles x splitm
+    return MF_OK;
+}
+
+extern "C" int mf_sizeof_wgrad_plan(void) { return (int)sizeof(mf_wgrad_plan); }
+
+extern "C" int mf_conv_wgrad_plan(const mf_wgrad_desc* d, mf_wgrad_plan* out) {
+    MF_CHECK_ARG(out != nullptr, "mf_conv_wgrad_plan: null plan");
+    WgradPlan p{};
+    const int rc = wgrad_plan(d, g_wgrad_dma, &p);
+    if (rc == MF_OK) *out = p.pub;
+    return rc;
+}
+
+// The kernel of a (form, dtype) and whether its dynamic LDS is above the default limit (the attribute is then set before the launch).
+struct WgradKernel { int form, dtype; const void* fn; bool lds_attr; };
+#define WG_FN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+static const WgradKernel kWgradKernels[] = {
+    {WG_FORM_F32, MF_F32, WG_FN(conv_wgrad_kernel), false},
+    {WG_FORM_TR128, MF_F16X3, WG_FN(conv_wgrad_tr_kernel<MF_F16X3>), true},
+    {WG_FORM_TR128, MF_BF16X1, WG_FN(conv_wgrad_tr_kernel<MF_BF16X1>), false},
+    {WG_FORM_TR128, MF_BF16, WG_FN(conv_wgrad_tr_kernel<MF_BF16X1, true>), false},
+    {WG_FORM_TR160, MF_F16X3, WG_FN(conv_wgrad_tr160_kernel<MF_F16X3, 2>), true},
+    {WG_FORM_TR160, MF_BF16X1, WG_FN(conv_wgrad_tr160_kernel<MF_BF16X1, 2>), false},
+    {WG_FORM_TR160, MF_BF16, WG_FN(conv_wgrad_tr160_kernel<MF_BF16X1, 2, true>), false},
+    {WG_FORM_DMA128, MF_BF16, WG_FN(conv_wgrad_dma_kernel), false},
+};
+#undef WG_FN
+constexpr int WG_NKERNELS = sizeof(kWgradKernels) / sizeof(kWgradKernels[0]);
+
+extern "C" int mf_conv_wgrad(const mf_wgrad_desc* d, void* stream) {
+    WgradPlan p{};
+    const int rc = wgrad_plan(d, g_wgrad_dma, &p);
+    if (rc != MF_OK) return rc;
+    const mf_wgrad_plan& q = p.pub;
+    WgradArgs a{};
+    a.a0 = d->a0; a.a1 = d->a1; a.C0 = d->c0; a.Ctot = d->c0 + d->c1; a.lda0 = d->lda0; a.lda1 = d->lda1;
+    a.Hin = d->h_in; a.Win = d->w_in; a.Ho = d->h_out; a.Wo = d->w_out; a.HoWo = d->h_out * d->w_out;
+    a.KW = d->kw; a.taps = d->kh * d->kw; a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.ups = d->upsample;
+    a.dy = d->dy; a.lddy = d->lddy;
+    wg_fastdiv_make((unsigned)a.HoWo, &a.mul_howo, &a.sh_howo);
+    wg_fastdiv_make((unsigned)a.Wo, &a.mul_wo, &a.sh_wo);
+    a.M = p.M; a.N = d->n;
+    a.tiles_n = p.tiles_n; a.tiles_k_per_tap = p.tiles_k_per_tap;
+    a.m_per_split = q.m_per_split; a.splitm = q.splitm;
+    a.acc_out = p.acc_out;
+    a.out = p.direct ? d->dw : d->ws;
+    a.ldo = p.direct ? d->lddw : p.K;
+    a.slab = (int64_t)a.N * p.K;
+    a.slabs_xcd = q.slabs_xcd;
+    int ki = 0;
+    while (ki < WG_NKERNELS && (kWgradKernels[ki].form != q.form || kWgradKernels[ki].dtype != d->dtype)) ++ki;
+    MF_CHECK_ARG(ki < WG_NKERNELS, "mf_conv_wgrad: no kernel of form %d for dtype %d", q.form, d->dtype);
+    const WgradKernel& k = kWgradKernels[ki];
+    if (k.lds_attr) {
+        // the dynamic-LDS attribute is per function AND per device: one flag per (kernel, device), the call's result checked
+        static bool attr[WG_NKERNELS][64] = {};
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+            mf_set_error("mf_conv_wgrad: hipGetDevice failed or device index above 63");
+            return MF_ELAUNCH;
+        }
+        if (!attr[ki][dev]) {
+            const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, q.lds_bytes);
+            if (e != hipSuccess) {
+                mf_set_error("mf_conv_wgrad: %d bytes of dynamic LDS refused on device %d: %s", q.lds_bytes, dev, hipGetErrorString(e));
+                return MF_ELAUNCH;
+            }
+            attr[ki][dev] = true;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid = q.form == WG_FORM_F32 ? dim3((unsigned)q.tiles, (unsigned)q.splitm) : dim3((unsigned)q.blocks);
+    void* args[] = {&a};
+    (void)hipLaunchKernel(k.fn, grid, dim3((unsigned)q.threads), args, (size_t)q.lds_bytes, s);
     MF_CHECK_LAUNCH("mf_conv_wgrad");
-    if (!direct) {
-        hipLaunchKernelGGL(sum_slabs_kernel, dim3(grid_for((int64_t)a.N * K)), dim3(256), 0, s, d->ws, a.splitm, a.slab, d->dw, d->lddw, a.N,
-                           (int)K, d->accumulate);
+    if (q.reduce_launch) {
+        hipLaunchKernelGGL(sum_slabs_kernel, dim3(grid_for((int64_t)a.N * p.K)), dim3(256), 0, s, d->ws, a.splitm, a.slab, d->dw, d->lddw, a.N,
+                           (int)p.K, d->accumulate);
         MF_CHECK_LAUNCH("mf_conv_wgrad(sum slabs)");
     }
     return MF_OK;
@@ -1976,10 +1932,7 @@ extern "C" int mf_groupnorm_bwd(const mf_groupnorm_bwd_desc* d, void* stream) {
             hipLaunchKernelGGL(gn_bwd2_reduce_kernel<0>, dim3((unsigned)(d->batch * d->groups)), dim3(256), 0, s, q);
         }
         hipLaunchKernelGGL(gn_bwd2_kernel<1>, grid, dim3(256), 0, s, q);
-        static const bool acc_v1 = getenv("MFHIP_GN_ACC_V1") != nullptr;       // developer A/B: one block per group over all images
-        if (d->dgamma_acc && acc_v1)
-            hipLaunchKernelGGL(gn_bwd2_reduce_acc_kernel, dim3((unsigned)d->groups), dim3(256), 0, s, q, d->dgamma_acc, d->dbeta_acc);
-        else if (d->dgamma_acc) {
+        if (d->dgamma_acc) {
             float* pg = q.part + (int64_t)d->batch * q.chunks * 2 * C;                 // [2][batch][C] per-image partials (workspace tail)
             q.a.dgamma_part = pg; q.a.dbeta_part = pg + (int64_t)d->batch * C;
             hipLaunchKernelGGL(gn_bwd2_reduce_kernel<1>, dim3((unsigned)(d->batch * d->groups)), dim3(256), 0, s, q);

@@ -81,6 +81,12 @@ class WgradDesc(C.Structure):
     ]
 
 
+class WgradPlan(C.Structure):
+    """mf_wgrad_plan: what mf_conv_wgrad would do with a descriptor (mf_conv_wgrad_plan; decided on the host, nothing is launched).
+    form: 0 fp32, 1 128-wide register-staged, 2 160-wide, 3 128-wide LDS-DMA."""
+    _fields_ = [(f, C.c_int32) for f in "form tile_w tiles splitm m_per_split reduce_launch slabs_xcd blocks threads lds_bytes".split()]
+
+
 class GroupNormBwdDesc(C.Structure):
     _fields_ = [
         ("x0", C.c_void_p), ("x1", C.c_void_p), ("c0", C.c_int32), ("c1", C.c_int32),
@@ -157,7 +163,7 @@ class SchedRow(C.Structure):
 # load() turns the table into argtypes / restype, so ctypes converts plain Python values and refuses the wrong ones before the library
 # is entered; program.py derives the recorder's signatures from it; tests/test_abi.py checks it against the header's prototypes in full.
 # A new entry is its prototype in mfhip.h and its line here.
-DESC_KINDS = {"G": GemmDesc, "P": GemmPlan, "N": GroupNormDesc, "A": AttnBwdDesc, "W": WgradDesc, "B": GroupNormBwdDesc}
+DESC_KINDS = {"G": GemmDesc, "P": GemmPlan, "N": GroupNormDesc, "A": AttnBwdDesc, "W": WgradDesc, "Q": WgradPlan, "B": GroupNormBwdDesc}
 SIGNATURES = {
     "mf_abi_version": "i:", "mf_last_error": "s:", "mf_sizeof_gemm_desc": "i:", "mf_sizeof_groupnorm_desc": "i:",
     "mf_gemm_conv": "i:Gp", "mf_gemm_conv_plan": "i:GP", "mf_sizeof_gemm_plan": "i:", "mf_gemm_num_tiles": "i:", "mf_gemm_tile_shape": "i:ipp",
@@ -202,7 +208,8 @@ SIGNATURES = {
     "mf_lpips_ws_bytes": "l:i", "mf_lpips_prepare": "i:pppiiiiiipip", "mf_relu": "i:pililp", "mf_maxpool3s2_ceil": "i:ppiiiiip",
     "mf_lpips_layer": "i:pipiliipp", "mf_lpips_finish": "i:pipp",
     # training (csrc/train.hip)
-    "mf_sizeof_wgrad_desc": "i:", "mf_conv_wgrad_ws_floats": "l:W", "mf_conv_wgrad": "i:Wp", "mf_split_pack": "i:plpliip",
+    "mf_sizeof_wgrad_desc": "i:", "mf_conv_wgrad_ws_floats": "l:W", "mf_conv_wgrad": "i:Wp", "mf_conv_wgrad_plan": "i:WQ",
+    "mf_sizeof_wgrad_plan": "i:", "mf_split_pack": "i:plpliip",
     "mf_transpose": "i:ppiiillllp", "mf_transpose_bf16": "i:ppiiillllp", "mf_colsum_ws_floats": "l:ili", "mf_colsum": "i:plpliliipp",
     "mf_sizeof_groupnorm_bwd_desc": "i:", "mf_groupnorm_bwd": "i:Bp", "mf_groupnorm_bwd_ws_floats": "l:iiii", "mf_groupnorm_bwd_streams": "i:iiii",
     "mf_layernorm_bwd": "i:pppppplifpp", "mf_layernorm_bwd_parts": "l:l", "mf_softmax_bwd": "i:pppliifp", "mf_silu_bwd": "i:ppplp",
@@ -224,7 +231,7 @@ EXPORTS = list(SIGNATURES)
 # (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
 _LAYOUTS = ((GemmDesc, "mf_sizeof_gemm_desc"), (GroupNormDesc, "mf_sizeof_groupnorm_desc"), (AttnBwdDesc, "mf_sizeof_attn_bwd_desc"),
             (WgradDesc, "mf_sizeof_wgrad_desc"), (GroupNormBwdDesc, "mf_sizeof_groupnorm_bwd_desc"), (SchedRow, "mf_sizeof_sched_row"),
-            (MetricsRow, "mf_sizeof_metrics_row"), (GemmPlan, "mf_sizeof_gemm_plan"))
+            (MetricsRow, "mf_sizeof_metrics_row"), (GemmPlan, "mf_sizeof_gemm_plan"), (WgradPlan, "mf_sizeof_wgrad_plan"))
 _CTYPES = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "s": C.c_char_p, "v": None,
            **{kind: C.POINTER(struct) for kind, struct in DESC_KINDS.items()}}
 

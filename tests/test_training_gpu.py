@@ -466,6 +466,43 @@ def test_weight_gradient_on_bf16_inputs_lds_dma_equals_register_staged():
         assert _rel(got, wt.grad) < 2e-5, (b, h, w_, c0, c1, n, k, stride, up)
 
 
+def test_every_weight_gradient_form_of_the_plan_against_float64():
+    """Each kernel form mf_conv_wgrad_plan names (0 fp32, 1 128-wide register-staged, 2 160-wide, 3 128-wide LDS-DMA), for every dtype
+    that reaches it, on the smallest shape of tests/test_wgrad_plan_cpu.py's table that takes it, against conv2d's weight gradient in
+    float64.  The form is asserted first: a change of routing cannot quietly shrink what this covers.  Bounds are the ones of the tests
+    above: 1e-5 fp32, 3e-5 f16x3, 5e-3 bf16x1 on fp32 inputs (operands rounded to 2^-9), 2e-5 MF_BF16 against float64 on the same bf16 values."""
+    from test_wgrad_plan_cpu import conv as plan_desc, planned
+    g = torch.Generator().manual_seed(63)
+    shapes = [  # (b, hw, c, n, k), [(dtype code, form, accumulate, bound)]
+        ((4, 32, 320, 320, 3), [(hip.MF_F16X3, 2, 1, 3e-5), (hip.MF_BF16X1, 2, 1, 5e-3), (hip.MF_BF16, 2, 1, 2e-5)]),
+        ((2, 16, 160, 160, 3), [(hip.MF_BF16X1, 1, 1, 5e-3), (hip.MF_BF16, 3, 1, 2e-5)]),
+        ((2, 8, 64, 64, 3), [(hip.MF_F32, 0, 0, 1e-5), (hip.MF_F32, 0, 1, 1e-5)]),
+    ]
+    for (b, hw, c, n, k), runs in shapes:
+        x, dy = torch.randn(b, hw, hw, c, generator=g), torch.randn(b * hw * hw, n, generator=g)
+        refs = {}
+
+        def ref_of(in16):          # float64 on the values the kernel is given: the fp32 tensors, or their bf16 roundings
+            if in16 not in refs:
+                xs, dys = (x.bfloat16(), dy.bfloat16()) if in16 else (x, dy)
+                wt = torch.zeros(n, c, k, k, dtype=torch.float64, requires_grad=True)
+                torch.nn.functional.conv2d(xs.double().permute(0, 3, 1, 2), wt, padding=k // 2).backward(dys.double().view(b, hw, hw, n).permute(0, 3, 1, 2))
+                refs[in16] = wt.grad
+            return refs[in16]
+
+        for code, form, acc, bound in runs:
+            p = planned(plan_desc(code, b, hw, hw, c, n, k, accumulate=acc))
+            assert p.form == form, (code, b, hw, c, n, k, p.form)
+            in16 = code == hip.MF_BF16
+            xd, dyd = (t.bfloat16().to(DEV) if in16 else t.to(DEV) for t in (x, dy))
+            dw = torch.full((n, k * k * c), 0.5, device=DEV)          # accumulate: += on 0.5; else overwritten
+            hip.conv_wgrad(xd, dyd, dw, code=code, c0=c, batch=b, h_in=hw, w_in=hw, h_out=hw, w_out=hw, kh=k, kw=k, pad_t=k // 2, pad_l=k // 2,
+                           n=n, accumulate=bool(acc))
+            err = _rel((dw - 0.5 * acc).view(n, k, k, c).permute(0, 3, 1, 2), ref_of(in16))
+            print(f"wgrad form {p.form} dtype {code} {b}x{hw}x{hw} {c}->{n} accumulate={acc} splitm={p.splitm} reduce={p.reduce_launch}: {err:.2e} (bound {bound:.0e})")
+            assert err < bound, (code, form, acc, err)
+
+
 @pytest.mark.parametrize("code_name", ["f16x3", "bf16x3"])
 def test_device_split_pack_matches_the_host_split(code_name):
     """mf_split_pack (the per-step split of the weights the optimizer just changed) is bit-identical to ops.split_pack (the split the

@@ -505,6 +505,21 @@ typedef struct mf_sched_row {
 int mf_sizeof_sched_row(void);
 int mf_sched_step_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row, int64_t n,
                       void* stream);
+/* mf_sched_step_dev with one more source of values, for samplers that add fresh noise at every step (DPM-Solver++ SDE): before the ops
+ * run, register `noise_reg` (2 <= noise_reg < MF_SCHED_MAX_REGS is checked; that it is a temporary of the row, noise_reg >= 2 + nslots,
+ * is the caller's duty — the row lives in device memory and the entry does not read it; schedulers.device_plan reports the register
+ * as plan.noise_reg) holds standard normals DRAWN IN THE KERNEL from the library's stream ("random numbers" below) — nothing is loaded
+ * for it.  latents is [samples][per_sample] with samples = n / per_sample, the rows [first_sample, first_sample + samples) of a draw of
+ * global_batch rows: element i of sample s is bit for bit what mf_philox_normal(scale = 1) writes for the same (seed, offset,
+ * first_sample, global_batch), i.e. lane i % 4 of block offset + (first_sample + s) * (per_sample / 4) + i / 4 with the Box-Muller
+ * pairing stated there.  One thread is one block: per_sample % 4 == 0 is required (MF_EINVAL otherwise).  seed / offset / rng_state
+ * follow mf_philox_normal: a non-null rng_state (device uint64 {seed, offset}) overrides the host pair, and the kernel never writes
+ * it; the caller follows the launch with mf_philox_advance(rng_state, mf_philox_normal_blocks(global_batch, per_sample)) on the same
+ * stream, which therefore runs after the kernel has read the state. */
+/* (appended; MF_ABI_VERSION stays 23: no existing entry or struct changed) */
+int mf_sched_step_noise_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row,
+                            int64_t n, int32_t noise_reg, int64_t per_sample, int64_t first_sample, int64_t global_batch, int64_t seed,
+                            int64_t offset, const uint64_t* rng_state, void* stream);
 /* training loss (examples/brushnet/train_brushnet_mirror.py:1433-1449): per_sample[r] = mean_i (pred[r][i] -
  * target[r][i])^2 * (weights ? weights[r] : 1) and loss[0] = mean_r per_sample[r]; fp32 in, double accumulation */
 int mf_mse_loss(const float* pred, const float* target, const float* weights, float* per_sample, float* loss,
@@ -914,7 +929,10 @@ int mf_program_run(mf_program* p, void* stream);
  *   "device": the update is inside (mf_sched_step_dev): io buffers "sched_row" (the step's row of the named constant
  *             "table.sched_row", copied in like coef4) and "sched_state" (the scheduler's history, nslots * latents; it persists
  *             between runs, so bind it once and leave it alone).  mf_denoise_step_fused(step, NULL, NULL, NULL, NULL, stream) then
- *             runs a whole PNDM / UniPC step.
+ *             runs a whole PNDM / UniPC / DPM-Solver++ step.  Under the SDE type of DPM-Solver++ the update is mf_sched_step_noise_dev
+ *             followed by mf_philox_advance: the generator's device state {seed, offset} is one more io buffer, "philox_state"
+ *             (16 bytes; bind it once and leave it alone, or write a pair into it to restart the noise), and the program's meta
+ *             carries "philox": {per_sample, first_sample, global_batch, blocks_per_step, noise_reg}.
  *   "host":   it ends with the guided noise prediction e = eu + g (ec - eu) in the io buffer "eps" (pipeline_brushnet.py:1310-1312)
  *             and the host's scheduler steps from it. */
 int mf_denoise_step_fused(mf_program* step, void* latents, const void* coef4, const void* temb_unet, const void* temb_brushnet, void* stream);
@@ -955,7 +973,7 @@ int mf_decode_image(mf_program* decoder, const void* latents, void* image_u8, vo
 int mf_memcpy2d(void* dst, int64_t dpitch, const void* src, int64_t spitch, int64_t width_bytes, int64_t height, void* stream);
 int mf_memset(void* dst, int32_t value, int64_t bytes, void* stream);
 
-/* ---- random numbers: one counter-based stream, the same from Python and from C (csrc/rng.hip; appended, ABI stays 23) -----------
+/* ---- random numbers: one counter-based stream, the same from Python and from C (csrc/rng.hip, csrc/philox.h; appended, ABI stays 23) -----------
  * GENERATOR  Philox4x32-10 with the standard constants: multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85,
  *            10 rounds.  Key = (seed low 32 bits, seed high 32 bits) of a 64-bit seed; counter = (block low 32, block high 32, 0, 0)
  *            of a 64-bit block index.  A generator is the pair (seed, offset), offset counted in blocks; one block yields four uint32

@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "mf_common.h"
+#include "philox.h"        // mf_sched_step_noise_dev draws the library's stream into a register
 
 static thread_local char g_err[512] = "";
 void mf_set_error(const char* fmt, ...) {
@@ -278,7 +279,17 @@ __global__ void axpby_kernel(AxpbyArgs a, float* y, int64_t n) {
 // it is wave-uniform; registers are selected by unrolled compares against compile-time indices (no private array is indexed at run
 // time: 0 scratch).  The arithmetic is that of cfg_combine_kernel (fmaf(g, ec - eu, eu)) and axpby_kernel (c0 * x0, then
 // fmaf(c_k, x_k, acc)), written out so that the contraction cannot differ.
+// mf_sched_step_noise_dev is the same body with NOISE: thread i holds elements [4i, 4i + 4), which are exactly Philox block `base + i` of
+// the draw (per_sample % 4 == 0, so the samples' streams are contiguous in blocks); its four normals go to register `reg` before the ops
+// run, through the same literal-index compare chain.  The generator's pair is read through scalar loads and never written.
 constexpr int kSchedRegs = MF_SCHED_MAX_REGS;
+
+struct SchedNoise {
+    int reg;                         // the register the normals fill (a temporary: 2 + nslots .. MF_SCHED_MAX_REGS - 1)
+    uint64_t first_block;            // first_sample * (per_sample / 4): the launch's first block past the generator's offset
+    uint64_t seed, offset;
+    const uint64_t* state;           // device {seed, offset}: overrides the two host values (what a captured graph reads)
+};
 
 __device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
@@ -286,11 +297,17 @@ __device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__bu
 // The register file is a local array of this one function and every index into it is a literal (fold expressions over Rs): SROA
 // keeps it in VGPRs.  (A helper taking the array by reference, or a loop over it, lets the optimizer turn the compare chain into a
 // load at a run-time offset first, and the array then lives in scratch.)
-template <int... Rs>
+template <bool NOISE, int... Rs>
 __device__ __forceinline__ void sched_step_body(const f32x4_t* __restrict__ eu, const f32x4_t* __restrict__ ec, float g,
                                                 f32x4_t* __restrict__ lat, f32x4_t* __restrict__ state,
-                                                const mf_sched_row* __restrict__ row, int64_t n4, std::integer_sequence<int, Rs...>) {
+                                                const mf_sched_row* __restrict__ row, int64_t n4, const SchedNoise& nz,
+                                                std::integer_sequence<int, Rs...>) {
     static_assert(sizeof...(Rs) == kSchedRegs, "one index per register");
+    uint64_t seed = 0, base = 0;
+    if constexpr (NOISE) {
+        seed = nz.state ? nz.state[0] : nz.seed;
+        base = (nz.state ? nz.state[1] : nz.offset) + nz.first_block;
+    }
     // (counts clamped to the struct: a malformed row never reads past it)
     const int nops = min(uniform_i(row->nops), MF_SCHED_MAX_OPS), nslots = uniform_i(row->nslots);
     const unsigned ldm = (unsigned)uniform_i((int)row->load), stm = (unsigned)uniform_i((int)row->store);
@@ -302,6 +319,15 @@ __device__ __forceinline__ void sched_step_body(const f32x4_t* __restrict__ eu, 
         for (int j = 0; j < 4; ++j) R[0][j] = __builtin_fmaf(g, c[j] - u[j], u[j]);
         R[1] = (ldm & 2u) ? lat[i] : zero;
         ((Rs >= 2 ? (R[Rs] = (Rs - 2 < nslots && ((ldm >> Rs) & 1u)) ? state[(int64_t)(Rs - 2) * n4 + i] : zero) : R[0]), ...);
+        if constexpr (NOISE) {
+            uint32_t x[4];
+            philox_block(seed, base + (uint64_t)i, x);
+            float z0, z1, z2, z3;
+            box_muller(x[0], x[1], 1.0f, z0, z1);
+            box_muller(x[2], x[3], 1.0f, z2, z3);
+            const f32x4_t z = {z0, z1, z2, z3};
+            ((R[Rs] = (Rs >= 2 && nz.reg == Rs) ? z : R[Rs]), ...);
+        }
         for (int o = 0; o < nops; ++o) {
             const mf_sched_op& op = row->ops[o];
             const int nt = min(uniform_i(op.nterms), MF_SCHED_MAX_TERMS), dst = uniform_i(op.dst), s0 = uniform_i(op.src[0]);
@@ -330,7 +356,13 @@ __device__ __forceinline__ void sched_step_body(const f32x4_t* __restrict__ eu, 
 __global__ __launch_bounds__(256) void sched_step_kernel(const f32x4_t* __restrict__ eu, const f32x4_t* __restrict__ ec, float g,
                                                          f32x4_t* __restrict__ lat, f32x4_t* __restrict__ state,
                                                          const mf_sched_row* __restrict__ row, int64_t n4) {
-    sched_step_body(eu, ec, g, lat, state, row, n4, std::make_integer_sequence<int, kSchedRegs>{});
+    sched_step_body<false>(eu, ec, g, lat, state, row, n4, SchedNoise{}, std::make_integer_sequence<int, kSchedRegs>{});
+}
+
+__global__ __launch_bounds__(256) void sched_step_noise_kernel(const f32x4_t* __restrict__ eu, const f32x4_t* __restrict__ ec, float g,
+                                                               f32x4_t* __restrict__ lat, f32x4_t* __restrict__ state,
+                                                               const mf_sched_row* __restrict__ row, int64_t n4, const SchedNoise nz) {
+    sched_step_body<true>(eu, ec, g, lat, state, row, n4, nz, std::make_integer_sequence<int, kSchedRegs>{});
 }
 
 // Training loss (train_brushnet_mirror.py:1433-1449): per-sample mean((pred - target)^2) * weight, then the
@@ -568,24 +600,59 @@ extern "C" int mf_axpby_n(const float* const* xs, const float* coefs, int32_t ni
     return MF_OK;
 }
 
+// the grid of the two scheduler-step kernels is sized to the device (a few blocks per CU, grid-stride loop), queried once per device
+static int sched_step_grid(int64_t n4, const char* name, int* grid) {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+        mf_set_error("%s: no current device", name);
+        return MF_ELAUNCH;
+    }
+    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus[dev] = 0;
+    const unsigned cap = (unsigned)(cus[dev] > 0 ? 4 * cus[dev] : 1024);
+    *grid = grid_for(n4, 256, (int)cap);
+    return MF_OK;
+}
+
 extern "C" int mf_sched_step_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row,
                                  int64_t n, void* stream) {
     MF_CHECK_ARG(eps_u && eps_c && latents && row && n > 0 && n % 4 == 0, "mf_sched_step_dev: bad arguments (n %% 4 == 0 needed)");
     MF_CHECK_ARG(mf_aligned16(eps_u) && mf_aligned16(eps_c) && mf_aligned16(latents) && (!state || mf_aligned16(state)),
                  "mf_sched_step_dev: tensors must be 16-byte aligned");
-    // the grid is sized to the device (a few blocks per CU, grid-stride loop), queried once per device
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        mf_set_error("mf_sched_step_dev: no current device");
-        return MF_ELAUNCH;
-    }
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus[dev] = 0;
     const int64_t n4 = n / 4;
-    const unsigned cap = (unsigned)(cus[dev] > 0 ? 4 * cus[dev] : 1024);
-    hipLaunchKernelGGL(sched_step_kernel, dim3(grid_for(n4, 256, (int)cap)), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
+    int grid = 0;
+    if (int rc = sched_step_grid(n4, "mf_sched_step_dev", &grid)) return rc;
+    hipLaunchKernelGGL(sched_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
                        (const f32x4_t*)eps_c, g, (f32x4_t*)latents, (f32x4_t*)state, row, n4);
     MF_CHECK_LAUNCH("mf_sched_step_dev");
+    return MF_OK;
+}
+
+extern "C" int mf_sched_step_noise_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row,
+                                       int64_t n, int32_t noise_reg, int64_t per_sample, int64_t first_sample, int64_t global_batch,
+                                       int64_t seed, int64_t offset, const uint64_t* rng_state, void* stream) {
+    MF_CHECK_ARG(eps_u && eps_c && latents && row && n > 0 && n % 4 == 0, "mf_sched_step_noise_dev: bad arguments (n %% 4 == 0 needed)");
+    MF_CHECK_ARG(mf_aligned16(eps_u) && mf_aligned16(eps_c) && mf_aligned16(latents) && (!state || mf_aligned16(state)),
+                 "mf_sched_step_noise_dev: tensors must be 16-byte aligned");
+    MF_CHECK_ARG(noise_reg >= 2 && noise_reg < MF_SCHED_MAX_REGS, "mf_sched_step_noise_dev: noise_reg %d outside [2, %d)", noise_reg,
+                 MF_SCHED_MAX_REGS);
+    MF_CHECK_ARG(per_sample > 0 && per_sample % 4 == 0 && n % per_sample == 0,
+                 "mf_sched_step_noise_dev: per_sample %lld must be a positive multiple of 4 that divides n = %lld (one thread is one Philox block)",
+                 (long long)per_sample, (long long)n);
+    MF_CHECK_ARG(first_sample >= 0 && global_batch >= first_sample + n / per_sample,
+                 "mf_sched_step_noise_dev: global_batch %lld < first_sample %lld + samples %lld", (long long)global_batch,
+                 (long long)first_sample, (long long)(n / per_sample));
+    MF_CHECK_ARG(((uintptr_t)rng_state & 7) == 0, "mf_sched_step_noise_dev: the generator state must be 8-byte aligned");
+    const int64_t n4 = n / 4;
+    int grid = 0;
+    if (int rc = sched_step_grid(n4, "mf_sched_step_noise_dev", &grid)) return rc;
+    SchedNoise nz;
+    nz.reg = noise_reg;
+    nz.first_block = (uint64_t)first_sample * (uint64_t)(per_sample / 4);
+    nz.seed = (uint64_t)seed; nz.offset = (uint64_t)offset; nz.state = rng_state;
+    hipLaunchKernelGGL(sched_step_noise_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
+                       (const f32x4_t*)eps_c, g, (f32x4_t*)latents, (f32x4_t*)state, row, n4, nz);
+    MF_CHECK_LAUNCH("mf_sched_step_noise_dev");
     return MF_OK;
 }
 

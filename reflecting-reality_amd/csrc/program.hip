@@ -58,7 +58,14 @@ const struct { int fn; const char* name; const char* sig; } kCallFns[G_END - F_C
     {G_MINMAX, "mf_minmax", "pplpp"}, {G_IMAGE_NORMALIZE, "mf_image_normalize", "pplp"}, {G_MASK_KEEP, "mf_mask_keep", "ppiil"},
     {G_POSTPROCESS, "mf_postprocess", "pppiili"}, {G_U8_TO_PLANES, "mf_u8_to_planes", "ppiiil"}, {G_AXPBY_N, "mf_axpby_n", "ppppppffffffipl"},
 };
-inline const char* sig_of(int fn) { return fn < F_COUNT ? kFns[fn].sig : kCallFns[fn - F_COUNT].sig; }
+// The update of a stochastic sampler (DPM-Solver++ SDE): the scheduler step that draws its noise in the kernel, and the advance of the
+// generator's device state that follows it ("philox_state", an io buffer the host binds once).  program._REPLAYABLE_NOISE holds the same
+// table; a table of its own, as the two above are pinned as they stand; ids go on from G_END.
+enum NoiseFn { H_SCHED_STEP_NOISE_DEV = G_END, H_PHILOX_ADVANCE, H_END };
+const struct { int fn; const char* name; const char* sig; } kNoiseFns[H_END - G_END] = {
+    {H_SCHED_STEP_NOISE_DEV, "mf_sched_step_noise_dev", "ppfppplilllllp"}, {H_PHILOX_ADVANCE, "mf_philox_advance", "pl"},
+};
+inline const char* sig_of(int fn) { return fn < F_COUNT ? kFns[fn].sig : fn < G_END ? kCallFns[fn - F_COUNT].sig : kNoiseFns[fn - G_END].sig; }
 
 struct Reader {
     const uint8_t* p; const uint8_t* end; bool ok = true;
@@ -154,6 +161,8 @@ extern "C" int mf_program_load(const void* blob, int64_t bytes, mf_program** out
             if (call.name == kFns[f].name) call.fn = f;
         for (const auto& g : kCallFns)
             if (call.name == g.name) call.fn = g.fn;
+        for (const auto& h : kNoiseFns)
+            if (call.name == h.name) call.fn = h.fn;
         if (call.stream >= nstreams) {
             mf_set_error("mf_program_load: call %u (%s) on stream %u of %u", c, call.name.c_str(), call.stream, nstreams);
             delete p;
@@ -346,6 +355,10 @@ int run_call(const mf_program* prog, const Call& c, void* s) {
         const float cs[6] = {F(6), F(7), F(8), F(9), F(10), F(11)};
         return mf_axpby_n(xs, cs, I(12), (float*)P(13), L(14), s);      // (the entry copies both arrays into the launch's arguments)
     }
+    case H_SCHED_STEP_NOISE_DEV:
+        return mf_sched_step_noise_dev(FP(0), FP(1), F(2), (float*)P(3), (float*)P(4), (const mf_sched_row*)P(5), L(6), I(7), L(8), L(9), L(10), L(11),
+                                       L(12), (const uint64_t*)P(13), s);
+    case H_PHILOX_ADVANCE: return mf_philox_advance((uint64_t*)P(0), L(1), s);
     default: break;
     }
 #undef P

@@ -226,6 +226,8 @@ SIGNATURES = {
     "mf_philox_normal_blocks": "l:ll", "mf_philox_int_blocks": "l:l", "mf_philox_bits_host": "i:plll", "mf_philox_bits": "i:plllpp",
     "mf_philox_normal": "i:pllfllllpp", "mf_philox_randint": "i:pllllllpp", "mf_philox_advance": "i:plp",
     "mf_train_batch_draw": "i:pipplllllllpp",
+    # the multistep update with per-step noise drawn in the kernel (csrc/elementwise.hip; DPM-Solver++ SDE)
+    "mf_sched_step_noise_dev": "i:ppfppplilllllpp",
 }
 EXPORTS = list(SIGNATURES)
 # (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
@@ -1272,6 +1274,28 @@ def sched_step_dev(eps_u: torch.Tensor, eps_c: torch.Tensor, g: float, latents: 
         if t is not None and (not t.is_contiguous() or (t.dtype != torch.float32 and t is not row)):
             raise MfhipError("sched_step_dev: contiguous fp32 tensors needed")
     _launch("mf_sched_step_dev", eps_u, eps_c, g, latents, state, row, n)
+    return latents
+
+
+def sched_step_noise_dev(eps_u: torch.Tensor, eps_c: torch.Tensor, g: float, latents: torch.Tensor, state: Optional[torch.Tensor],
+                         row: torch.Tensor, noise_reg: int, seed: int = 0, offset: int = 0, first_sample: int = 0,
+                         global_batch: Optional[int] = None, rng_state: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sched_step_dev for a row that reads a step's noise (mf_sched_step_noise_dev): register `noise_reg` (plan.noise_reg of
+    schedulers.device_plan) holds standard normals drawn in the kernel, bit for bit philox_normal(latents.shape, seed, offset, ...,
+    first_sample, global_batch); `rng_state` (PhiloxGenerator.device_state()) overrides (seed, offset) and is not written: follow the
+    launch with philox_advance(rng_state, philox_normal_blocks(global_batch, per_sample))."""
+    _req_cuda(eps_u, eps_c, latents, state, row, rng_state)
+    n = latents.numel()
+    if latents.dim() < 1 or eps_u.numel() != n or eps_c.numel() != n or (state is not None and state.numel() % n) \
+            or row.numel() * row.element_size() < C.sizeof(SchedRow):
+        raise MfhipError("sched_step_noise_dev: mismatched sizes")
+    for t in (eps_u, eps_c, latents, state, row):
+        if t is not None and (not t.is_contiguous() or (t.dtype != torch.float32 and t is not row)):
+            raise MfhipError("sched_step_noise_dev: contiguous fp32 tensors needed")
+    b = latents.shape[0]
+    gb = b + first_sample if global_batch is None else int(global_batch)
+    _launch("mf_sched_step_noise_dev", eps_u, eps_c, g, latents, state, row, n, int(noise_reg), n // b, int(first_sample), gb,
+            _s64(seed), _s64(offset), _philox_state(rng_state))
     return latents
 
 

@@ -30,7 +30,7 @@ import torch
 from . import hip
 from .models import AutoencoderKL, BrushNetModel, UNet2DConditionModel
 from .rng import PhiloxGenerator, is_philox, randn_tensor
-from .schedulers import DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler, device_plan
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, UniPCMultistepScheduler, device_plan
 
 try:
     import PIL.Image
@@ -149,28 +149,62 @@ class _FusedDDIM:
 
 
 class _DevicePlan:
-    """PNDM / UniPC inside the captured step: mf_sched_step_dev runs the step's row of schedulers.device_plan (a trace of their own
-    step()) on a state buffer that keeps their history; the scheduler gets its end state from it after the loop."""
+    """PNDM / UniPC / DPM-Solver++ inside the captured step: mf_sched_step_dev runs the step's row of schedulers.device_plan (a trace of
+    their own step()) on a state buffer that keeps their history; the scheduler gets its end state from it after the loop.  A plan that
+    reads a step's noise (DPM-Solver++ SDE) takes a rng.PhiloxGenerator: mf_sched_step_noise_dev draws the noise in the kernel from the
+    generator's device state and mf_philox_advance moves that state, both inside the graph; the host pair follows per replayed step."""
 
-    def __init__(self, pipe, g, nsteps):
+    def __init__(self, pipe, g, nsteps, generator=None):
         self.sched, self.g = pipe.scheduler, float(g)
         self.plan = device_plan(self.sched, steps=nsteps)
         name = type(self.sched).__name__
         self.key = (name, "device", self.plan.nslots)
         self.result = f"latents ({name} update inside: mf_sched_step_dev; history in sched_state)"
+        self.gen, self.meta = None, {}
+        if self.plan.noise_reg >= 0:
+            if not isinstance(generator, PhiloxGenerator):
+                raise hip.MfhipError("a device plan that draws noise needs a rng.PhiloxGenerator")
+            self.gen = generator
+            generator.device = generator.device or torch.device(pipe.device)
+            # taken HERE, outside the capture; its address is part of the graph's key (another generator's state: another graph)
+            self.rng_state = generator.device_state()
+            self.key += (self.plan.noise_reg, self.rng_state.data_ptr())
+            self.result = f"latents ({name} update inside: mf_sched_step_noise_dev + mf_philox_advance; history in sched_state)"
 
     def attach(self, st, lat, ts):
         if "state" not in st:                     # the step's mf_sched_row, and the scheduler's history (persists between steps)
             st["row_cur"] = torch.empty(self.plan.rows.shape[1], dtype=torch.int32, device=lat.device)
             st["state"] = torch.empty((max(self.plan.nslots, 1),) + tuple(lat.shape), dtype=torch.float32, device=lat.device)
         self.row_cur, self.state, self.rows = st["row_cur"], st["state"], self.plan.rows.to(lat.device)
+        if self.gen is not None:
+            self.per = lat[0].numel()
+            self.blocks = hip.philox_normal_blocks(lat.shape[0], self.per)           # what one step's draw consumes
+            self.meta = dict(philox=dict(per_sample=self.per, first_sample=0, global_batch=int(lat.shape[0]), blocks_per_step=self.blocks,
+                                         noise_reg=self.plan.noise_reg))
+            self.rng_state = self.gen.device_state()       # (level with the host pair again: prepare_latents drew since __init__)
 
     def load(self, i): self.row_cur.copy_(self.rows[i])
-    def launch(self, eu, ec, lat): hip.sched_step_dev(eu, ec, self.g, lat, self.state, self.row_cur)
-    def after_replay(self, t, lat): pass
+
+    def launch(self, eu, ec, lat):
+        if self.gen is None:
+            hip.sched_step_dev(eu, ec, self.g, lat, self.state, self.row_cur)
+        else:                                     # (same stream: the advance runs after the kernel has read the state)
+            hip.sched_step_noise_dev(eu, ec, self.g, lat, self.state, self.row_cur, self.plan.noise_reg, rng_state=self.rng_state)
+            hip.philox_advance(self.rng_state, self.blocks)
+
+    def after_replay(self, t, lat):
+        if self.gen is not None:
+            self.gen.note_advanced(self.blocks, on_device=True)
+
     def finish(self): self.plan.finish(self.sched, self.state)    # the counters and history the host's step() would have left
+
     # (the host copies the step's row in like coef4, and the history slots stay in "sched_state" between runs)
-    def export(self): return dict(sched_row=self.row_cur, sched_state=self.state), {"table.sched_row": self.rows.contiguous()}
+    # (the generator's device state of a noise-drawing plan is one more io buffer, bound once like sched_state)
+    def export(self):
+        io = dict(sched_row=self.row_cur, sched_state=self.state)
+        if self.gen is not None:
+            io["philox_state"] = self.rng_state
+        return io, {"table.sched_row": self.rows.contiguous()}
 
 
 class _HostStep:
@@ -259,7 +293,7 @@ class StableDiffusionBrushNetPipeline:
         self.normal_embedder = None      # 'ip_adapter' normals mode: a frontend.NormalEmbedder turns `normals=` [B, 1, 3] into the ip token
 
     # ---- loading / saving (pipelines/pipeline_utils.py:148-296 save_pretrained, :465-919 from_pretrained) ---------
-    _scheduler_classes = ("DDIMScheduler", "PNDMScheduler", "UniPCMultistepScheduler")
+    _scheduler_classes = ("DDIMScheduler", "PNDMScheduler", "UniPCMultistepScheduler", "DPMSolverMultistepScheduler")
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, torch_dtype=None, device="cuda", **kwargs):
@@ -698,13 +732,17 @@ class StableDiffusionBrushNetPipeline:
         fused_ddim = do_cfg and isinstance(self.scheduler, DDIMScheduler) and eta == 0.0 and rescale == 0.0
         use_graph = (self.use_hip_graph and do_cfg and callback is None and (fused_ddim or eta == 0.0) and rescale == 0.0
                      and all(k == 1.0 for k in keep) and len(ts) > 2 and not guess_mode)
-        # THE place that decides how a step ends.  PNDM / UniPC update on the device (one plan row per step) unless a callback may read
-        # the scheduler between steps, or an eps-form step program is being exported; the eager loop always steps them on the host
+        # THE place that decides how a step ends.  PNDM / UniPC / DPM-Solver++ update on the device (one plan row per step) unless a
+        # callback may read the scheduler between steps, or an eps-form step program is being exported; the eager loop always steps them
+        # on the host.  The SDE type of DPM-Solver++ draws noise at every step: on the device only from ONE rng.PhiloxGenerator (the
+        # library's stream, which the kernel can draw); a torch.Generator, none, or a list of generators steps on the host.
+        sde = isinstance(self.scheduler, DPMSolverMultistepScheduler) and self.scheduler.config["algorithm_type"] == "sde-dpmsolver++"
         if fused_ddim:
             update = _FusedDDIM(self, guidance_scale)
         elif (use_graph and callback_on_step_end is None and not (_export is not None and _export["scheduler"] == "host")
-              and isinstance(self.scheduler, (PNDMScheduler, UniPCMultistepScheduler))):
-            update = _DevicePlan(self, guidance_scale, len(ts))
+              and isinstance(self.scheduler, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler))
+              and (not sde or isinstance(generator, PhiloxGenerator))):
+            update = _DevicePlan(self, guidance_scale, len(ts), generator if sde else None)
         else:
             update = _HostStep(self, guidance_scale, rescale, eta, generator)
 
@@ -971,7 +1009,7 @@ class StableDiffusionBrushNetPipeline:
         meta = dict(entry="mf_denoise_step_fused", reference="pipelines/brushnet/pipeline_brushnet.py:1250-1332", precision=self.unet.prec.name,
                     result=update.result, latents=list(lat.shape), steps=nsteps, recorded_step=step, guidance_scale=float(guidance_scale),
                     conditioning_scale=cond_scale if isinstance(cond_scale, (int, float)) else list(cond_scale),
-                    temb_unet=list(temb_u.shape), temb_brushnet=list(temb_b.shape), brushnet_once=bool(once))
+                    temb_unet=list(temb_u.shape), temb_brushnet=list(temb_b.shape), brushnet_once=bool(once), **getattr(update, "meta", {}))
         export["info"] = rec.save(export["path"], meta=json.dumps(meta))
         export["info"]["meta"] = meta
         return graph
@@ -982,13 +1020,20 @@ class StableDiffusionBrushNetPipeline:
         constants of the file), the guidance and conditioning scales, and the schedule (its tables travel as named constants).
         `scheduler` (PNDM, UniPC): "host" ends the step with the guided noise prediction in the io buffer "eps" for the host's own
         scheduler; "device" records the update too (mf_sched_step_dev: io buffers "sched_row" / "sched_state", table "table.sched_row"),
-        so that mf_denoise_step_fused alone runs a whole step.  DDIM's update is inside either way."""
+        so that mf_denoise_step_fused alone runs a whole step.  DDIM's update is inside either way.  DPM-Solver++ exports like UniPC; its SDE
+        type needs generator=rng.PhiloxGenerator(seed) for "device" (mf_sched_step_noise_dev + mf_philox_advance on the io buffer
+        "philox_state", the generator's device pair; meta["philox"] holds per_sample, global_batch and the blocks a step consumes)."""
         if self.device.type != "cuda":
             raise hip.MfhipError("export_denoise_step needs the device: a program is a recording of real launches")
         if scheduler not in ("host", "device"):
             raise ValueError(f"export_denoise_step: scheduler must be 'host' or 'device', not {scheduler!r}")
-        if scheduler == "device" and not isinstance(self.scheduler, (DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler)):
+        if scheduler == "device" and not isinstance(self.scheduler, (DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler,
+                                                                     DPMSolverMultistepScheduler)):
             raise NotImplementedError(f"{type(self.scheduler).__name__} has no device update")
+        if (scheduler == "device" and getattr(self.scheduler, "config", {}).get("algorithm_type") == "sde-dpmsolver++"
+                and not isinstance(call_kwargs.get("generator"), PhiloxGenerator)):
+            raise NotImplementedError("a step program of the DPM-Solver++ SDE update draws its noise in the kernel: pass "
+                                      "generator=rng.PhiloxGenerator(seed), or export with scheduler='host'")
         from . import program
         program.refuse_ip_processors(self.unet)      # before anything is captured (the recorder would refuse in the middle of a two-stream capture)
         request = dict(path=path, scheduler=scheduler, info=None)       # travels with the call; _denoise_graph leaves the result in it

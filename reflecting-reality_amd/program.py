@@ -51,7 +51,12 @@ SIGNATURES_CALL = {name: hip.SIGNATURES[name][2:-1] for name in _REPLAYABLE_CALL
 # them when the call is made and writes them out flat — six pointers, six coefficients (unused: null / 0), then nin, y, n
 _AXPBY_MAX = 6
 SIGNATURES_CALL["mf_axpby_n"] = "p" * _AXPBY_MAX + "f" * _AXPBY_MAX + "ipl"
-_ALL_SIGNATURES = {**SIGNATURES, **SIGNATURES_CALL}
+# The update of a stochastic sampler inside a denoise step (DPM-Solver++ SDE, pipeline._DevicePlan): the scheduler step that draws its noise
+# in the kernel and the advance of the generator's device state, the io buffer "philox_state".  csrc/program.hip's kNoiseFns; a third
+# table, as the two above are pinned as they stand.
+_REPLAYABLE_NOISE = ("mf_sched_step_noise_dev", "mf_philox_advance")
+SIGNATURES_NOISE = {name: hip.SIGNATURES[name][2:-1] for name in _REPLAYABLE_NOISE}
+_ALL_SIGNATURES = {**SIGNATURES, **SIGNATURES_CALL, **SIGNATURES_NOISE}
 # queries / developer switches: forwarded, never recorded
 _PASS_THROUGH = ("mf_last_error", "mf_abi_version", "mf_gemm_num_tiles", "mf_gemm_tile_shape", "mf_gemm_tile_table_version",
                  "mf_groupnorm_ws_floats", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc", "mf_sizeof_sched_row", "mf_minmax_ws_floats",

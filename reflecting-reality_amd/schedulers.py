@@ -5,7 +5,7 @@ add_noise :473-497) and scheduling_pndm.py (set_timesteps :168-226, step_prk :26
 _get_prev_sample :407-448).  The scalar coefficients are computed on the host exactly like the reference
 does (fp32 0-dim tensor arithmetic on the alphas_cumprod table); the per-element update is one HIP kernel
 (mf_cfg_ddim_step / mf_axpby_n).  Latents stay fp32 whatever the model precision.  device_plan (end of the file) turns a PNDM /
-UniPC schedule into rows for mf_sched_step_dev, the whole update of a step in one launch with device-resident coefficients.
+UniPC / DPM-Solver++ schedule into rows for mf_sched_step_dev, the whole update of a step in one launch with device-resident coefficients.
 """
 from __future__ import annotations
 
@@ -507,6 +507,222 @@ class UniPCMultistepScheduler(_SchedulerBase):
         raise NotImplementedError("UniPC.add_noise is only used by the training script (SURVEY.md §8 f-2)")
 
 
+class DPMSolverMultistepScheduler(_SchedulerBase):
+    """schedulers/scheduling_dpmsolver_multistep.py: DPM-Solver++ (2M and its orders 1 / 3, midpoint / heun, Karras sigmas) and its SDE
+    variant.  The data prediction (convert_model_output :489-555) and every update (:588-863) are linear in {sample, converted model
+    outputs, noise}: the host evaluates the scalar coefficients like the reference (fp32 0-dim tensor arithmetic on the sigma table),
+    folds the differences D1 / D2 into them, and each update is ONE mf_axpby_n launch.  scale_model_input is the identity and
+    init_noise_sigma is 1, so the step body before the update is that of DDIM / PNDM / UniPC."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
+                     sample_max_value=1.0, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
+                     euler_at_final=False, use_karras_sigmas=False, use_lu_lambdas=False, final_sigmas_type="zero",
+                     lambda_min_clipped=-float("inf"), variance_type=None, timestep_spacing="linspace", steps_offset=0,
+                     rescale_betas_zero_snr=False)
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        c = self.config
+        for key in ("thresholding", "use_lu_lambdas", "variance_type", "rescale_betas_zero_snr"):
+            if c[key]:
+                raise NotImplementedError(f"{key} is outside the MirrorFusion path")
+        if c["algorithm_type"] not in ("dpmsolver++", "sde-dpmsolver++"):
+            raise NotImplementedError(f"algorithm_type {c['algorithm_type']} is not built: 'dpmsolver++' and 'sde-dpmsolver++' are")
+        if c["solver_type"] not in ("midpoint", "heun"):
+            raise NotImplementedError(f"{c['solver_type']} does is not implemented for {self.__class__}")
+        if c["prediction_type"] not in ("epsilon", "v_prediction", "sample"):
+            raise ValueError(f"prediction_type given as {c['prediction_type']} must be one of `epsilon`, `sample`, or `v_prediction` "
+                             "for the DPMSolverMultistepScheduler.")
+        if c["final_sigmas_type"] not in ("zero", "sigma_min"):
+            raise ValueError(f"`final_sigmas_type` must be one of 'zero', or 'sigma_min', but got {c['final_sigmas_type']}")
+        if not 1 <= c["solver_order"] <= 3 or (c["solver_order"] == 3 and c["algorithm_type"] != "dpmsolver++"):
+            raise NotImplementedError("solver_order is 1, 2 or 3, and 3 for algorithm_type 'dpmsolver++' only (the reference has no "
+                                      "third-order SDE update)")
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self.sigmas = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
+        self.timesteps = torch.from_numpy(np.linspace(0, c["num_train_timesteps"] - 1, c["num_train_timesteps"], dtype=np.float32)[::-1].copy())
+        self.model_outputs = [None] * c["solver_order"]
+        self.lower_order_nums = 0
+        self._step_index = None
+        self._begin_index = None
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    @property
+    def begin_index(self):
+        return self._begin_index
+
+    def set_begin_index(self, begin_index: int = 0):
+        self._begin_index = begin_index
+
+    @staticmethod
+    def _sigma_to_t(sigma, log_sigmas):
+        """:421-442 (Euler's): the fractional training timestep whose log sigma interpolates to log(sigma)."""
+        log_sigma = np.log(np.maximum(sigma, 1e-10))
+        dists = log_sigma - log_sigmas[:, np.newaxis]
+        low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+        high_idx = low_idx + 1
+        low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+        w = np.clip((low - log_sigma) / (low - high), 0, 1)
+        return ((1 - w) * low_idx + w * high_idx).reshape(sigma.shape)
+
+    def set_timesteps(self, num_inference_steps: int = None, device=None):
+        c = self.config
+        nt = c["num_train_timesteps"]
+        clipped_idx = torch.searchsorted(torch.flip(self.lambda_t, [0]), c["lambda_min_clipped"])
+        last = int((nt - clipped_idx).item())
+        if c["timestep_spacing"] == "linspace":
+            ts = np.linspace(0, last - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif c["timestep_spacing"] == "leading":
+            ts = (np.arange(0, num_inference_steps + 1) * (last // (num_inference_steps + 1))).round()[::-1][:-1].copy().astype(np.int64)
+            ts += c["steps_offset"]
+        elif c["timestep_spacing"] == "trailing":
+            ts = np.arange(last, 0, -nt / num_inference_steps).round().copy().astype(np.int64)
+            ts -= 1
+        else:
+            raise ValueError(f"{c['timestep_spacing']} is not supported. Please make sure to choose one of 'linspace', 'leading' or 'trailing'.")
+        sigmas = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        if c["use_karras_sigmas"]:                                   # Karras et al. (2022), rho = 7 (:451-474)
+            log_sigmas = np.log(sigmas)
+            sigma_min, sigma_max = float(sigmas[0]), float(sigmas[-1])
+            ramp = np.linspace(0, 1, num_inference_steps)
+            min_inv_rho, max_inv_rho = sigma_min ** (1 / 7.0), sigma_max ** (1 / 7.0)
+            sigmas = (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** 7.0
+            ts = np.array([self._sigma_to_t(s, log_sigmas) for s in sigmas]).round()
+        else:
+            sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
+        sigma_last = float(((1 - self.alphas_cumprod[0]) / self.alphas_cumprod[0]) ** 0.5) if c["final_sigmas_type"] == "sigma_min" else 0.0
+        new_sigmas = torch.from_numpy(np.concatenate([sigmas, [sigma_last]]).astype(np.float32))
+        # the coefficients depend only on (sigma table, step index, history length): memoised across calls, like UniPC's
+        if getattr(self, "_coef_cache", None) is None or self.sigmas.shape != new_sigmas.shape or not torch.equal(self.sigmas, new_sigmas):
+            self._coef_cache = {}
+        self.sigmas = new_sigmas
+        self.timesteps = torch.from_numpy(np.asarray(ts)).to(torch.int64)       # kept on the host: the loop indexes coefficient tables
+        self.num_inference_steps = len(ts)
+        self.model_outputs = [None] * c["solver_order"]
+        self.lower_order_nums = 0
+        self._step_index = None
+        self._begin_index = None
+
+    _alpha_sigma = staticmethod(UniPCMultistepScheduler._alpha_sigma)
+
+    def index_for_timestep(self, timestep, schedule_timesteps=None):
+        ts = self.timesteps if schedule_timesteps is None else schedule_timesteps
+        cand = (ts == int(timestep)).nonzero()
+        if len(cand) == 0:
+            return len(self.timesteps) - 1
+        return int(cand[1]) if len(cand) > 1 else int(cand[0])
+
+    def _lambda(self, idx):
+        alpha, sigma = self._alpha_sigma(self.sigmas[idx])
+        return alpha, sigma, torch.log(alpha) - torch.log(sigma)
+
+    def _update_coefs(self, order: int) -> List[float]:
+        """Coefficients of (sample, m0 [, m1 [, m2]] [, noise]) for the update of this order at the current step index.  The reference's
+        own factors (of sample, D0, D1, D2, noise) are fp32 0-dim tensor arithmetic as there; D1 and D2 are differences of the model
+        outputs (:717, :843-846), and their weights are folded into the outputs' coefficients in double, rounded once to fp32."""
+        i = self._step_index
+        sde = self.config["algorithm_type"] == "sde-dpmsolver++"
+        heun = self.config["solver_type"] == "heun"
+        alpha_t, sigma_t, lambda_t = self._lambda(i + 1)
+        _, sigma_s0, lambda_s0 = self._lambda(i)
+        h = lambda_t - lambda_s0
+        if sde:
+            cx = sigma_t / sigma_s0 * torch.exp(-h)
+            c0 = alpha_t * (1 - torch.exp(-2.0 * h))
+            cn = sigma_t * torch.sqrt(1.0 - torch.exp(-2 * h))
+        else:
+            cx = sigma_t / sigma_s0
+            c0 = -(alpha_t * (torch.exp(-h) - 1.0))
+        out = [float(cx), float(c0)]
+        if order >= 2:
+            _, _, lambda_s1 = self._lambda(i - 1)
+            r0 = float((lambda_s0 - lambda_s1) / h)
+            if sde:
+                c1 = 0.5 * (alpha_t * (1 - torch.exp(-2.0 * h))) if not heun else alpha_t * ((1.0 - torch.exp(-2.0 * h)) / (-2.0 * h) + 1.0)
+            elif order == 2 and not heun:
+                c1 = -0.5 * (alpha_t * (torch.exp(-h) - 1.0))
+            else:
+                c1 = alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)
+            c1 = float(c1)
+            if order == 2:                                           # D1 = (m0 - m1) / r0
+                out = [out[0], out[1] + c1 / r0, -c1 / r0]
+            else:                                                    # D1 = (1 + k) D1_0 - k D1_1, D2 = (D1_0 - D1_1) / (r0 + r1)
+                _, _, lambda_s2 = self._lambda(i - 2)
+                r1 = float((lambda_s1 - lambda_s2) / h)
+                c2 = float(-(alpha_t * ((torch.exp(-h) - 1.0 + h) / h ** 2 - 0.5)))
+                k, q = r0 / (r0 + r1), 1.0 / (r0 + r1)
+                a, b = c1 * (1 + k) + c2 * q, -c1 * k - c2 * q       # weights of D1_0 = (m0 - m1) / r0 and D1_1 = (m1 - m2) / r1
+                out = [out[0], out[1] + a / r0, -a / r0 + b / r1, -b / r1]
+        if sde:
+            out.append(float(cn))
+        return out
+
+    def _noise(self, shape, generator, device):
+        from .rng import PhiloxGenerator, randn_tensor
+        if isinstance(generator, PhiloxGenerator):
+            generator.device = generator.device or torch.device(device)
+            return generator.randn(shape)
+        return randn_tensor(shape, generator, device)
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
+             variance_noise: Optional[torch.Tensor] = None, return_dict: bool = True):
+        """:896-978.  `variance_noise`: the step's noise for the SDE type (drawn from `generator` when None: one draw per step, the last
+        step included, where its coefficient is zero)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._step_index = self.index_for_timestep(timestep) if self._begin_index is None else self._begin_index
+        c = self.config
+        n = len(self.timesteps)
+        final = self._step_index == n - 1 and (c["euler_at_final"] or (c["lower_order_final"] and n < 15) or c["final_sigmas_type"] == "zero")
+        second = self._step_index == n - 2 and c["lower_order_final"] and n < 15
+        eps = model_output.float().contiguous()
+        x = sample.float().contiguous()
+        if c["prediction_type"] == "sample":                                    # convert_model_output (:531-555): the x0 prediction
+            m_t = eps
+        else:
+            key = ("m", self._step_index)
+            cm = self._coef_cache.get(key)
+            if cm is None:
+                a_c, s_c = self._alpha_sigma(self.sigmas[self._step_index])
+                cm = [float(1 / a_c), float(-s_c / a_c)] if c["prediction_type"] == "epsilon" else [float(a_c), float(-s_c)]
+                self._coef_cache[key] = cm
+            m_t = hip.axpby_n([x, eps], cm)
+        for i in range(c["solver_order"] - 1):
+            self.model_outputs[i] = self.model_outputs[i + 1]
+        self.model_outputs[-1] = m_t
+        sde = c["algorithm_type"] == "sde-dpmsolver++"
+        if sde and variance_noise is None:
+            variance_noise = self._noise(tuple(x.shape), generator, x.device)
+        if c["solver_order"] == 1 or self.lower_order_nums < 1 or final:
+            order = 1
+        elif c["solver_order"] == 2 or self.lower_order_nums < 2 or second:
+            order = 2
+        else:
+            order = 3
+        key = ("u", order, self._step_index)
+        coefs = self._coef_cache.get(key)
+        if coefs is None:
+            coefs = self._coef_cache[key] = self._update_coefs(order)
+        terms = [x] + [self.model_outputs[-(i + 1)] for i in range(order)]
+        if sde:
+            terms.append(variance_noise if isinstance(variance_noise, _Sym) else variance_noise.to(x.device).float().contiguous())
+        prev = hip.axpby_n(terms, coefs)
+        if self.lower_order_nums < c["solver_order"]:
+            self.lower_order_nums += 1
+        self._step_index += 1
+        return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        raise NotImplementedError("DPMSolverMultistepScheduler.add_noise is only used by training / image-to-image (SURVEY.md §8 f-2)")
+
+
 # ---- the multistep schedulers' update on the device (mf_sched_step_dev) ------------------------------------------------------------
 # A step of PNDM / UniPC is a short list of mf_axpby_n calls over the guided noise prediction, the latents and the history the
 # scheduler keeps.  device_plan() runs the scheduler's OWN step() on stand-in tensors that record those calls (terms, order, float
@@ -560,11 +776,16 @@ def _held(sched) -> List[_Sym]:
     return list(out.values())
 
 
-def _plan_step(calls, e: _Sym, x: _Sym, prev: _Sym, held: List[_Sym], slots: list):
+def _plan_step(calls, e: _Sym, x: _Sym, prev: _Sym, held: List[_Sym], slots: list, noise: Optional[_Sym] = None):
     """Registers for one traced step.  `slots`: the value each state slot holds (carried from step to step, updated here).  Returns
-    ops as (dst, [src], coefs | None for a move) with locations ("r", 0 | 1), ("s", slot), ("t", temporary), and the temporaries used."""
+    ops as (dst, [src], coefs | None for a move) with locations ("r", 0 | 1), ("s", slot), ("t", temporary), and the temporaries used.
+    `noise`: the step's noise value, which the launch leaves in temporary 0 (free for reuse once the step has read it)."""
     keep = {id(s) for s in held}
     loc = {id(e): ("r", REG_EPS), id(x): ("r", REG_LATENTS)}
+    if noise is not None:
+        if id(noise) in keep:
+            raise NotImplementedError("device_plan: the scheduler keeps a step's noise between steps")
+        loc[id(noise)] = ("t", 0)
     for i, s in enumerate(slots):
         if s is not None:
             loc[id(s)] = ("s", i)
@@ -572,7 +793,7 @@ def _plan_step(calls, e: _Sym, x: _Sym, prev: _Sym, held: List[_Sym], slots: lis
     for _, xs, _ in calls:
         for i in {id(v) for v in xs}:
             reads[i] = reads.get(i, 0) + 1
-    temps, ops = [], []
+    temps, ops = ([] if noise is None else [noise]), []
 
     def free(v):
         return v is None or (id(v) not in keep and reads.get(id(v), 0) == 0)
@@ -616,8 +837,10 @@ class SchedPlan:
     """device_plan()'s result: `rows` (int32 [steps, sizeof(mf_sched_row) / 4], one mf_sched_row per step, host memory), `nslots` (S: the
     state buffer is [S, *latents.shape] fp32) and the traced scheduler, whose end state finish() hands to the real one."""
 
-    def __init__(self, rows: torch.Tensor, nslots: int, traced, steps: int):
+    def __init__(self, rows: torch.Tensor, nslots: int, traced, steps: int, noise_reg: int = -1):
         self.rows, self.nslots, self._traced, self.steps = rows, nslots, traced, steps
+        # the register mf_sched_step_noise_dev fills with the step's standard normals (SDE samplers); -1: the plan reads no noise
+        self.noise_reg = noise_reg
 
     def finish(self, sched, state: torch.Tensor) -> None:
         """After the last device step: `sched` ends in the state its own step() would have left — the counters of the trace, and the
@@ -635,10 +858,11 @@ class SchedPlan:
 
 
 def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
-    """The rows of mf_sched_step_dev for the first `steps` (default: all) entries of `sched.timesteps`, for a PNDMScheduler or
-    UniPCMultistepScheduler right after set_timesteps.  `sched` itself is not changed (a copy is traced)."""
+    """The rows of mf_sched_step_dev for the first `steps` (default: all) entries of `sched.timesteps`, for a PNDMScheduler,
+    UniPCMultistepScheduler or DPMSolverMultistepScheduler right after set_timesteps.  `sched` itself is not changed (a copy is traced).
+    The SDE type of DPM-Solver++ reads a noise value per step: its register is `noise_reg` of the plan (mf_sched_step_noise_dev)."""
     global hip
-    if not isinstance(sched, (PNDMScheduler, UniPCMultistepScheduler)):
+    if not isinstance(sched, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler)):
         raise NotImplementedError(f"{type(sched).__name__} has no device plan (DDIM updates through mf_cfg_ddim_step_dev)")
     if sched.num_inference_steps is None:
         raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
@@ -654,15 +878,17 @@ def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
     steps = len(ts) if steps is None else int(steps)
     slots, per_step, ntemps = [], [], 0
     real, tracer = hip, _TraceHip()
+    noisy = isinstance(sched, DPMSolverMultistepScheduler) and sched.config["algorithm_type"] == "sde-dpmsolver++"
     for k in range(steps):
         e, x = _Sym(f"e{k}"), _Sym(f"x{k}")
+        noise = _Sym(f"n{k}") if noisy else None
         tracer.calls = []
         hip = tracer
         try:
-            prev = traced.step(e, ts[k], x, return_dict=False)[0]
+            prev = traced.step(e, ts[k], x, **(dict(variance_noise=noise) if noisy else {}), return_dict=False)[0]
         finally:
             hip = real
-        ops, nt = _plan_step(tracer.calls, e, x, prev, _held(traced), slots)
+        ops, nt = _plan_step(tracer.calls, e, x, prev, _held(traced), slots, noise)
         per_step.append(ops)
         ntemps = max(ntemps, nt)
     nslots = len(slots)
@@ -693,4 +919,4 @@ def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
         rows.append(bytes(row))
     table = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.int32).view(steps, -1).clone() if rows else \
         torch.zeros(0, C.sizeof(_Row) // 4, dtype=torch.int32)
-    return SchedPlan(table, nslots, traced, steps)
+    return SchedPlan(table, nslots, traced, steps, base["t"] if noisy else -1)

@@ -268,6 +268,26 @@ int64_t mf_groupnorm_ws_floats(int32_t batch, int32_t groups, int32_t channels);
 /* 1 when the shape of [*, hw, channels] in `groups` groups (one segment) fits mf_groupnorm's one-launch slab form, the form sk_ws needs;
  * the pointer alignments the form also asks for are checked by mf_groupnorm itself.  No GPU needed. */
 int mf_groupnorm_slab_applies(int32_t hw, int32_t channels, int32_t groups);
+/* What mf_groupnorm would do with a descriptor, decided on the host: mf_groupnorm is this plan followed by its launches.
+ * mf_groupnorm_plan makes every check and every choice of the call (same return code, same mf_last_error text), launches nothing,
+ * needs no GPU and reads nothing behind the descriptor's pointers (only their null-ness and 16-byte alignment count).
+ * (appended; MF_ABI_VERSION stays 23: no existing entry or struct changed) */
+typedef struct mf_gn_plan {
+    int32_t form;               /* 0 one-launch slab; 1 own statistics pass; 2 producer's per-channel sums (part0 / part1); 3 producer's
+                                 * per-group sums (grp0) */
+    int32_t launches;           /* kernels the call issues: 1..3 */
+    int32_t vec;                /* channels per thread vector: 8 or 4 */
+    int32_t finalize;           /* who turns the statistics into (mean, rstd): 0 a finalize launch, 1 every apply block combines the
+                                 * chunks, 2 every apply block combines the producer's group sums; 0 for the slab */
+    int32_t centered;           /* 1: an fp32 output is formed around the group's mean carried as two floats; 0 for the slab */
+    int32_t chunks, rows_per_chunk;     /* of the statistics pass (they place the statistics in ws for forms 1-3); 0 for the slab */
+    int32_t rows_per_block;     /* apply pass: rows per block; slab: rows of an image in flight per slab */
+    int32_t blocks, threads;    /* of the last launch (the apply pass, or the slab) */
+    int32_t lds_bytes;          /* largest dynamic LDS request of any launch of the plan */
+    int32_t finalize_parts;     /* form 2: threads per channel of the finalize launch; else 0 */
+} mf_gn_plan;
+int mf_groupnorm_plan(const mf_groupnorm_desc* d, mf_gn_plan* out);
+int mf_sizeof_gn_plan(void);
 
 /* LayerNorm over the last dim of [rows][c]; replaces nn.LayerNorm (attention.py:203,233,261). */
 int mf_layernorm(const void* x, int32_t in_dtype, void* out, int32_t out_dtype, const float* gamma,

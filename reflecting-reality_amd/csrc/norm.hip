@@ -1,13 +1,15 @@
 // GroupNorm(+SiLU), LayerNorm and row softmax for NHWC / token-major activations on gfx950.
 // All three are HBM-bound: one read + one write of the tensor (GroupNorm above 16x16 reads it twice: stats,
 // then apply), fp32 statistics, vectorised 4-channel accesses, no atomics (bitwise reproducible).
-#include <stdlib.h>
 #include <type_traits>
 #include "mf_common.h"
 
 namespace {
 
-constexpr int GN_MAX_CHUNKS = 64;
+// Settled by sweeps (profiles/r03_groupnorm_grid_sweep.txt, profiles/gn_streaming_ab.txt: "the block target stays 1024 and U stays 4"):
+constexpr int GN_MAX_CHUNKS = 64;          // chunks of rows per image in the statistics pass (and slots per group in ws)
+constexpr int GN_TARGET_BLOCKS = 1024;     // blocks of the apply pass: ~4 row blocks per CU
+constexpr int GN_ROWS_IN_FLIGHT = 4;       // whole rows a thread of either pass has in flight (U); 8 were slower or the same everywhere
 constexpr int GN_BLK = 512;
 
 struct GnArgs {
@@ -195,8 +197,9 @@ __device__ __forceinline__ float gn_pivot(const GnArgs& p, int b, int g) {
         return lo;
     }
 }
-template <int IN_DT, int VW, int U>
+template <int IN_DT, int VW>
 __global__ __launch_bounds__(GN_BLK) void gn_stats_kernel(const GnArgs p) {
+    constexpr int U = GN_ROWS_IN_FLIGHT;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float2* chan = reinterpret_cast<float2*>(smem_raw);   // [rif][C] (sum, sum of squares)
     const int chunk = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
@@ -518,19 +521,19 @@ __global__ __launch_bounds__(GN_BLK) void gn_finalize_part_kernel(const GnArgs p
 
 // Waves per SIMD the apply kernel is compiled for.  With U = 4 packed 16-bit rows (4 VGPRs each) and the scale / shift of 8 channels
 // the row loop needs about 60 VGPRs, but the statistics combine in the prologue (double-precision divisions, a square root) spills
-// below 80: 6 waves per SIMD = three resident blocks of 8 waves per CU.  Two segments (per-lane row pointers) and U = 8 take the
+// below 80: 6 waves per SIMD = three resident blocks of 8 waves per CU.  Two segments (per-lane row pointers) take the
 // 96 VGPRs of 5 waves; fp32 rows need more.  tests/test_groupnorm_resources_cpu.py holds the 16-bit kernels to 96 and no scratch.
-constexpr int gn_apply_waves(int in_dt, int out_dt, int u, bool seg2) {
-    if (in_dt == MF_F32 && u > 4) return 2;             // (the developer sweep's 16 fp32 loads in flight: 64 VGPRs of rows alone)
-    return in_dt == MF_F32 || out_dt == MF_F32 ? 4 : u <= 4 && !seg2 ? 6 : 5;
+constexpr int gn_apply_waves(int in_dt, int out_dt, bool seg2) {
+    return in_dt == MF_F32 || out_dt == MF_F32 ? 4 : !seg2 ? 6 : 5;
 }
 
 // Pass 2, grid (row blocks, batch): pure streaming y = silu(x*a[c] + b[c]) with the thread's a/b in registers.
-// Storage dtypes, vector width, rows in flight and SiLU are template arguments, and everything else a launch decides (the three
+// Storage dtypes, vector width and SiLU are template arguments, the rows in flight (U) a constant, and everything else a launch decides (the three
 // fuse_finalize modes, the segment a column lies in) is settled before the row loop, so that the loop is U whole-row loads issued
 // back to back, counted waits, branch-free arithmetic on one unpacked row at a time and whole-row stores.
-template <int IN_DT, int OUT_DT, int VW, int U, bool SILU, bool SEG2>
-__global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, U, SEG2)) void gn_apply_kernel(const GnArgs p, int rows_per_block) {
+template <int IN_DT, int OUT_DT, int VW, bool SILU, bool SEG2>
+__global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, SEG2)) void gn_apply_kernel(const GnArgs p, int rows_per_block) {
+    constexpr int U = GN_ROWS_IN_FLIGHT;
     const int b = blockIdx.y, t = threadIdx.x;
     const int lcol = t % p.tpr, trow = t / p.tpr;
     __shared__ float gm[64], gr[64], gl[64];
@@ -549,16 +552,10 @@ __global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, U, SEG2)) voi
     }
     if (p.fuse_finalize) {       // every block combines the chunk statistics itself: one launch (and its gap) less
         // (the affine parameters of the thread's first column are requested first: their latency hides under the combine)
-        if constexpr (U <= 4) {
-            gn_loadf<VW>(p.gamma + lcol * VW, ga);
-            gn_loadf<VW>(p.beta + lcol * VW, be);
-        }
+        gn_loadf<VW>(p.gamma + lcol * VW, ga);
+        gn_loadf<VW>(p.beta + lcol * VW, be);
         if (p.fuse_finalize == 2) gn_group_from_sums(p, b, gm, gr, gl);
         else gn_group_mean_rstd(p, b, gm, gr, gl);
-        if constexpr (U > 4) {                           // (U = 8, the developer sweep, has no registers to spare across the combine)
-            gn_loadf<VW>(p.gamma + lcol * VW, ga);
-            gn_loadf<VW>(p.beta + lcol * VW, be);
-        }
         __syncthreads();
         if (p.stats_out && blockIdx.x == 0)
             for (int g = t; g < p.G; g += blockDim.x) {
@@ -643,13 +640,10 @@ __global__ __launch_bounds__(GN_BLK, gn_apply_waves(IN_DT, OUT_DT, U, SEG2)) voi
                 else gn_load<IN_DT, VW>(gn_uniform(ptr + u * step) + ioff, raw[u]);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if constexpr (U > 4) __builtin_amdgcn_sched_barrier(0);      // (eight rows are held: one row's temporaries at a time)
-                finish(raw[u], optr + u * ostep);
-            }
+            for (int u = 0; u < U; ++u) finish(raw[u], optr + u * ostep);
         }
         // at most U - 1 rows are left: TB at a time, their loads go out together too (a row past the end re-reads row r)
-        constexpr int TB = U > 4 ? 1 : 3;      // (U = 8, the developer sweep, holds eight rows already: its tail goes row by row)
+        constexpr int TB = U - 1;
         for (; r < r1; r += TB * p.rif, ptr += TB * step, optr += TB * ostep) {
             gn_raw<IN_DT, VW> raw[TB];
 #pragma unroll
@@ -1019,27 +1013,8 @@ bool gn_for_dtypes(int in_dt, int out_dt, F&& f) {
     return false;
 }
 
-template <int I, int O>
-void gn_launch_slab(const GnArgs& a, dim3 grid, int nthr, size_t smem, hipStream_t s, int sc, int nv, int P) {
-    auto* kern = a.sk_ws ? (a.silu ? gn_slab_kernel<I, O, true, true> : gn_slab_kernel<I, O, false, true>)
-                         : (a.silu ? gn_slab_kernel<I, O, true, false> : gn_slab_kernel<I, O, false, false>);
-    hipLaunchKernelGGL(kern, grid, dim3(nthr), smem, s, a, sc, nv, P);
-}
-
-template <int I>
-void gn_launch_stats(const GnArgs& a, int vw, int u, dim3 grid, int nthr, size_t smem, hipStream_t s) {
-    auto* kern = vw == 8 ? (u == 8 ? gn_stats_kernel<I, 8, 8> : gn_stats_kernel<I, 8, 4>) : gn_stats_kernel<I, 4, 4>;
-    hipLaunchKernelGGL(kern, grid, dim3(nthr), smem, s, a);
-}
-
-template <int I, int O, bool SILU, bool SEG2>
-void gn_launch_apply(const GnArgs& a, int vw, int u, dim3 grid, int nthr, hipStream_t s, int rows_per_block) {
-    auto* kern = vw == 8 ? (u == 8 ? gn_apply_kernel<I, O, 8, 8, SILU, SEG2> : gn_apply_kernel<I, O, 8, 4, SILU, SEG2>) : gn_apply_kernel<I, O, 4, 4, SILU, SEG2>;
-    hipLaunchKernelGGL(kern, grid, dim3(nthr), 0, s, a, rows_per_block);
-}
-
 // The one-launch slab form of mf_groupnorm, shape half: 8-channel vectors, slabs of sc = lcm(cpg, 8) channels x P rows of an image of at
-// most 4 P rows, at most 1024 threads and 64 KB of LDS per block.  (The alignment half is mf_groupnorm's.)
+// most 4 P rows, at most 1024 threads and 64 KB of LDS per block.  (The alignment half is gn_plan's.)
 struct GnSlab { int sc, nv, P, nthr; size_t smem; };
 bool gn_slab_shape(int hw, int c0, int c1, int groups, GnSlab* sl) {
     const int C = c0 + c1;
@@ -1054,6 +1029,129 @@ bool gn_slab_shape(int hw, int c0, int c1, int groups, GnSlab* sl) {
     return hw <= sl->P * 4 && C % sl->sc == 0 && sl->sc / cpg <= 8 && sl->nthr <= 1024 && sl->smem <= 64 * 1024;
 }
 
+// ---- plan, then launch: gn_plan makes every check and every decision of a call on the host (no HIP runtime call; of the descriptor's
+// pointers only null-ness and 16-byte alignment count), gn_launch issues what the plan says.  mf_groupnorm is one after the other.
+enum GnForm { kGnSlab = 0, kGnOwnStats = 1, kGnChannelSums = 2, kGnGroupSums = 3 };      // mf_gn_plan::form
+
+struct GnPlan {
+    GnArgs a;                 // what the kernels take
+    mf_gn_plan r;             // the decisions, as mf_groupnorm_plan reports them: gn_launch reads grids, blocks and LDS sizes from here
+    GnSlab sl;                // kGnSlab: the geometry of a slab
+    int batch, slices, gps;   // kGnChannelSums: slices of the groups per image and groups per slice of the finalize launch
+};
+
+int gn_plan(const mf_groupnorm_desc* d, GnPlan* plan) {
+    MF_CHECK_ARG(d && d->x0 && d->out && d->gamma && d->beta && d->ws, "mf_groupnorm: null pointer");
+    MF_CHECK_ARG((d->x1 != nullptr) == (d->c1 > 0) && d->c0 > 0, "mf_groupnorm: bad segments");
+    const int C = d->c0 + d->c1;
+    MF_CHECK_ARG(d->groups > 0 && C % d->groups == 0, "mf_groupnorm: C=%d not divisible by groups=%d", C, d->groups);
+    MF_CHECK_ARG(d->c0 % 4 == 0 && d->c1 % 4 == 0, "mf_groupnorm: channel counts must be multiples of 4");
+    MF_CHECK_ARG(d->batch >= 1 && d->hw >= 1, "mf_groupnorm: bad batch/hw");
+    MF_CHECK_ARG(!(mf_any_f16(d->in_dtype, d->out_dtype) && mf_any_bf16(d->in_dtype, d->out_dtype)), "mf_groupnorm: fp16 and bf16 operands in one launch");
+    MF_CHECK_ARG(d->groups <= 64, "mf_groupnorm: at most 64 groups");
+    *plan = GnPlan{};
+    plan->batch = d->batch;
+    GnArgs& a = plan->a;
+    a.x0 = (const char*)d->x0; a.x1 = (const char*)d->x1;
+    a.C0 = d->c0; a.C1 = d->c1; a.C = C; a.in_dt = d->in_dtype; a.HW = d->hw; a.G = d->groups;
+    a.cpg = C / d->groups;
+    a.eps = d->eps; a.gamma = d->gamma; a.beta = d->beta; a.silu = d->silu;
+    a.out = (char*)d->out; a.out_dt = d->out_dtype; a.ws = d->ws; a.stats_out = d->stats_out;
+    a.ws_ab = d->ws + (int64_t)d->batch * d->groups * GN_MAX_CHUNKS * 2;
+    const bool affine16 = mf_aligned16(d->gamma) && mf_aligned16(d->beta);
+    const bool known = gn_for_dtypes(d->in_dtype, d->out_dtype, [](auto, auto) {});
+    // The one-launch slab kernel for the low-resolution levels.  Measured against the two-launch form (tools/bench_gn.py, batch 8, us):
+    // 8x8 C 1280: 11.7 -> 5.0, 2560: 13.0 -> 6.0; 16x16 C 1280: 12.8 -> 8.1, 2560: 17.4 -> 9.8
+    const GnSlab& sl = plan->sl;
+    const bool slab_ok = gn_slab_shape(d->hw, d->c0, d->c1, d->groups, &plan->sl) && affine16 && mf_aligned16(d->x0) && mf_aligned16(d->out) && (!d->x1 || mf_aligned16(d->x1));
+    if (d->sk_ws) {
+        MF_CHECK_ARG(slab_ok && d->c1 == 0 && d->sk_splits >= 2 && d->stats_out == nullptr && mf_aligned16(d->sk_ws) &&
+                         (!d->sk_bias || mf_aligned16(d->sk_bias)) && (!d->sk_temb || (mf_aligned16(d->sk_temb) && d->sk_ld_temb % 4 == 0)),
+                     "mf_groupnorm: a deferred split-K input (sk_ws) needs the one-launch form (hw <= 256, channels %% 8 == 0, one segment), "
+                     ">= 2 slabs, 16-byte aligned slabs / bias / temb and no stats_out");
+        a.sk_ws = d->sk_ws; a.sk_splits = d->sk_splits; a.sk_bias = d->sk_bias; a.sk_temb = d->sk_temb; a.sk_ld_temb = d->sk_ld_temb;
+        a.sk_alpha = d->sk_alpha; a.sk_mn = (int64_t)d->batch * d->hw * C;
+    }
+    if (slab_ok) {
+        MF_CHECK_ARG(known, "mf_groupnorm: no kernel for in_dtype %d with out_dtype %d", d->in_dtype, d->out_dtype);
+        plan->r = mf_gn_plan{kGnSlab, 1, 8, 0, 0, 0, 0, sl.P, C / sl.sc * d->batch, sl.nthr, (int32_t)sl.smem, 0};
+        return MF_OK;
+    }
+    // The streaming forms.  Statistics from the producers' per-channel sums: every present segment has them and their row blocks divide
+    // the image (at most 128 per image: the finalize launch walks them serially per channel).  From the producer's per-GROUP sums: no
+    // statistics pass and no finalize launch — every apply block combines its image's row blocks.  Else a pass of its own.
+    const bool from_parts = d->part0 != nullptr && d->part0_rows > 0 && d->hw % d->part0_rows == 0 && d->hw / d->part0_rows <= 128 &&
+                            (d->c1 == 0 || (d->part1 != nullptr && d->part1_rows > 0 && d->hw % d->part1_rows == 0 && d->hw / d->part1_rows <= 128));
+    const bool from_groups = d->grp0 != nullptr && d->c1 == 0 && d->grp0_rows > 0 && d->hw % d->grp0_rows == 0 && d->hw / d->grp0_rows <= 64 && affine16;
+    const int form = from_groups ? kGnGroupSums : from_parts ? kGnChannelSums : kGnOwnStats;
+    a.part0 = (const float2*)d->part0; a.part1 = (const float2*)d->part1; a.pr0 = d->part0_rows; a.pr1 = d->part1_rows;
+    if (from_groups) { a.grp0 = (const float2*)d->grp0; a.nch0 = d->hw / d->grp0_rows; }
+    a.rows_per_chunk = d->hw > 16 * GN_MAX_CHUNKS ? (d->hw + GN_MAX_CHUNKS - 1) / GN_MAX_CHUNKS : 16;
+    a.nchunks = (d->hw + a.rows_per_chunk - 1) / a.rows_per_chunk;
+    // Who turns the statistics into (mean, rstd): every apply block (1: the chunks of the own pass; 2: the producer's group sums) or a
+    // finalize launch (0).  Measured (tools/bench_gn.py): -1.5...2 us per GroupNorm up to 32x32, +1 us at 64x64 (64 chunks combined by 256
+    // blocks; round 3: fetching a thread's first rows AHEAD of the combine was neutral there, 26.3 vs 25.6 us, and removed).
+    a.fuse_finalize = from_groups ? 2 : !from_parts && d->hw <= 1024 && affine16 ? 1 : 0;
+    a.centered = d->out_dtype == MF_F32 && a.nchunks >= 2 && affine16;
+    const int vw = (d->c0 % 8 == 0 && d->c1 % 8 == 0) ? 8 : 4;
+    a.cvn = C / vw;
+    a.tpr = a.cvn < GN_BLK ? a.cvn : GN_BLK;
+    a.rif = GN_BLK / a.tpr;
+    const int nthr = (a.tpr * a.rif + 63) / 64 * 64;
+    const size_t smem1 = (size_t)a.rif * C * sizeof(float2);      // the statistics pass's [rif][C] sums
+    MF_CHECK_ARG(smem1 <= 64 * 1024, "mf_groupnorm: C=%d too large", C);
+    // the apply pass: GN_TARGET_BLOCKS row blocks in all, at least 4 rows per thread
+    const int rows_even = (int)(((int64_t)d->hw * d->batch + GN_TARGET_BLOCKS - 1) / GN_TARGET_BLOCKS);
+    const int rows_per_block = rows_even < 4 * a.rif ? 4 * a.rif : rows_even;
+    const int nblk = (d->hw + rows_per_block - 1) / rows_per_block;
+    int kparts = 0;
+    if (form == kGnChannelSums) {
+        // finalize from partial sums: 8 slices of the groups per image, and as many threads per channel as the block has room for
+        plan->slices = d->groups >= 32 ? 8 : 1;
+        plan->gps = (d->groups + plan->slices - 1) / plan->slices;
+        kparts = GN_BLK / (plan->gps * a.cpg);
+        const int nb0 = d->hw / d->part0_rows, nb1 = d->c1 ? d->hw / d->part1_rows : nb0, nbmin = nb0 < nb1 ? nb0 : nb1;
+        kparts = kparts > nbmin ? nbmin : kparts < 1 ? 1 : kparts;
+        while ((size_t)kparts * plan->gps * a.cpg * sizeof(double2) > 48 * 1024 && kparts > 1) --kparts;
+    }
+    MF_CHECK_ARG(known, "mf_groupnorm: no kernel for in_dtype %d with out_dtype %d", d->in_dtype, d->out_dtype);
+    const size_t smem = form == kGnOwnStats ? smem1 : (size_t)kparts * plan->gps * a.cpg * sizeof(double2);      // (group sums: 0)
+    plan->r = mf_gn_plan{form, from_groups ? 1 : from_parts || a.fuse_finalize ? 2 : 3, vw, a.fuse_finalize, a.centered, a.nchunks,
+                         a.rows_per_chunk, rows_per_block, nblk * d->batch, nthr, (int32_t)smem, kparts};
+    return MF_OK;
+}
+
+template <int I, int O, int VW>
+auto* gn_apply_for(bool silu, bool seg2) {
+    return silu ? (seg2 ? gn_apply_kernel<I, O, VW, true, true> : gn_apply_kernel<I, O, VW, true, false>)
+                : (seg2 ? gn_apply_kernel<I, O, VW, false, true> : gn_apply_kernel<I, O, VW, false, false>);
+}
+
+int gn_launch(const GnPlan& p, hipStream_t s) {
+    const GnArgs& a = p.a;
+    const mf_gn_plan& r = p.r;
+    gn_for_dtypes(a.in_dt, a.out_dt, [&](auto in_c, auto out_c) {        // (gn_plan refused a pair without kernels)
+        constexpr int I = decltype(in_c)::value, O = decltype(out_c)::value;
+        if (r.form == kGnSlab) {
+            auto* kern = a.sk_ws ? (a.silu ? gn_slab_kernel<I, O, true, true> : gn_slab_kernel<I, O, false, true>)
+                                 : (a.silu ? gn_slab_kernel<I, O, true, false> : gn_slab_kernel<I, O, false, false>);
+            hipLaunchKernelGGL(kern, dim3(a.C / p.sl.sc, p.batch), dim3(r.threads), r.lds_bytes, s, a, p.sl.sc, p.sl.nv, p.sl.P);
+            return;
+        }
+        if (r.form == kGnChannelSums) {
+            hipLaunchKernelGGL(gn_finalize_part_kernel, dim3(p.batch, p.slices), dim3(GN_BLK), r.lds_bytes, s, a, p.gps, r.finalize_parts);
+        } else if (r.form == kGnOwnStats) {
+            auto* stats = r.vec == 8 ? gn_stats_kernel<I, 8> : gn_stats_kernel<I, 4>;
+            hipLaunchKernelGGL(stats, dim3(a.nchunks, p.batch), dim3(r.threads), r.lds_bytes, s, a);
+            if (!a.fuse_finalize) hipLaunchKernelGGL(gn_finalize_kernel, dim3(p.batch), dim3(GN_BLK), 0, s, a);
+        }
+        auto* apply = r.vec == 8 ? gn_apply_for<I, O, 8>(a.silu, a.C1) : gn_apply_for<I, O, 4>(a.silu, a.C1);
+        hipLaunchKernelGGL(apply, dim3(r.blocks / p.batch, p.batch), dim3(r.threads), 0, s, a, r.rows_per_block);
+    });
+    MF_CHECK_LAUNCH(r.form == kGnSlab ? "mf_groupnorm(slab)" : "mf_groupnorm(apply)");
+    return MF_OK;
+}
+
 }  // namespace
 
 extern "C" int mf_groupnorm_slab_applies(int32_t hw, int32_t channels, int32_t groups) {
@@ -1066,112 +1164,18 @@ extern "C" int64_t mf_groupnorm_ws_floats(int32_t batch, int32_t groups, int32_t
 }
 
 extern "C" int mf_groupnorm(const mf_groupnorm_desc* d, void* stream) {
-    MF_CHECK_ARG(d && d->x0 && d->out && d->gamma && d->beta && d->ws, "mf_groupnorm: null pointer");
-    MF_CHECK_ARG((d->x1 != nullptr) == (d->c1 > 0) && d->c0 > 0, "mf_groupnorm: bad segments");
-    const int C = d->c0 + d->c1;
-    MF_CHECK_ARG(d->groups > 0 && C % d->groups == 0, "mf_groupnorm: C=%d not divisible by groups=%d", C, d->groups);
-    MF_CHECK_ARG(d->c0 % 4 == 0 && d->c1 % 4 == 0, "mf_groupnorm: channel counts must be multiples of 4");
-    MF_CHECK_ARG(d->batch >= 1 && d->hw >= 1, "mf_groupnorm: bad batch/hw");
-    MF_CHECK_ARG(!(mf_any_f16(d->in_dtype, d->out_dtype) && mf_any_bf16(d->in_dtype, d->out_dtype)), "mf_groupnorm: fp16 and bf16 operands in one launch");
-    GnArgs a{};
-    a.x0 = (const char*)d->x0; a.x1 = (const char*)d->x1;
-    a.C0 = d->c0; a.C1 = d->c1; a.C = C; a.in_dt = d->in_dtype; a.HW = d->hw; a.G = d->groups;
-    a.cpg = C / d->groups;
-    static const int gn_chunks = getenv("MFHIP_GN_CHUNKS") ? atoi(getenv("MFHIP_GN_CHUNKS")) : GN_MAX_CHUNKS;      // developer sweep
-    const int want_chunks = gn_chunks >= 1 && gn_chunks <= GN_MAX_CHUNKS ? gn_chunks : GN_MAX_CHUNKS;
-    a.rows_per_chunk = (d->hw + want_chunks - 1) / want_chunks;
-    if (a.rows_per_chunk < 16) a.rows_per_chunk = 16;
-    a.nchunks = (d->hw + a.rows_per_chunk - 1) / a.rows_per_chunk;
-    a.eps = d->eps; a.gamma = d->gamma; a.beta = d->beta; a.silu = d->silu;
-    a.out = (char*)d->out; a.out_dt = d->out_dtype; a.ws = d->ws; a.stats_out = d->stats_out;
-    a.ws_ab = d->ws + (int64_t)d->batch * d->groups * GN_MAX_CHUNKS * 2;
-    MF_CHECK_ARG(d->groups <= 64, "mf_groupnorm: at most 64 groups");
-    static const bool gn3 = getenv("MFHIP_GN3") != nullptr;     // A/B switch: separate finalize launch
-    // measured (tools/bench_gn.py): -1.5...2 us per GroupNorm up to 32x32, +1 us at 64x64 (64 chunks combined by 256 blocks)
-    // (round 3: fetching a thread's first rows AHEAD of the combine, so that the fused form could also serve 64x64, was
-    // measured neutral there — 26.3 vs 25.6 us, tools/bench_gn.py, and 16.70 vs 16.75 ms per denoise step — and removed)
-    a.fuse_finalize = !gn3 && d->hw <= 1024 && mf_aligned16(d->gamma) && mf_aligned16(d->beta);
-    a.centered = d->out_dtype == MF_F32 && a.nchunks >= 2 && mf_aligned16(d->gamma) && mf_aligned16(d->beta);
-    const int vw = (d->c0 % 8 == 0 && d->c1 % 8 == 0) ? 8 : 4;
-    hipStream_t s = (hipStream_t)stream;
-    {   // one-launch slab kernel for the low-resolution levels
-        // measured (tools/bench_gn.py, batch 8, us): 8x8 C 1280: 11.7 -> 5.0, 2560: 13.0 -> 6.0; 16x16 C 1280: 12.8 -> 8.1,
-        // 2560: 17.4 -> 9.8
-        static const bool two_pass = getenv("MFHIP_GN_2PASS") != nullptr;     // A/B switch: always the two-launch form
-        GnSlab sl;
-        const bool shape_ok = gn_slab_shape(d->hw, d->c0, d->c1, d->groups, &sl);
-        a.sk_ws = d->sk_ws; a.sk_splits = d->sk_splits; a.sk_bias = d->sk_bias; a.sk_temb = d->sk_temb; a.sk_ld_temb = d->sk_ld_temb;
-        a.sk_alpha = d->sk_alpha; a.sk_mn = (int64_t)d->batch * d->hw * C;
-        const bool slab_ok = shape_ok && mf_aligned16(d->gamma) && mf_aligned16(d->beta) && mf_aligned16(d->x0) && mf_aligned16(d->out) &&
-                             (!d->x1 || mf_aligned16(d->x1));
-        if (d->sk_ws) {
-            MF_CHECK_ARG(slab_ok && d->c1 == 0 && d->sk_splits >= 2 && d->stats_out == nullptr && mf_aligned16(d->sk_ws) &&
-                             (!d->sk_bias || mf_aligned16(d->sk_bias)) && (!d->sk_temb || (mf_aligned16(d->sk_temb) && d->sk_ld_temb % 4 == 0)),
-                         "mf_groupnorm: a deferred split-K input (sk_ws) needs the one-launch form (hw <= 256, channels %% 8 == 0, one segment), "
-                         ">= 2 slabs, 16-byte aligned slabs / bias / temb and no stats_out");
-        }
-        if ((!two_pass || d->sk_ws) && slab_ok) {
-            const bool known = gn_for_dtypes(d->in_dtype, d->out_dtype, [&](auto in_c, auto out_c) {
-                gn_launch_slab<decltype(in_c)::value, decltype(out_c)::value>(a, dim3(C / sl.sc, d->batch), sl.nthr, sl.smem, s, sl.sc, sl.nv, sl.P);
-            });
-            MF_CHECK_ARG(known, "mf_groupnorm: no kernel for in_dtype %d with out_dtype %d", d->in_dtype, d->out_dtype);
-            MF_CHECK_LAUNCH("mf_groupnorm(slab)");
-            return MF_OK;
-        }
-    }
-    // statistics from the producers' partial sums: every present segment has them and their row blocks divide the image
-    // (at most 128 partial blocks per image: the finalize launch walks them serially per channel)
-    const bool from_parts = d->part0 != nullptr && d->part0_rows > 0 && d->hw % d->part0_rows == 0 && d->hw / d->part0_rows <= 128 &&
-                            (d->c1 == 0 || (d->part1 != nullptr && d->part1_rows > 0 && d->hw % d->part1_rows == 0 && d->hw / d->part1_rows <= 128));
-    a.part0 = (const float2*)d->part0; a.part1 = (const float2*)d->part1; a.pr0 = d->part0_rows; a.pr1 = d->part1_rows;
-    if (from_parts) a.fuse_finalize = 0;
-    // per-GROUP sums from the producer: no statistics pass and no finalize launch — every apply block combines its image's row blocks
-    const bool from_groups = d->grp0 != nullptr && d->c1 == 0 && d->grp0_rows > 0 && d->hw % d->grp0_rows == 0 && d->hw / d->grp0_rows <= 64 &&
-                             mf_aligned16(d->gamma) && mf_aligned16(d->beta);
-    if (from_groups) { a.grp0 = (const float2*)d->grp0; a.nch0 = d->hw / d->grp0_rows; a.fuse_finalize = 2; }
-    a.cvn = C / vw;
-    a.tpr = a.cvn < GN_BLK ? a.cvn : GN_BLK;
-    a.rif = GN_BLK / a.tpr;
-    const int nthr = (a.tpr * a.rif + 63) / 64 * 64;
-    const size_t smem1 = (size_t)a.rif * C * sizeof(float2) > (size_t)2 * d->groups * sizeof(float)
-                             ? (size_t)a.rif * C * sizeof(float2) : (size_t)2 * d->groups * sizeof(float);
-    MF_CHECK_ARG(smem1 <= 64 * 1024, "mf_groupnorm: C=%d too large", C);
-    // ~4 row blocks per CU, at least 4 rows per thread
-    static const int gn_blocks = getenv("MFHIP_GN_APPLY_BLOCKS") ? atoi(getenv("MFHIP_GN_APPLY_BLOCKS")) : 1024;   // developer sweep
-    const int tgt = gn_blocks >= 64 ? gn_blocks : 1024;
-    int rows_per_block = (int)(((int64_t)d->hw * d->batch + tgt - 1) / tgt);
-    if (rows_per_block < 4 * a.rif) rows_per_block = 4 * a.rif;
-    const int nblk = (d->hw + rows_per_block - 1) / rows_per_block;
-    static const int gn_u = getenv("MFHIP_GN_UNROLL") ? atoi(getenv("MFHIP_GN_UNROLL")) : 4;      // developer sweep: 4 or 8 rows in flight
-    // finalize from partial sums: 8 slices of the groups per image, and as many threads per channel as the block has room for
-    const int gn_slices = d->groups >= 32 ? 8 : 1, gn_gps = (d->groups + gn_slices - 1) / gn_slices;
-    int gn_kparts = GN_BLK / (gn_gps * a.cpg);
-    {
-        const int nb0 = from_parts ? d->hw / d->part0_rows : 1, nb1 = (from_parts && d->c1) ? d->hw / d->part1_rows : nb0;
-        const int nbmin = nb0 < nb1 ? nb0 : nb1;
-        if (gn_kparts > nbmin) gn_kparts = nbmin;
-        if (gn_kparts < 1) gn_kparts = 1;
-        while ((size_t)gn_kparts * gn_gps * a.cpg * sizeof(double2) > 48 * 1024 && gn_kparts > 1) --gn_kparts;
-    }
-    const int u = vw == 8 && gn_u == 8 ? 8 : 4;
-    const bool known = gn_for_dtypes(d->in_dtype, d->out_dtype, [&](auto in_c, auto out_c) {
-        constexpr int I = decltype(in_c)::value, O = decltype(out_c)::value;
-        if (from_groups) {
-        } else if (from_parts) {
-            hipLaunchKernelGGL(gn_finalize_part_kernel, dim3(d->batch, gn_slices), dim3(GN_BLK), (size_t)gn_kparts * gn_gps * a.cpg * sizeof(double2), s, a, gn_gps, gn_kparts);
-        } else {
-            gn_launch_stats<I>(a, vw, u, dim3(a.nchunks, d->batch), nthr, smem1, s);
-            if (!a.fuse_finalize) hipLaunchKernelGGL(gn_finalize_kernel, dim3(d->batch), dim3(GN_BLK), 0, s, a);
-        }
-        const dim3 grid(nblk, d->batch);
-        if (a.silu && a.C1) gn_launch_apply<I, O, true, true>(a, vw, u, grid, nthr, s, rows_per_block);
-        else if (a.silu) gn_launch_apply<I, O, true, false>(a, vw, u, grid, nthr, s, rows_per_block);
-        else if (a.C1) gn_launch_apply<I, O, false, true>(a, vw, u, grid, nthr, s, rows_per_block);
-        else gn_launch_apply<I, O, false, false>(a, vw, u, grid, nthr, s, rows_per_block);
-    });
-    MF_CHECK_ARG(known, "mf_groupnorm: no kernel for in_dtype %d with out_dtype %d", d->in_dtype, d->out_dtype);
-    MF_CHECK_LAUNCH("mf_groupnorm(apply)");
-    return MF_OK;
+    GnPlan plan;
+    const int rc = gn_plan(d, &plan);
+    return rc != MF_OK ? rc : gn_launch(plan, (hipStream_t)stream);
+}
+
+extern "C" int mf_sizeof_gn_plan(void) { return (int)sizeof(mf_gn_plan); }
+extern "C" int mf_groupnorm_plan(const mf_groupnorm_desc* d, mf_gn_plan* out) {
+    MF_CHECK_ARG(out != nullptr, "mf_groupnorm_plan: null plan");
+    GnPlan p;
+    const int rc = gn_plan(d, &p);
+    if (rc == MF_OK) *out = p.r;
+    return rc;
 }
 
 extern "C" int mf_layernorm(const void* x, int32_t in_dtype, void* out, int32_t out_dtype, const float* gamma,
@@ -1179,10 +1183,9 @@ extern "C" int mf_layernorm(const void* x, int32_t in_dtype, void* out, int32_t 
     MF_CHECK_ARG(x && out && gamma && beta, "mf_layernorm: null pointer");
     MF_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= 2048, "mf_layernorm: C=%d must be a multiple of 4 and <= 2048", c);
     if (rows <= 0) return MF_OK;
-    static const bool ln4 = getenv("MFHIP_LN4") != nullptr;     // A/B switch: the 4-channel kernel
     MF_CHECK_ARG(!(mf_any_f16(in_dtype, out_dtype) && mf_any_bf16(in_dtype, out_dtype)), "mf_layernorm: fp16 and bf16 operands in one launch");
     const bool f16 = mf_any_f16(in_dtype, out_dtype);
-    const bool v8 = !ln4 && c % 8 == 0 && mf_aligned16(x) && mf_aligned16(out) && mf_aligned16(gamma) && mf_aligned16(beta);
+    const bool v8 = c % 8 == 0 && mf_aligned16(x) && mf_aligned16(out) && mf_aligned16(gamma) && mf_aligned16(beta);
     const dim3 grid((unsigned)(v8 ? (rows + 7) / 8 : (rows + 3) / 4));
     auto* kern = v8 ? (f16 ? layernorm8_kernel<true> : layernorm8_kernel<false>) : (f16 ? layernorm_kernel<true> : layernorm_kernel<false>);
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, (const char*)x, in_dtype, (char*)out, out_dtype, gamma, beta, rows, c, eps);

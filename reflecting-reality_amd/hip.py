@@ -138,6 +138,13 @@ class GroupNormDesc(C.Structure):
     ]
 
 
+class GnPlan(C.Structure):
+    """mf_gn_plan: what mf_groupnorm would do with a descriptor (mf_groupnorm_plan; decided on the host, nothing is launched).
+    form: 0 one-launch slab, 1 own statistics pass, 2 the producers' per-channel sums, 3 the producer's per-group sums."""
+    _fields_ = [(f, C.c_int32) for f in ("form launches vec finalize centered chunks rows_per_chunk rows_per_block blocks threads lds_bytes "
+                                         "finalize_parts").split()]
+
+
 SCHED_MAX_OPS, SCHED_MAX_TERMS, SCHED_MAX_REGS = 8, 6, 16       # include/mfhip.h MF_SCHED_MAX_*
 
 
@@ -163,11 +170,13 @@ class SchedRow(C.Structure):
 # load() turns the table into argtypes / restype, so ctypes converts plain Python values and refuses the wrong ones before the library
 # is entered; program.py derives the recorder's signatures from it; tests/test_abi.py checks it against the header's prototypes in full.
 # A new entry is its prototype in mfhip.h and its line here.
-DESC_KINDS = {"G": GemmDesc, "P": GemmPlan, "N": GroupNormDesc, "A": AttnBwdDesc, "W": WgradDesc, "Q": WgradPlan, "B": GroupNormBwdDesc}
+DESC_KINDS = {"G": GemmDesc, "P": GemmPlan, "N": GroupNormDesc, "A": AttnBwdDesc, "W": WgradDesc, "Q": WgradPlan, "B": GroupNormBwdDesc,
+              "R": GnPlan}
 SIGNATURES = {
     "mf_abi_version": "i:", "mf_last_error": "s:", "mf_sizeof_gemm_desc": "i:", "mf_sizeof_groupnorm_desc": "i:",
     "mf_gemm_conv": "i:Gp", "mf_gemm_conv_plan": "i:GP", "mf_sizeof_gemm_plan": "i:", "mf_gemm_num_tiles": "i:", "mf_gemm_tile_shape": "i:ipp",
     "mf_gemm_tile_table_version": "i:", "mf_groupnorm": "i:Np", "mf_groupnorm_ws_floats": "l:iii", "mf_groupnorm_slab_applies": "i:iii",
+    "mf_groupnorm_plan": "i:NR", "mf_sizeof_gn_plan": "i:",
     "mf_layernorm": "i:pipipplifp", "mf_softmax_rows": "i:ppiliip",
     "mf_attention_bf16": "i:plplplpliiiiifp", "mf_attention_f16": "i:plplplpliiiiifp",
     "mf_attention_f16x3": "i:pplpplpplpliiiiifp", "mf_attention_f16x3_lse": "i:pplpplpplplpiiiiifp", "mf_attention_causal_bf16": "i:plplplpliiiiifp",
@@ -233,7 +242,8 @@ EXPORTS = list(SIGNATURES)
 # (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
 _LAYOUTS = ((GemmDesc, "mf_sizeof_gemm_desc"), (GroupNormDesc, "mf_sizeof_groupnorm_desc"), (AttnBwdDesc, "mf_sizeof_attn_bwd_desc"),
             (WgradDesc, "mf_sizeof_wgrad_desc"), (GroupNormBwdDesc, "mf_sizeof_groupnorm_bwd_desc"), (SchedRow, "mf_sizeof_sched_row"),
-            (MetricsRow, "mf_sizeof_metrics_row"), (GemmPlan, "mf_sizeof_gemm_plan"), (WgradPlan, "mf_sizeof_wgrad_plan"))
+            (MetricsRow, "mf_sizeof_metrics_row"), (GemmPlan, "mf_sizeof_gemm_plan"), (WgradPlan, "mf_sizeof_wgrad_plan"),
+            (GnPlan, "mf_sizeof_gn_plan"))
 _CTYPES = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "s": C.c_char_p, "v": None,
            **{kind: C.POINTER(struct) for kind, struct in DESC_KINDS.items()}}
 
@@ -767,14 +777,10 @@ def gemm_conv(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, dtype, w_
     return out
 
 
-def groupnorm(x0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, groups: int, eps: float, silu: bool,
-              out_dtype: torch.dtype, x1: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-              stats_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x0/x1: NHWC [B, H, W, C] (or [B, HW, C]); returns the normalised tensor over cat([x0, x1], -1).  stats_out (fp32
-    [B, groups, 2], written): every group's (mean, rstd), which groupnorm_bwd takes as `stats`."""
-    pend = getattr(x0, "_sk_pending", None)
-    if pend is not None:
-        x0._sk_pending = None              # consumed here (x0 itself stays unwritten: nothing else may read it)
+def _groupnorm_desc(x0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, pend, *, groups: int, eps: float, silu: bool,
+                    out_dtype: torch.dtype, x1: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                    stats_out: Optional[torch.Tensor] = None):
+    """(descriptor, out) of groupnorm()'s one mf_groupnorm call; `pend`: the deferred split-K input taken off x0, or None."""
     _req_cuda(x0, x1, gamma, beta)
     b = x0.shape[0]
     c0 = x0.shape[-1]
@@ -812,8 +818,33 @@ def groupnorm(x0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, grou
                 d.part1, d.part1_rows = p1[0].data_ptr(), p1[1]
             if x1 is None and len(p0) > 2 and p0[2] == groups and GN_FROM_GROUPS:
                 d.grp0, d.grp0_rows = p0[0].data_ptr() + 4 * 2 * c0 * (b * hw // p0[1]), p0[1]
+    return d, out
+
+
+def groupnorm(x0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, groups: int, eps: float, silu: bool,
+              out_dtype: torch.dtype, x1: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+              stats_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x0/x1: NHWC [B, H, W, C] (or [B, HW, C]); returns the normalised tensor over cat([x0, x1], -1).  stats_out (fp32
+    [B, groups, 2], written): every group's (mean, rstd), which groupnorm_bwd takes as `stats`."""
+    pend = getattr(x0, "_sk_pending", None)
+    if pend is not None:
+        x0._sk_pending = None              # consumed here (x0 itself stays unwritten: nothing else may read it)
+    d, out = _groupnorm_desc(x0, gamma, beta, pend, groups=groups, eps=eps, silu=silu, out_dtype=out_dtype, x1=x1, out=out, stats_out=stats_out)
     _launch("mf_groupnorm", C.byref(d))
     return out
+
+
+def groupnorm_plan(x0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, **kw) -> GnPlan:
+    """What the library would do with exactly the call groupnorm(x0, gamma, beta, **kw) makes (mf_groupnorm_plan: nothing is launched) —
+    the producer's sums and a deferred split-K input attached to x0 / x1 included, and left attached."""
+    pend, x0._sk_pending = getattr(x0, "_sk_pending", None), None
+    try:
+        d, _ = _groupnorm_desc(x0, gamma, beta, pend, **kw)
+    finally:
+        x0._sk_pending = pend
+    plan = GnPlan()
+    _check(load().mf_groupnorm_plan(C.byref(d), C.byref(plan)), "mf_groupnorm_plan")
+    return plan
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out_dtype: torch.dtype

@@ -1,7 +1,7 @@
 """Parser of the prototypes of include/mfhip.h, shared by the ABI tests (a plain helper module, like gemm_ref.py).
 
 Kinds: 'p' pointer, 'i' int / int32_t, 'l' int64_t, 'f' float; a return may also be 's' (const char*) or 'v' (void).  A pointer to one of
-the host descriptor structs (mf_*_desc, and mf_gemm_plan / mf_wgrad_plan, which the library fills) is given as the struct's C name instead of 'p';
+the host descriptor structs (mf_*_desc, and mf_gemm_plan / mf_wgrad_plan / mf_gn_plan, which the library fills) is given as the struct's C name instead of 'p';
 mf_sched_row and mf_program are not descriptors (the first lives in device memory, the second is opaque)."""
 import os
 import re
@@ -24,7 +24,7 @@ def declared_names(path: str = HEADER) -> list:
 def _param_kind(decl: str) -> str:
     words = decl.replace("*", " * ").split()
     if "*" in words:
-        desc = [w for w in words if re.fullmatch(r"mf_\w+_desc|mf_gemm_plan|mf_wgrad_plan", w)]
+        desc = [w for w in words if re.fullmatch(r"mf_\w+_desc|mf_gemm_plan|mf_wgrad_plan|mf_gn_plan", w)]
         return desc[0] if desc else "p"
     scalar = [w for w in words if w != "const"]
     if not scalar or scalar[0] not in _SCALARS:

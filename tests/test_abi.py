@@ -10,7 +10,8 @@ from reflecting_reality_amd import _build, hip
 
 # the host descriptor structs of the header and their ctypes mirrors
 DESCRIPTORS = {"mf_gemm_desc": hip.GemmDesc, "mf_gemm_plan": hip.GemmPlan, "mf_groupnorm_desc": hip.GroupNormDesc, "mf_attn_bwd_desc": hip.AttnBwdDesc,
-               "mf_wgrad_desc": hip.WgradDesc, "mf_wgrad_plan": hip.WgradPlan, "mf_groupnorm_bwd_desc": hip.GroupNormBwdDesc}
+               "mf_wgrad_desc": hip.WgradDesc, "mf_wgrad_plan": hip.WgradPlan, "mf_groupnorm_bwd_desc": hip.GroupNormBwdDesc,
+               "mf_gn_plan": hip.GnPlan}
 CTYPES = {"p": ctypes.c_void_p, "i": ctypes.c_int32, "l": ctypes.c_int64, "f": ctypes.c_float, "s": ctypes.c_char_p, "v": None}
 
 

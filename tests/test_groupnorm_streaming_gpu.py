@@ -146,6 +146,7 @@ def test_slab_deferred_split_k_input(hw, splits, terms, dt):
     for _ in range(2):
         x = torch.empty(b, hw, c, device=DEV, dtype=dt)          # comes back unwritten from the producing GEMM
         x._sk_pending = (ws, splits, bias, temb, c, alpha)
+        assert hip.groupnorm_plan(x, gamma, beta, groups=32, eps=1e-5, silu=True, out_dtype=dt).form == 0
         z = hip.groupnorm(x, gamma, beta, groups=32, eps=1e-5, silu=True, out_dtype=dt)
         assert x._sk_pending is None
         assert torch.equal(z, z_ref), f"deferred reduce differs from reduce + GroupNorm by {(z.float() - z_ref.float()).abs().max()}"

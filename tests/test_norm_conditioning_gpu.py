@@ -54,22 +54,29 @@ ROUTES = {
 ROUTE_SHAPES = [(r, i) for r, shapes in ROUTES.items() for i in range(len(shapes))]
 
 
-def on_route(route, c, hw, groups):
-    """The path is checked, not assumed."""
-    assert hip.gn_slab_applies(hw, c, groups) == (route == "slab"), (route, c, hw)
-    if route == "vec4":
-        assert c % 8 == 4
-    if route == "separate":
-        assert hw > 1024
-    if route == "fused":
-        assert 256 < hw <= 1024
+# what the library's plan of a call says on each route (hip.GnPlan)
+PLAN_OF_ROUTE = {
+    "slab": dict(form=0, launches=1, vec=8),
+    "fused": dict(form=1, finalize=1, launches=2, vec=8),
+    "separate": dict(form=1, finalize=0, launches=3, vec=8),
+    "vec4": dict(form=1, vec=4),
+}
 
 
-def gn_run(x, c0, gamma, beta, groups, silu, out_dt, **kw):
-    """x [B, HW, C] on the host, split into the segments (c0, C - c0); a repeated launch must give the same bits."""
+def on_route(route, x0, gamma, beta, **call):
+    """The path is checked, not assumed: the library's own plan of the very call hip.groupnorm makes of these arguments."""
+    plan = hip.groupnorm_plan(x0, gamma, beta, **call)
+    got = {field: getattr(plan, field) for field in PLAN_OF_ROUTE[route]}
+    assert got == PLAN_OF_ROUTE[route], (route, tuple(x0.shape), {f: getattr(plan, f) for f, _ in hip.GnPlan._fields_})
+    assert hip.gn_slab_applies(x0.shape[1], x0.shape[2] + (call["x1"].shape[2] if call.get("x1") is not None else 0), call["groups"]) == (route == "slab")
+
+
+def gn_run(x, c0, gamma, beta, groups, silu, out_dt, route, **kw):
+    """x [B, HW, C] on the host, split into the segments (c0, C - c0), on `route`; a repeated launch must give the same bits."""
     x0 = x[..., :c0].contiguous().to(DEV)
     x1 = x[..., c0:].contiguous().to(DEV) if c0 < x.shape[-1] else None
     ga, be = gamma.to(DEV), beta.to(DEV)
+    on_route(route, x0, ga, be, groups=groups, eps=R.EPS, silu=silu, out_dtype=out_dt, x1=x1, **kw)
     y = hip.groupnorm(x0, ga, be, groups=groups, eps=R.EPS, silu=silu, out_dtype=out_dt, x1=x1, **kw)
     y2 = hip.groupnorm(x0, ga, be, groups=groups, eps=R.EPS, silu=silu, out_dtype=out_dt, x1=x1, **kw)
     assert torch.equal(y, y2), "a repeated launch gave other bits"
@@ -81,12 +88,11 @@ def gn_run(x, c0, gamma, beta, groups, silu, out_dt, **kw):
 @pytest.mark.parametrize("route,which", ROUTE_SHAPES)
 def test_groupnorm_forward(route, which, rung, silu):
     c0, c1, hw, groups = ROUTES[route][which]
-    on_route(route, c0 + c1, hw, groups)
     for in_dt, out_dt in (PAIRS if which == 0 else SAME):
         if rung not in R.ladder(in_dt):
             continue
         x, gamma, beta, ref, yard = R.gn_case(rung, B, hw, c0 + c1, groups, in_dt, 11, silu)
-        y = gn_run(x, c0, gamma, beta, groups, silu, out_dt)
+        y = gn_run(x, c0, gamma, beta, groups, silu, out_dt, route)
         R.judge(f"groupnorm {route}[{c0}+{c1},{hw}] {rung} {in_dt}->{out_dt} silu={silu}", y, ref[0], yard[0], *GN_TOL[out_dt])
 
 
@@ -100,7 +106,7 @@ def test_groupnorm_stats_out(route, which, rung, in_dt):
     c0, c1, hw, groups = ROUTES[route][which]
     x, gamma, beta, ref, yard = R.gn_case(rung, B, hw, c0 + c1, groups, in_dt, 11, True)
     st = torch.zeros(B, groups, 2, device=DEV)
-    gn_run(x, c0, gamma, beta, groups, True, in_dt, stats_out=st)
+    gn_run(x, c0, gamma, beta, groups, True, in_dt, route, stats_out=st)
     for k, what in ((0, "mean"), (1, "rstd")):
         R.judge(f"stats_out {what} {route}[{c0}+{c1},{hw}] {rung} {in_dt}", st[..., k], ref[1 + k], yard[1 + k], *GN_TOL[F32])
 
@@ -136,6 +142,8 @@ def test_groupnorm_slab_deferred_split_k(hw, splits, terms, rung, dt):
     for _ in range(2):
         xin = torch.empty(B, hw, c, device=DEV, dtype=dt)          # comes back unwritten from the producing GEMM
         xin._sk_pending = (ws, splits, bias, temb, c, alpha)
+        plan = hip.groupnorm_plan(xin, ga, be, groups=groups, eps=R.EPS, silu=True, out_dtype=dt)
+        assert plan.form == 0 and plan.launches == 1 and xin._sk_pending is not None
         z = hip.groupnorm(xin, ga, be, groups=groups, eps=R.EPS, silu=True, out_dtype=dt)
         assert xin._sk_pending is None
         assert torch.equal(z, z_ref), f"deferred reduce differs from reduce + GroupNorm by {(z.float() - z_ref.float()).abs().max()}"
@@ -158,9 +166,9 @@ def test_a_well_conditioned_image_keeps_its_bits_beside_an_ill_conditioned_one(r
     x_base = R.gn_input("base", B, hw, c, groups, dt, 14)
     assert torch.equal(x_mix[0], x_base[0]) and torch.equal(x_mix[2], x_base[2]) and not torch.equal(x_mix[1], x_base[1])
     gamma, beta = R.params(c, 14)
-    y_mix, y_base = gn_run(x_mix, c0, gamma, beta, groups, True, dt), gn_run(x_base, c0, gamma, beta, groups, True, dt)
+    y_mix, y_base = gn_run(x_mix, c0, gamma, beta, groups, True, dt, route), gn_run(x_base, c0, gamma, beta, groups, True, dt, route)
     assert torch.equal(y_mix[0], y_base[0]) and torch.equal(y_mix[2], y_base[2]), "an image depends on its neighbour"
-    y_one = gn_run(x_mix[1:2].contiguous(), c0, gamma, beta, groups, True, dt)
+    y_one = gn_run(x_mix[1:2].contiguous(), c0, gamma, beta, groups, True, dt, route)
     assert torch.equal(y_mix[1:2], y_one), "an image depends on its place in the batch"
     ref, yard = R._gn(x_mix, gamma, beta, groups, True, torch.float64), R._gn(x_mix, gamma, beta, groups, True, F32)
     R.judge(f"mixed batch {route}[{c0}+{c1},{hw}] base|{rung}|base {dt}", y_mix, ref[0], yard[0], *GN_TOL[dt])
@@ -200,6 +208,8 @@ def test_groupnorm_from_handed_over_sums(dt, rung):
                               ("grp0", (torch.cat([chan.reshape(-1), grp.reshape(-1)]).contiguous(), rows, groups),
                                grp.double().view(B, -1, groups, 2).sum(1))):
         xd._gn_part = part
+        plan = hip.groupnorm_plan(xd, ga, be, groups=groups, eps=R.EPS, silu=True, out_dtype=dt)
+        assert (plan.form, plan.launches) == {"part0": (2, 2), "grp0": (3, 1)}[route], (route, plan.form, plan.launches)
         y = hip.groupnorm(xd, ga, be, groups=groups, eps=R.EPS, silu=True, out_dtype=dt)
         y2 = hip.groupnorm(xd, ga, be, groups=groups, eps=R.EPS, silu=True, out_dtype=dt)
         del xd._gn_part

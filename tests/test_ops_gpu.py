@@ -1019,6 +1019,7 @@ def test_split_k_reduce_deferred_to_the_groupnorm_is_bit_identical(prec_name, hw
     assert y._sk_pending is not None and y._sk_pending[1] >= 2, "the forced split-K launch should have left its reduce"
     with pytest.raises(hip.MfhipError, match="deferred"):
         hip.add(y, y, prec.act)
+    assert hip.groupnorm_plan(y, *norm, groups=32, eps=1e-5, silu=True, out_dtype=prec.act).form == 0 and y._sk_pending is not None
     z = ops.groupnorm(y, norm, groups=32, eps=1e-5, silu=True, out_dtype=prec.act)
     assert y._sk_pending is None
     assert torch.equal(z, z_ref), f"deferred reduce differs from reduce + GroupNorm by {(z.float() - z_ref.float()).abs().max()}"
@@ -1064,6 +1065,8 @@ def test_groupnorm_from_producer_group_sums_is_one_launch(dt, c, hw, rows, silu)
     chan = torch.stack([v.sum(1), (v * v).sum(1)], dim=-1)                               # [blocks, c, 2]
     grp = chan.view(-1, groups, c // groups, 2).sum(2)                                   # [blocks, groups, 2]
     x._gn_part = (torch.cat([chan.reshape(-1), grp.reshape(-1)]).contiguous(), rows, groups)
+    plan = hip.groupnorm_plan(x, gamma, beta, groups=groups, eps=1e-5, silu=silu, out_dtype=dt)
+    assert plan.launches == 1 and plan.form == 3, (plan.launches, plan.form)
     y = hip.groupnorm(x, gamma, beta, groups=groups, eps=1e-5, silu=silu, out_dtype=dt)
     y2 = hip.groupnorm(x, gamma, beta, groups=groups, eps=1e-5, silu=silu, out_dtype=dt)
     assert torch.equal(y, y2)
@@ -1096,6 +1099,7 @@ def test_groupnorm_from_producer_partial_sums(dt, c0, c1, hw, silu):
     x0._gn_part = parts(x0, 256)
     if x1 is not None:
         x1._gn_part = parts(x1, 128)
+    assert hip.groupnorm_plan(x0, gamma, beta, groups=groups, eps=1e-5, silu=silu, out_dtype=dt, x1=x1).form == 2
     y = hip.groupnorm(x0, gamma, beta, groups=groups, eps=1e-5, silu=silu, out_dtype=dt, x1=x1)
     y2 = hip.groupnorm(x0, gamma, beta, groups=groups, eps=1e-5, silu=silu, out_dtype=dt, x1=x1)
     assert torch.equal(y, y2)

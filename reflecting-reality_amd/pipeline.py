@@ -30,7 +30,8 @@ import torch
 from . import hip
 from .models import AutoencoderKL, BrushNetModel, UNet2DConditionModel
 from .rng import PhiloxGenerator, is_philox, randn_tensor
-from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, UniPCMultistepScheduler, device_plan
+from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, PNDMScheduler,
+                         UniPCMultistepScheduler, device_plan)
 
 try:
     import PIL.Image
@@ -124,6 +125,9 @@ class VaeImageProcessor:
 # `eager`: a step of the eager loop.  For the captured step: `key` is the form's part of the graph-cache key, `attach` puts its static
 # buffers into the kept state, `load(i)` is the per-step copy before a replay, `launch` ends one_step, `after_replay` / `finish` are the
 # host's part, `export` gives a step program its io buffers and tables, and `result` is its meta's sentence about what a run leaves.
+# `sample(lat)` is the sample after a step, what a callback_on_step_end sees and the loop returns; `replace(new, lat)` goes on with the
+# callback's own.  Both are `lat` itself except under the Euler family, where `lat` holds the MODEL INPUT of the step about to run
+# (sample / sqrt(sigma^2 + 1)) and the sample is the update object's own: a slot of the plan's state, or a tensor of _HostStep.
 class _FusedDDIM:
     """DDIM with eta == 0 and no rescale: classifier-free guidance and the update are one kernel, reading the step's four
     coefficients from a row of a [steps, 4] table."""
@@ -144,6 +148,8 @@ class _FusedDDIM:
     def load(self, i): self.coef_cur.copy_(self.coefs[i])
     def launch(self, eu, ec, lat): hip.cfg_ddim_step_dev(eu, ec, self.g, lat, self.coef_cur, self.ptype, self.clip, out=lat)
     def after_replay(self, t, lat): pass
+    def sample(self, lat): return lat
+    def replace(self, new, lat): lat.copy_(new)
     def finish(self): pass
     def export(self): return dict(coef4=self.coef_cur), {"table.coef4": self.coefs.contiguous()}
 
@@ -152,7 +158,9 @@ class _DevicePlan:
     """PNDM / UniPC / DPM-Solver++ inside the captured step: mf_sched_step_dev runs the step's row of schedulers.device_plan (a trace of
     their own step()) on a state buffer that keeps their history; the scheduler gets its end state from it after the loop.  A plan that
     reads a step's noise (DPM-Solver++ SDE) takes a rng.PhiloxGenerator: mf_sched_step_noise_dev draws the noise in the kernel from the
-    generator's device state and mf_philox_advance moves that state, both inside the graph; the host pair follows per replayed step."""
+    generator's device state and mf_philox_advance moves that state, both inside the graph; the host pair follows per replayed step.
+    Euler / Euler-ancestral: the plan keeps the sample in slot `plan.x_slot` and every row ends by writing the next step's model input
+    into the latents; attach() starts the run (x0 into the slot, x0 * plan.first_scale into the latents: one launch)."""
 
     def __init__(self, pipe, g, nsteps, generator=None):
         self.sched, self.g = pipe.scheduler, float(g)
@@ -170,6 +178,11 @@ class _DevicePlan:
             self.rng_state = generator.device_state()
             self.key += (self.plan.noise_reg, self.rng_state.data_ptr())
             self.result = f"latents ({name} update inside: mf_sched_step_noise_dev + mf_philox_advance; history in sched_state)"
+        if self.plan.x_slot >= 0:
+            self.key += ("x", self.plan.x_slot)
+            self.result = self.result[:-1] + f"; latents hold the model input, sched_state slot {self.plan.x_slot} the sample)"
+            # a host starts a run with x0 in that slot and x0 * first_input_scale in latents
+            self.meta = dict(sample_slot=self.plan.x_slot, first_input_scale=float(self.plan.first_scale))
 
     def attach(self, st, lat, ts):
         if "state" not in st:                     # the step's mf_sched_row, and the scheduler's history (persists between steps)
@@ -179,9 +192,14 @@ class _DevicePlan:
         if self.gen is not None:
             self.per = lat[0].numel()
             self.blocks = hip.philox_normal_blocks(lat.shape[0], self.per)           # what one step's draw consumes
-            self.meta = dict(philox=dict(per_sample=self.per, first_sample=0, global_batch=int(lat.shape[0]), blocks_per_step=self.blocks,
-                                         noise_reg=self.plan.noise_reg))
+            self.meta = dict(self.meta, philox=dict(per_sample=self.per, first_sample=0, global_batch=int(lat.shape[0]),
+                                                    blocks_per_step=self.blocks, noise_reg=self.plan.noise_reg))
             self.rng_state = self.gen.device_state()       # (level with the host pair again: prepare_latents drew since __init__)
+        self.x = None
+        if self.plan.x_slot >= 0:
+            self.x = self.state[self.plan.x_slot].copy_(lat)
+            hip.axpby_n([self.x], [self.plan.first_scale], out=lat)
+            self.sched.model_input_prescaled = True          # (scale_model_input inside the step body: the identity; finish() clears it)
 
     def load(self, i): self.row_cur.copy_(self.rows[i])
 
@@ -195,6 +213,14 @@ class _DevicePlan:
     def after_replay(self, t, lat):
         if self.gen is not None:
             self.gen.note_advanced(self.blocks, on_device=True)
+
+    def sample(self, lat): return lat if self.x is None else self.x
+
+    def replace(self, new, lat):
+        if self.x is None:
+            lat.copy_(new)
+        else:
+            raise hip.MfhipError("a device plan of the Euler family steps without a callback_on_step_end")
 
     def finish(self): self.plan.finish(self.sched, self.state)    # the counters and history the host's step() would have left
 
@@ -217,6 +243,7 @@ class _HostStep:
         params = inspect.signature(pipe.scheduler.step).parameters
         self.extra = {k: v for k, v in (("eta", eta), ("generator", generator)) if k in params}
         self.key = (type(pipe.scheduler).__name__, "host")
+        self.scaled, self.x = bool(getattr(pipe.scheduler, "scales_model_input", False)), None
 
     def eager(self, eu, ec, t, latents):
         noise_pred = eu if ec is None else hip.cfg_combine(eu, ec, self.g)                          # :1310-1312
@@ -228,12 +255,37 @@ class _HostStep:
             noise_pred = (r * (noise_pred.float() * (std_text / std_cfg)) + (1.0 - r) * noise_pred.float()).to(noise_pred.dtype)
         return self.pipe._sched_step(noise_pred, t, latents, self.extra)
 
-    def attach(self, st, lat, ts): self.eps = st.setdefault("eps", torch.empty_like(lat))
+    def attach(self, st, lat, ts):
+        self.eps = st.setdefault("eps", torch.empty_like(lat))
+        if self.scaled:                           # Euler family: the sample is this object's, `lat` gets the first step's model input
+            sched = self.pipe.scheduler
+            self.x = lat.clone()
+            hip.axpby_n([self.x], [sched._input_scale(sched.index_for_timestep(ts[0]) if sched.begin_index is None else sched.begin_index)],
+                        out=lat)
+            sched.model_input_prescaled = True    # (scale_model_input inside the step body: the identity; finish() clears it)
+
     def load(self, i): pass
     def launch(self, eu, ec, lat): self.eps.copy_(hip.cfg_combine(eu, ec, self.g))                  # :1310-1312
+
     # (multistep schedulers keep references to their inputs (ets, last_sample): hand them copies, not the graph's static buffers)
-    def after_replay(self, t, lat): lat.copy_(self.pipe._sched_step(self.eps.clone(), t, lat.clone(), self.extra))    # :1315
-    def finish(self): pass
+    def after_replay(self, t, lat):
+        if self.scaled:
+            self.replace(self.pipe._sched_step(self.eps.clone(), t, self.x, self.extra), lat)
+        else:
+            lat.copy_(self.pipe._sched_step(self.eps.clone(), t, lat.clone(), self.extra))          # :1315
+
+    def sample(self, lat): return self.x if self.scaled else lat
+
+    def replace(self, new, lat):
+        if self.scaled:                           # the sample, and the model input of the step that follows
+            self.x = new
+            hip.axpby_n([new.contiguous()], [self.pipe.scheduler._input_scale(self.pipe.scheduler.step_index)], out=lat)
+        else:
+            lat.copy_(new)
+
+    def finish(self):
+        if self.scaled:
+            self.pipe.scheduler.model_input_prescaled = False
     def export(self): return dict(eps=self.eps), {}
 
 
@@ -293,7 +345,8 @@ class StableDiffusionBrushNetPipeline:
         self.normal_embedder = None      # 'ip_adapter' normals mode: a frontend.NormalEmbedder turns `normals=` [B, 1, 3] into the ip token
 
     # ---- loading / saving (pipelines/pipeline_utils.py:148-296 save_pretrained, :465-919 from_pretrained) ---------
-    _scheduler_classes = ("DDIMScheduler", "PNDMScheduler", "UniPCMultistepScheduler", "DPMSolverMultistepScheduler")
+    _scheduler_classes = ("DDIMScheduler", "PNDMScheduler", "UniPCMultistepScheduler", "DPMSolverMultistepScheduler",
+                          "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler")
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, torch_dtype=None, device="cuda", **kwargs):
@@ -341,6 +394,11 @@ class StableDiffusionBrushNetPipeline:
                 CLIPTokenizer = None
             if CLIPTokenizer is not None:
                 tokenizer = CLIPTokenizer.from_pretrained(root, subfolder="tokenizer")
+        return cls._assemble(root, mods, sched, text_encoder, tokenizer, torch_dtype, device, kwargs)
+
+    @classmethod
+    def _assemble(cls, root, mods, sched, text_encoder, tokenizer, torch_dtype, device, kwargs):
+        """from_pretrained's last step: the constructor call (the XL subclass has another constructor)."""
         return cls(vae=mods["vae"], text_encoder=text_encoder, tokenizer=tokenizer,
                    unet=mods["unet"], brushnet=mods["brushnet"], scheduler=sched, safety_checker=None,
                    feature_extractor=kwargs.pop("feature_extractor", None),
@@ -732,15 +790,17 @@ class StableDiffusionBrushNetPipeline:
         fused_ddim = do_cfg and isinstance(self.scheduler, DDIMScheduler) and eta == 0.0 and rescale == 0.0
         use_graph = (self.use_hip_graph and do_cfg and callback is None and (fused_ddim or eta == 0.0) and rescale == 0.0
                      and all(k == 1.0 for k in keep) and len(ts) > 2 and not guess_mode)
-        # THE place that decides how a step ends.  PNDM / UniPC / DPM-Solver++ update on the device (one plan row per step) unless a
-        # callback may read the scheduler between steps, or an eps-form step program is being exported; the eager loop always steps them
-        # on the host.  The SDE type of DPM-Solver++ draws noise at every step: on the device only from ONE rng.PhiloxGenerator (the
-        # library's stream, which the kernel can draw); a torch.Generator, none, or a list of generators steps on the host.
-        sde = isinstance(self.scheduler, DPMSolverMultistepScheduler) and self.scheduler.config["algorithm_type"] == "sde-dpmsolver++"
+        # THE place that decides how a step ends.  PNDM / UniPC / DPM-Solver++ / Euler update on the device (one plan row per step) unless
+        # a callback may read the scheduler between steps, or an eps-form step program is being exported; the eager loop always steps them
+        # on the host.  The SDE type of DPM-Solver++ and Euler-ancestral draw noise at every step: on the device only from ONE
+        # rng.PhiloxGenerator (the library's stream, which the kernel can draw); a torch.Generator, none, or a list of generators steps on
+        # the host.
+        sde = isinstance(self.scheduler, EulerAncestralDiscreteScheduler) or (
+            isinstance(self.scheduler, DPMSolverMultistepScheduler) and self.scheduler.config["algorithm_type"] == "sde-dpmsolver++")
         if fused_ddim:
             update = _FusedDDIM(self, guidance_scale)
         elif (use_graph and callback_on_step_end is None and not (_export is not None and _export["scheduler"] == "host")
-              and isinstance(self.scheduler, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler))
+              and isinstance(self.scheduler, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler))
               and (not sde or isinstance(generator, PhiloxGenerator))):
             update = _DevicePlan(self, guidance_scale, len(ts), generator if sde else None)
         else:
@@ -959,12 +1019,13 @@ class StableDiffusionBrushNetPipeline:
                         one_step, export, update, st, lat, temb_u, temb_b, cond, len(ts), i, guidance_scale, cond_scale, once)
                 st["graph"].replay()
             update.after_replay(ts[i], lat)
-            new = step_end(i, ts[i], lat)
-            if new is not lat:
-                lat.copy_(new)
+            cur = update.sample(lat)
+            new = step_end(i, ts[i], cur)
+            if new is not cur:
+                update.replace(new, lat)
             bar.update()
         update.finish()
-        return lat.clone()
+        return update.sample(lat).clone()
 
     def _capture(self, one_step, rec=None):
         """Capture one_step() into a hipGraph (nothing executes) and return it.  `rec`: a program.Recorder(capture=True) that ALSO
@@ -1018,21 +1079,25 @@ class StableDiffusionBrushNetPipeline:
         """Run the pipeline once and write the denoise step's program to `path` (see program.py / include/mfhip.h "step programs").
         `call_kwargs`: what __call__ takes; the program is specialised on their shapes, the prompt (its cross-attention K / V^T are
         constants of the file), the guidance and conditioning scales, and the schedule (its tables travel as named constants).
-        `scheduler` (PNDM, UniPC): "host" ends the step with the guided noise prediction in the io buffer "eps" for the host's own
+        `scheduler` (PNDM, UniPC, DPM-Solver++, Euler): "host" ends the step with the guided noise prediction in the io buffer "eps" for the host's own
         scheduler; "device" records the update too (mf_sched_step_dev: io buffers "sched_row" / "sched_state", table "table.sched_row"),
         so that mf_denoise_step_fused alone runs a whole step.  DDIM's update is inside either way.  DPM-Solver++ exports like UniPC; its SDE
         type needs generator=rng.PhiloxGenerator(seed) for "device" (mf_sched_step_noise_dev + mf_philox_advance on the io buffer
-        "philox_state", the generator's device pair; meta["philox"] holds per_sample, global_batch and the blocks a step consumes)."""
+        "philox_state", the generator's device pair; meta["philox"] holds per_sample, global_batch and the blocks a step consumes).  Euler and
+        Euler-ancestral (the latter like the SDE type) keep the sample in slot meta["sample_slot"] of "sched_state" and the model input in
+        "latents": a host starts a run by writing x0 (noise * init_noise_sigma) into that slot and x0 * meta["first_input_scale"] into
+        "latents"; after the last step of a full schedule the two are equal."""
         if self.device.type != "cuda":
             raise hip.MfhipError("export_denoise_step needs the device: a program is a recording of real launches")
         if scheduler not in ("host", "device"):
             raise ValueError(f"export_denoise_step: scheduler must be 'host' or 'device', not {scheduler!r}")
         if scheduler == "device" and not isinstance(self.scheduler, (DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler,
-                                                                     DPMSolverMultistepScheduler)):
+                                                                     DPMSolverMultistepScheduler, EulerDiscreteScheduler)):
             raise NotImplementedError(f"{type(self.scheduler).__name__} has no device update")
-        if (scheduler == "device" and getattr(self.scheduler, "config", {}).get("algorithm_type") == "sde-dpmsolver++"
-                and not isinstance(call_kwargs.get("generator"), PhiloxGenerator)):
-            raise NotImplementedError("a step program of the DPM-Solver++ SDE update draws its noise in the kernel: pass "
+        if (scheduler == "device" and not isinstance(call_kwargs.get("generator"), PhiloxGenerator)
+                and (getattr(self.scheduler, "config", {}).get("algorithm_type") == "sde-dpmsolver++"
+                     or isinstance(self.scheduler, EulerAncestralDiscreteScheduler))):
+            raise NotImplementedError("a step program of the DPM-Solver++ SDE / Euler-ancestral update draws its noise in the kernel: pass "
                                       "generator=rng.PhiloxGenerator(seed), or export with scheduler='host'")
         from . import program
         program.refuse_ip_processors(self.unet)      # before anything is captured (the recorder would refuse in the middle of a two-stream capture)
@@ -1123,6 +1188,9 @@ class StableDiffusionBrushNetPipeline:
         file decoding and random numbers stay the caller's).  examples/c_host/inpaint_host.c runs the directory without Python."""
         from . import program
         from .text_encoder import CLIPTextModel
+        if isinstance(self.scheduler, EulerDiscreteScheduler):       # before any file is written
+            raise NotImplementedError(f"export_call under {type(self.scheduler).__name__}: the exported call's host loop feeds the sample "
+                                      "to the step, the Euler family's step reads the scaled model input (export_denoise_step carries it)")
         program.refuse_ip_processors(self.unet)
         if type(self) is not StableDiffusionBrushNetPipeline:
             raise NotImplementedError("export_call is built for the SD1.5 pipeline (SDXL's pooled text embedding feeds export-time tables)")
@@ -1198,6 +1266,19 @@ class StableDiffusionXLBrushNetPipeline(StableDiffusionBrushNetPipeline):
             raise NotImplementedError("the invisible watermark is outside the accelerated path")
         self.text_encoder_2, self.tokenizer_2 = text_encoder_2, tokenizer_2
         self.config.update(force_zeros_for_empty_prompt=force_zeros_for_empty_prompt)
+
+    @classmethod
+    def _assemble(cls, root, mods, sched, text_encoder, tokenizer, torch_dtype, device, kwargs):
+        """`text_encoder_2/` goes into the HIP CLIPTextModelWithProjection when the folder exists and none was passed; `tokenizer_2`
+        stays the caller's object."""
+        text_encoder_2 = kwargs.pop("text_encoder_2", None)
+        if text_encoder_2 is None and os.path.isdir(os.path.join(root, "text_encoder_2")):
+            from .text_encoder import CLIPTextModelWithProjection
+            text_encoder_2 = CLIPTextModelWithProjection.from_pretrained(root, subfolder="text_encoder_2", torch_dtype=torch_dtype, device=device)
+        return cls(vae=mods["vae"], text_encoder=text_encoder, text_encoder_2=text_encoder_2, tokenizer=tokenizer,
+                   tokenizer_2=kwargs.pop("tokenizer_2", None), unet=mods["unet"], brushnet=mods["brushnet"], scheduler=sched,
+                   force_zeros_for_empty_prompt=kwargs.pop("force_zeros_for_empty_prompt", True),
+                   feature_extractor=kwargs.pop("feature_extractor", None))
 
     def _get_add_time_ids(self, original_size, crops_coords_top_left, target_size, text_encoder_projection_dim):
         """pipeline_brushnet_sd_xl.py:_get_add_time_ids, including its consistency check against add_embedding."""

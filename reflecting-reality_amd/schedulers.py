@@ -5,12 +5,15 @@ add_noise :473-497) and scheduling_pndm.py (set_timesteps :168-226, step_prk :26
 _get_prev_sample :407-448).  The scalar coefficients are computed on the host exactly like the reference
 does (fp32 0-dim tensor arithmetic on the alphas_cumprod table); the per-element update is one HIP kernel
 (mf_cfg_ddim_step / mf_axpby_n).  Latents stay fp32 whatever the model precision.  device_plan (end of the file) turns a PNDM /
-UniPC / DPM-Solver++ schedule into rows for mf_sched_step_dev, the whole update of a step in one launch with device-resident coefficients.
+UniPC / DPM-Solver++ / Euler schedule into rows for mf_sched_step_dev, the whole update of a step in one launch with device-resident coefficients.
+EulerDiscreteScheduler / EulerAncestralDiscreteScheduler (scheduling_euler_discrete.py, scheduling_euler_ancestral_discrete.py) are the two
+classes whose scale_model_input is not the identity: their plans keep the sample in a state slot and write the model input to the latents.
 """
 from __future__ import annotations
 
 import copy
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import List, Optional, Tuple, Union
 
@@ -723,6 +726,192 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         raise NotImplementedError("DPMSolverMultistepScheduler.add_noise is only used by training / image-to-image (SURVEY.md §8 f-2)")
 
 
+class EulerDiscreteScheduler(_SchedulerBase):
+    """schedulers/scheduling_euler_discrete.py (Karras et al. 2022, algorithm 2 without churn).  The sample x lives at the sigma scale
+    (init_noise_sigma :242-248), the model reads x / sqrt(sigma_i^2 + 1) (scale_model_input :275-299), and a step (:436-546) is linear
+    in {sample, model output}: the host folds the data prediction and the derivative into two coefficients per step, evaluated in double
+    on the fp32 sigma table (dt as the reference's fp32 difference) and rounded once, so a step is ONE mf_axpby_n launch.  Timesteps are
+    float32, fractional under `linspace` spacing and Karras sigmas.  The reference draws a noise tensor it only uses under s_churn > 0
+    (:505); this class draws nothing, so a torch.Generator handed to step() ends in another state than the reference's.
+
+    `model_input_prescaled`: set by the pipeline's captured denoise step, whose static latents buffer already holds the model input
+    (the per-step factor travels with the scheduler update, never as a constant of the capture); scale_model_input is then the identity.
+    set_timesteps clears it."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     prediction_type="epsilon", interpolation_type="linear", use_karras_sigmas=False, sigma_min=None, sigma_max=None,
+                     timestep_spacing="linspace", timestep_type="discrete", steps_offset=0, rescale_betas_zero_snr=False)
+    _prediction_types = ("epsilon", "v_prediction", "sample")
+    scales_model_input = True
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        c = self.config
+        if c.get("rescale_betas_zero_snr"):
+            raise NotImplementedError("rescale_betas_zero_snr is outside the MirrorFusion path")
+        if c.get("interpolation_type", "linear") != "linear":
+            raise NotImplementedError(f"interpolation_type {c['interpolation_type']!r} is not built: 'linear' is")
+        if c.get("timestep_type", "discrete") != "discrete":
+            raise NotImplementedError(f"timestep_type {c['timestep_type']!r} is not built: 'discrete' is")
+        for key in ("sigma_min", "sigma_max"):
+            if c.get(key) is not None:
+                raise NotImplementedError(f"{key} is not built: Karras sigmas span the schedule's own range")
+        if c["prediction_type"] == "original_sample":
+            raise NotImplementedError("prediction_type 'original_sample' (the deprecated name of 'sample')")
+        if c["prediction_type"] not in self._prediction_types:
+            if c["prediction_type"] == "sample":
+                raise NotImplementedError("prediction_type not implemented yet: sample")
+            raise ValueError(f"prediction_type given as {c['prediction_type']} must be one of `epsilon`, or `v_prediction`")
+        self.sigmas = torch.from_numpy(np.concatenate([self._sigma_table()[::-1], np.zeros(1, dtype=np.float32)]))
+        self.timesteps = torch.from_numpy(np.linspace(0, c["num_train_timesteps"] - 1, c["num_train_timesteps"], dtype=float)[::-1].copy()
+                                          ).to(torch.float32)
+        self.init_noise_sigma = self._init_noise_sigma()
+        self.model_input_prescaled = False
+        self._step_index = None
+        self._begin_index = None
+
+    def _sigma_table(self) -> np.ndarray:
+        """sqrt((1 - alphas_cumprod) / alphas_cumprod), fp32.  The schedule's scalars (this table, init_noise_sigma, the model-input
+        factors, the ancestral sigma_up / sigma_down) are numpy float32 arithmetic with np.sqrt where the reference writes torch's
+        `** 0.5`: +, -, *, / and sqrt are correctly rounded on every machine, torch's vectorised float32 math is not on every CPU (where
+        it is, the two agree bit for bit), and the ancestral sigma_down is a difference that amplifies a last-bit change a hundredfold."""
+        a = self.alphas_cumprod.numpy()
+        return np.sqrt((1 - a) / a)
+
+    def _init_noise_sigma(self) -> float:
+        """:242-248: the largest sigma, or sqrt(sigma_max^2 + 1) under `leading` spacing (fp32 arithmetic, as there)."""
+        m = self.sigmas.numpy().max()
+        return float(m if self.config["timestep_spacing"] in ("linspace", "trailing") else np.sqrt(m * m + np.float32(1)))
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    @property
+    def begin_index(self):
+        return self._begin_index
+
+    def set_begin_index(self, begin_index: int = 0):
+        self._begin_index = begin_index
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        c = self.config
+        nt = c["num_train_timesteps"]
+        self.num_inference_steps = num_inference_steps
+        if c["timestep_spacing"] == "linspace":
+            ts = np.linspace(0, nt - 1, num_inference_steps, dtype=np.float32)[::-1].copy()
+        elif c["timestep_spacing"] == "leading":
+            ts = (np.arange(0, num_inference_steps) * (nt // num_inference_steps)).round()[::-1].copy().astype(np.float32)
+            ts += c["steps_offset"]
+        elif c["timestep_spacing"] == "trailing":
+            ts = (np.arange(nt, 0, -nt / num_inference_steps)).round().copy().astype(np.float32)
+            ts -= 1
+        else:
+            raise ValueError(f"{c['timestep_spacing']} is not supported. Please make sure to choose one of 'linspace', 'leading' or 'trailing'.")
+        table = self._sigma_table()
+        sigmas = np.interp(ts, np.arange(0, len(table)), table)
+        if c.get("use_karras_sigmas"):                               # Karras et al. (2022), rho = 7, over the spaced sigmas' range (:389-412)
+            log_sigmas = np.log(table)
+            min_inv_rho, max_inv_rho = sigmas[-1].item() ** (1 / 7.0), sigmas[0].item() ** (1 / 7.0)
+            sigmas = (max_inv_rho + np.linspace(0, 1, num_inference_steps) * (min_inv_rho - max_inv_rho)) ** 7.0
+            ts = np.array([DPMSolverMultistepScheduler._sigma_to_t(s, log_sigmas) for s in sigmas])      # (fractional: not rounded)
+        self.sigmas = torch.from_numpy(np.concatenate([sigmas.astype(np.float32), np.zeros(1, dtype=np.float32)]))
+        self.timesteps = torch.from_numpy(ts.astype(np.float32))     # kept on the host: the loop indexes coefficient tables
+        self.init_noise_sigma = self._init_noise_sigma()
+        self._coefs = self._step_coefs()
+        s = self.sigmas.numpy()
+        self._scales = [float(v) for v in np.float32(1) / np.sqrt(s * s + np.float32(1))]     # (fp32, as the reference's divisor; sigma 0: exactly 1)
+        self.model_input_prescaled = False
+        self._step_index = None
+        self._begin_index = None
+
+    def _dt(self):
+        """Per step (sigma, dt) as doubles holding the fp32 values the reference computes with (:501, :533)."""
+        s = self.sigmas.numpy()
+        return s[:-1].astype(np.float64).tolist(), (s[1:] - s[:-1]).astype(np.float64).tolist()
+
+    def _fold(self, sigma: float, dt: float) -> List[float]:
+        """x + derivative * dt with derivative = (x - x0) / sigma as coefficients of (sample, model output)."""
+        p = self.config["prediction_type"]
+        if p == "epsilon":                   # x0 = x - sigma e: the derivative is e
+            return [1.0, dt]
+        if p == "v_prediction":              # x0 = -sigma / sqrt(sigma^2 + 1) v + x / (sigma^2 + 1)
+            return [1.0 + dt * sigma / (sigma * sigma + 1.0), dt / math.sqrt(sigma * sigma + 1.0)]
+        return [1.0 + dt / sigma, -dt / sigma]       # x0 is the model output (the last step, dt = -sigma: exactly [0, 1])
+
+    def _step_coefs(self) -> List[List[float]]:
+        return [self._fold(s, d) for s, d in zip(*self._dt())]
+
+    def _input_scale(self, index: int) -> float:
+        """1 / sqrt(sigma_index^2 + 1): what the model input of step `index` is the sample times."""
+        return self._scales[index]
+
+    def index_for_timestep(self, timestep, schedule_timesteps=None):
+        ts = self.timesteps if schedule_timesteps is None else schedule_timesteps
+        cand = (ts == float(timestep)).nonzero()
+        return int(cand[1 if len(cand) > 1 else 0])
+
+    def _ready(self, timestep):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if isinstance(timestep, int) or (torch.is_tensor(timestep) and not torch.is_floating_point(timestep)):
+            raise ValueError(f"Passing integer indices (e.g. from `enumerate(timesteps)`) as timesteps to `{type(self).__name__}.step()` is "
+                             "not supported. Make sure to pass one of the `scheduler.timesteps` as a timestep.")
+        if self._step_index is None:
+            self._step_index = self.index_for_timestep(timestep) if self._begin_index is None else self._begin_index
+
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        if self.model_input_prescaled:
+            return sample
+        self._ready(timestep)
+        return hip.axpby_n([sample.float().contiguous()], [self._input_scale(self._step_index)])
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, s_churn: float = 0.0, s_tmin: float = 0.0,
+             s_tmax: float = float("inf"), s_noise: float = 1.0, generator=None, return_dict: bool = True):
+        """:436-546 with s_churn == 0 (gamma == 0: sigma_hat is sigma and no noise enters; `generator` is not read)."""
+        if s_churn > 0:
+            raise NotImplementedError("s_churn > 0 (stochastic churn) is not built")
+        self._ready(timestep)
+        prev = hip.axpby_n([sample.float().contiguous(), model_output.float().contiguous()], self._coefs[self._step_index])
+        self._step_index += 1
+        return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        raise NotImplementedError(f"{type(self).__name__}.add_noise is only used by training / image-to-image (SURVEY.md §8 f-2)")
+
+
+class EulerAncestralDiscreteScheduler(EulerDiscreteScheduler):
+    """schedulers/scheduling_euler_ancestral_discrete.py: the Euler step down to sigma_down, then fresh noise of scale sigma_up (:422-437),
+    linear in {sample, model output, noise}: ONE mf_axpby_n launch.  sigma_up / sigma_down are the reference's fp32 arithmetic.  One
+    draw per step, the last included, where sigma_up is 0.  The reference has neither Karras sigmas nor the 'sample' prediction here."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0, rescale_betas_zero_snr=False)
+    _prediction_types = ("epsilon", "v_prediction")
+
+    def _step_coefs(self) -> List[List[float]]:
+        s_from, s_to = self.sigmas.numpy()[:-1], self.sigmas.numpy()[1:]
+        up = np.sqrt(s_to * s_to * (s_from * s_from - s_to * s_to) / (s_from * s_from))
+        down = np.sqrt(s_to * s_to - up * up)
+        dts = (down - s_from).astype(np.float64).tolist()
+        return [self._fold(s, d) + [u] for s, d, u in zip(s_from.astype(np.float64).tolist(), dts, up.astype(np.float64).tolist())]
+
+    _noise = DPMSolverMultistepScheduler._noise
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
+             variance_noise: Optional[torch.Tensor] = None, return_dict: bool = True):
+        """:349-450.  `variance_noise`: the step's noise (drawn from `generator` when None)."""
+        self._ready(timestep)
+        x = sample.float().contiguous()
+        if variance_noise is None:
+            variance_noise = self._noise(tuple(x.shape), generator, x.device)
+        if not isinstance(variance_noise, _Sym):
+            variance_noise = variance_noise.to(x.device).float().contiguous()
+        prev = hip.axpby_n([x, model_output.float().contiguous(), variance_noise], self._coefs[self._step_index])
+        self._step_index += 1
+        return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
+
+
 # ---- the multistep schedulers' update on the device (mf_sched_step_dev) ------------------------------------------------------------
 # A step of PNDM / UniPC is a short list of mf_axpby_n calls over the guided noise prediction, the latents and the history the
 # scheduler keeps.  device_plan() runs the scheduler's OWN step() on stand-in tensors that record those calls (terms, order, float
@@ -837,10 +1026,13 @@ class SchedPlan:
     """device_plan()'s result: `rows` (int32 [steps, sizeof(mf_sched_row) / 4], one mf_sched_row per step, host memory), `nslots` (S: the
     state buffer is [S, *latents.shape] fp32) and the traced scheduler, whose end state finish() hands to the real one."""
 
-    def __init__(self, rows: torch.Tensor, nslots: int, traced, steps: int, noise_reg: int = -1):
+    def __init__(self, rows: torch.Tensor, nslots: int, traced, steps: int, noise_reg: int = -1, x_slot: int = -1, first_scale: float = 1.0):
         self.rows, self.nslots, self._traced, self.steps = rows, nslots, traced, steps
-        # the register mf_sched_step_noise_dev fills with the step's standard normals (SDE samplers); -1: the plan reads no noise
+        # the register mf_sched_step_noise_dev fills with the step's standard normals (SDE and ancestral samplers); -1: the plan reads no noise
         self.noise_reg = noise_reg
+        # Euler family: the slot that holds the sample x, while the latents (register 1) hold the model input, x / sqrt(sigma^2 + 1) of
+        # the step about to run.  A run starts with x0 in the slot and x0 * first_scale in the latents.  -1: the latents are the sample.
+        self.x_slot, self.first_scale = x_slot, first_scale
 
     def finish(self, sched, state: torch.Tensor) -> None:
         """After the last device step: `sched` ends in the state its own step() would have left — the counters of the trace, and the
@@ -859,10 +1051,10 @@ class SchedPlan:
 
 def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
     """The rows of mf_sched_step_dev for the first `steps` (default: all) entries of `sched.timesteps`, for a PNDMScheduler,
-    UniPCMultistepScheduler or DPMSolverMultistepScheduler right after set_timesteps.  `sched` itself is not changed (a copy is traced).
-    The SDE type of DPM-Solver++ reads a noise value per step: its register is `noise_reg` of the plan (mf_sched_step_noise_dev)."""
+    UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler or EulerAncestralDiscreteScheduler right after set_timesteps.  `sched` itself is not changed (a copy is traced).
+    The SDE type of DPM-Solver++ and the ancestral Euler class read a noise value per step: its register is `noise_reg` of the plan (mf_sched_step_noise_dev)."""
     global hip
-    if not isinstance(sched, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler)):
+    if not isinstance(sched, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler)):
         raise NotImplementedError(f"{type(sched).__name__} has no device plan (DDIM updates through mf_cfg_ddim_step_dev)")
     if sched.num_inference_steps is None:
         raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
@@ -878,9 +1070,19 @@ def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
     steps = len(ts) if steps is None else int(steps)
     slots, per_step, ntemps = [], [], 0
     real, tracer = hip, _TraceHip()
-    noisy = isinstance(sched, DPMSolverMultistepScheduler) and sched.config["algorithm_type"] == "sde-dpmsolver++"
+    noisy = isinstance(sched, EulerAncestralDiscreteScheduler) or (
+        isinstance(sched, DPMSolverMultistepScheduler) and sched.config["algorithm_type"] == "sde-dpmsolver++")
+    # Euler family: the sample keeps slot 0 from step to step (the host puts x0 there), and every row ends with one more op, the next
+    # step's model input into register 1
+    euler = isinstance(sched, EulerDiscreteScheduler)
+    sample = _Sym("x") if euler else None
+    first_scale = 1.0
+    if euler:
+        slots.append(sample)
+        sample.slot = 0
+        first_scale = sched._input_scale(sched.index_for_timestep(ts[0]) if sched.begin_index is None else sched.begin_index) if steps else 1.0
     for k in range(steps):
-        e, x = _Sym(f"e{k}"), _Sym(f"x{k}")
+        e, x = _Sym(f"e{k}"), (sample if euler else _Sym(f"x{k}"))
         noise = _Sym(f"n{k}") if noisy else None
         tracer.calls = []
         hip = tracer
@@ -888,7 +1090,14 @@ def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
             prev = traced.step(e, ts[k], x, **(dict(variance_noise=noise) if noisy else {}), return_dict=False)[0]
         finally:
             hip = real
-        ops, nt = _plan_step(tracer.calls, e, x, prev, _held(traced), slots, noise)
+        held = _held(traced)
+        if euler:
+            sample = prev
+            prev = tracer.axpby_n([sample], [traced._input_scale(traced.step_index)])
+            held = held + [sample]
+        ops, nt = _plan_step(tracer.calls, e, x, prev, held, slots, noise)
+        if euler and sample.slot != 0:
+            raise AssertionError("device_plan: the Euler sample left its slot")
         per_step.append(ops)
         ntemps = max(ntemps, nt)
     nslots = len(slots)
@@ -919,4 +1128,4 @@ def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
         rows.append(bytes(row))
     table = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.int32).view(steps, -1).clone() if rows else \
         torch.zeros(0, C.sizeof(_Row) // 4, dtype=torch.int32)
-    return SchedPlan(table, nslots, traced, steps, base["t"] if noisy else -1)
+    return SchedPlan(table, nslots, traced, steps, base["t"] if noisy else -1, 0 if euler else -1, first_scale)

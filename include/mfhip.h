@@ -1039,6 +1039,45 @@ int mf_train_batch_draw(float* const* posterior_noise, int32_t nsrc, float* nois
                         int64_t per_sample, int64_t T, int64_t first_sample, int64_t global_batch, int64_t seed, int64_t offset,
                         const uint64_t* state, void* stream);
 
+/* ---- LoRA adapters merged on the device (csrc/lora.hip; appended, ABI stays 23) -------------------------------------------------------
+ * models/lora.py:324,410 (`_fuse_lora` of LoRACompatibleConv / LoRACompatibleLinear) for a TABLE of weights in one grouped launch.  For
+ * every target t, with base_t and out_t row-major fp32 [rows][cols] in the reference's own weight layout (cols = Cin * kh * kw: a conv
+ * LoRA needs no layout knowledge, down is [rank][Cin * kh * kw] and up is the 1 x 1 conv), and its terms first_term .. first_term + nterms:
+ *     out[i][k] = base[i][k] + sum_terms coef[term] * ( sum_{j < rank} up[i][j] * down[j][k] )        up [rows][rank], down [rank][cols]
+ * ARITHMETIC  Each output element is computed by exactly one thread: per term s = 0, then s = fmaf(up[i][j], down[j][k], s) for ascending
+ *             j; the element starts as base[i][k] and takes fmaf(coef[term], s, element) per term, in table order.  fp32 throughout, no
+ *             atomics, and the result does not depend on the grid: the same inputs give the same bits on every run.  (A term with
+ *             coef 0 and finite factors leaves the element's value unchanged.)
+ * TABLES      The target table, the term table and coef (one float per term) are read by the kernel from DEVICE memory (targets_dev,
+ *             terms_dev, coef_dev); they are built once per adapter set, outside any capture, and a new scale or adapter weight
+ *             rewrites coef alone before the next launch.  `targets` / `terms` are the HOST copies of the same two tables: the entry
+ *             validates them and sizes the grid from them.  Targets use the term table in order without gaps (first_term is the running
+ *             sum of nterms), and first_tile is the running sum of mf_lora_tiles(rows, cols).
+ * REFUSED     (-EINVAL, text in mf_last_error) a null table or pointer, rows, cols or rank < 1, out overlapping base (the base is kept
+ *             so that un-merging is exact: it is never subtracted back), a term or tile index out of sequence.  Outputs of different
+ *             targets must not overlap each other either (not checked).
+ * 16-byte accesses along cols are used where cols % 4 == 0 and the addresses allow; other targets (conv_in: cols = 36 is fine, 9 is
+ * not) take scalar accesses.  All pointers need 4-byte alignment. */
+typedef struct mf_lora_target {
+    const float* base;       /* [rows][cols] */
+    float* out;              /* [rows][cols], no overlap with base */
+    int32_t rows, cols;
+    int32_t first_term, nterms;
+    int64_t first_tile;      /* sum of mf_lora_tiles over the targets before this one */
+} mf_lora_target;
+typedef struct mf_lora_term {
+    const float* up;         /* [rows][rank] */
+    const float* down;       /* [rank][cols] */
+    int32_t rank;
+    int32_t reserved;        /* 0 */
+} mf_lora_term;
+int mf_sizeof_lora_target(void);
+int mf_sizeof_lora_term(void);
+/* work items (thread blocks' tiles) of one target; -1 (mf_last_error) for rows or cols < 1 */
+int64_t mf_lora_tiles(int32_t rows, int32_t cols);
+int mf_lora_merge(const mf_lora_target* targets, const mf_lora_term* terms, const mf_lora_target* targets_dev, const mf_lora_term* terms_dev,
+                  const float* coef_dev, int32_t ntargets, int32_t nterms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,17 @@ class SchedRow(C.Structure):
                 ("ops", SchedOp * SCHED_MAX_OPS)]
 
 
+class LoraTarget(C.Structure):
+    """mf_lora_target: one weight of mf_lora_merge's target table (a host copy for the entry's checks, a device copy for the kernel)."""
+    _fields_ = [("base", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("first_term", C.c_int32), ("nterms", C.c_int32), ("first_tile", C.c_int64)]
+
+
+class LoraTerm(C.Structure):
+    """mf_lora_term: one up / down pair of mf_lora_merge's term table."""
+    _fields_ = [("up", C.c_void_p), ("down", C.c_void_p), ("rank", C.c_int32), ("reserved", C.c_int32)]
+
+
 # The C ABI, once: every function include/mfhip.h declares, as "<return kind>:<one kind per parameter>" (the stream included).
 # p pointer (device or host memory, an opaque handle, a C string), i int / int32_t, l int64_t, f float; returns also s (const char*) and
 # v (void); one letter per host descriptor struct (DESC_KINDS), so that a descriptor parameter takes a pointer to ITS struct only.
@@ -237,13 +248,15 @@ SIGNATURES = {
     "mf_train_batch_draw": "i:pipplllllllpp",
     # the multistep update with per-step noise drawn in the kernel (csrc/elementwise.hip; DPM-Solver++ SDE)
     "mf_sched_step_noise_dev": "i:ppfppplilllllpp",
+    # LoRA adapters merged on the device (csrc/lora.hip)
+    "mf_sizeof_lora_target": "i:", "mf_sizeof_lora_term": "i:", "mf_lora_tiles": "l:ii", "mf_lora_merge": "i:pppppiip",
 }
 EXPORTS = list(SIGNATURES)
 # (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
 _LAYOUTS = ((GemmDesc, "mf_sizeof_gemm_desc"), (GroupNormDesc, "mf_sizeof_groupnorm_desc"), (AttnBwdDesc, "mf_sizeof_attn_bwd_desc"),
             (WgradDesc, "mf_sizeof_wgrad_desc"), (GroupNormBwdDesc, "mf_sizeof_groupnorm_bwd_desc"), (SchedRow, "mf_sizeof_sched_row"),
             (MetricsRow, "mf_sizeof_metrics_row"), (GemmPlan, "mf_sizeof_gemm_plan"), (WgradPlan, "mf_sizeof_wgrad_plan"),
-            (GnPlan, "mf_sizeof_gn_plan"))
+            (GnPlan, "mf_sizeof_gn_plan"), (LoraTarget, "mf_sizeof_lora_target"), (LoraTerm, "mf_sizeof_lora_term"))
 _CTYPES = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "s": C.c_char_p, "v": None,
            **{kind: C.POINTER(struct) for kind, struct in DESC_KINDS.items()}}
 
@@ -2139,3 +2152,59 @@ def depth_normalize(depth: torch.Tensor, mask: Optional[torch.Tensor] = None, ma
     _launch("mf_depth_normalize", depth, mask.contiguous() if mask is not None else None, out, depth.numel(), max_scene_depth, delta,
             int(signed_range), _mm_ws(depth.device))
     return out
+
+
+# ---- LoRA adapters merged on the device (csrc/lora.hip) --------------------------------------------------------------------------
+class LoraTables:
+    """The target / term tables of mf_lora_merge for `targets` = [(base, out, [(up, down), ...]), ...]: fp32 device tensors, base / out
+    [rows, cols], up [rows, rank], down [rank, cols], all contiguous.  Built once per adapter set (host -> device copies: never inside a
+    capture); `coef` (one float per term, device) is the only thing a new scale rewrites.  Keeps every tensor it points to alive."""
+
+    def __init__(self, targets, device):
+        lib = load()
+        self.keep = []
+        tg, tm = [], []
+        tiles = 0
+        for base, out, pairs in targets:
+            _f32(base, out)
+            rows, cols = base.shape
+            if tuple(out.shape) != (rows, cols) or not (base.is_contiguous() and out.is_contiguous()):
+                raise MfhipError("lora: base and out are contiguous fp32 [rows, cols] of one shape")
+            if not pairs:
+                raise MfhipError("lora: a target without a term")
+            tg.append(LoraTarget(base.data_ptr(), out.data_ptr(), rows, cols, len(tm), len(pairs), tiles))
+            n = lib.mf_lora_tiles(rows, cols)
+            if n < 0:
+                raise MfhipError(f"mf_lora_tiles failed: {lib.mf_last_error().decode()}")
+            tiles += n
+            self.keep += [base, out]
+            for up, down in pairs:
+                _f32(up, down)
+                if up.dim() != 2 or down.dim() != 2 or up.shape[0] != rows or down.shape[1] != cols or up.shape[1] != down.shape[0] \
+                        or not (up.is_contiguous() and down.is_contiguous()):
+                    raise MfhipError(f"lora: up {tuple(up.shape)} / down {tuple(down.shape)} do not fit a [{rows}, {cols}] weight")
+                tm.append(LoraTerm(up.data_ptr(), down.data_ptr(), up.shape[1], 0))
+                self.keep += [up, down]
+        if not tg:
+            raise MfhipError("lora: no targets")
+        self.targets = (LoraTarget * len(tg))(*tg)
+        self.terms = (LoraTerm * len(tm))(*tm)
+        self.ntargets, self.nterms, self.tiles = len(tg), len(tm), tiles
+        as_dev = lambda arr: torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+        self.targets_dev, self.terms_dev = as_dev(self.targets), as_dev(self.terms)
+        self.coef = torch.zeros(len(tm), dtype=torch.float32, device=device)
+        # bytes one merge moves: base read + out written, and each term's factors once (their re-reads come from the caches)
+        self.bytes = sum(8 * b.numel() for b, _, _ in targets) + sum(4 * (u.numel() + d.numel()) for _, _, ps in targets for u, d in ps)
+
+
+def lora_merge(tables: LoraTables, coef=None) -> None:
+    """out_t = base_t + sum_terms coef * up @ down for every target of the tables, one launch (mf_lora_merge).  `coef`: the per-term
+    factors (a sequence or tensor of nterms floats) to upload first; None keeps tables.coef as it is."""
+    if coef is not None:
+        c = torch.as_tensor(coef, dtype=torch.float32).reshape(-1)
+        if c.numel() != tables.nterms:
+            raise MfhipError(f"lora_merge: {c.numel()} coefficients for {tables.nterms} terms")
+        tables.coef.copy_(c)
+    _req_cuda(tables.coef, tables.targets_dev, tables.terms_dev)
+    _launch("mf_lora_merge", C.cast(tables.targets, C.c_void_p), C.cast(tables.terms, C.c_void_p), tables.targets_dev, tables.terms_dev,
+            tables.coef, tables.ntargets, tables.nterms)

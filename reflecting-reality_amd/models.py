@@ -24,6 +24,7 @@ import torch
 
 from . import autograd, hip, ops
 from .autograd import Param
+from .lora import LoraMixin, scale_of as _lora_scale_of
 from .ops import ConvWeight, Precision
 
 F32 = torch.float32
@@ -98,8 +99,8 @@ def from_nchw(x: torch.Tensor, prec: Precision, c_pad: Optional[int] = None) -> 
     return hip.pack_nhwc(x, None, cp, prec.act)
 
 
-class HipModel:
-    """Minimal ModelMixin/ConfigMixin counterpart (modeling_utils.py, configuration_utils.py)."""
+class HipModel(LoraMixin):
+    """Minimal ModelMixin/ConfigMixin counterpart (modeling_utils.py, configuration_utils.py).  LoRA adapters: lora.LoraMixin."""
 
     config_name = "config.json"
     weights_name = "diffusion_pytorch_model.safetensors"
@@ -107,6 +108,8 @@ class HipModel:
     training = False            # class defaults: objects assembled piecewise (tests) are inference models
     flat_w = flat_g = None
     _weights_gen = 0
+    _lora_refusal = "this model is no LoRA target (adapters load into UNet2DConditionModel and CLIPTextModel)"
+    _only = None                # module names whose derived layouts a selective rebuild (lora.py) re-derives; None: _prepare builds all
 
     def __init__(self, config: Dict[str, Any], precision: Union[str, Precision, torch.dtype] = "bf16",
                  device: Union[str, torch.device] = "cuda"):
@@ -160,7 +163,7 @@ class HipModel:
             return self._export(self.flat_w)
         if self._src is None:
             raise RuntimeError("no parameters loaded")
-        return dict(self._src)
+        return self._lora_state_dict() or dict(self._src)      # (the merged weights when a LoRA adapter is fused, as the reference saves)
 
     def grad_state_dict(self) -> Dict[str, torch.Tensor]:
         """The gradient arena in the reference's parameter layout (what `p.grad` holds there)."""
@@ -174,6 +177,9 @@ class HipModel:
         optimizer updates them in place every step, so nothing is pre-split or fused) plus, when the model trains, a
         gradient arena of the same layout.  Precision must keep fp32 storage ('fp32', 'f16x3', or 'bf16x1': the arithmetic
         of the reference's --mixed_precision=bf16)."""
+        if self._lora_state() is not None:
+            raise NotImplementedError("prepare_training() with LoRA adapters loaded: they are merged into the inference layouts, and "
+                                      "training LoRA layers is not built; unload_lora() first")
         if self.prec.act != F32:
             raise NotImplementedError("training runs with fp32 master weights and activations: build the model with "
                                       "precision='fp32', 'f16x3' or 'bf16x1' (bf16 products, fp32 storage)")
@@ -309,6 +315,9 @@ class HipModel:
         return out
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
+        if self._lora_state() is not None:
+            raise RuntimeError(f"{type(self).__name__}.load_state_dict with LoRA adapters loaded would leave their stashed base weights "
+                               "stale: unload_lora() first")
         shapes = self.param_shapes()
         sd = self._convert_deprecated_keys(dict(sd))
         missing = [k for k in shapes if k not in sd]
@@ -356,6 +365,9 @@ class HipModel:
         """nn.Module.train(): the MirrorFusion nets have no dropout / batch-norm state (dropout 0.0, resnet.py:393), so the
         only effect is switching the parameters to the training layout the first time."""
         if mode and not self.training:
+            if self._lora_state() is not None:
+                raise NotImplementedError("train() with LoRA adapters loaded: they are merged into the inference layouts, and training "
+                                          "LoRA layers is not built; unload_lora() first")
             if self.__dict__.get("_ip_procs"):
                 raise NotImplementedError("IP-Adapter processors are inference only: the backward pass of the ip branch is not built")
             self.prepare_training()
@@ -389,6 +401,19 @@ class HipModel:
         save_file({k: v.contiguous() for k, v in self.state_dict().items()}, os.path.join(path, self.weights_name))
 
     # -- helpers shared by the three models -------------------------------------------------------
+    def _put(self, key: str, deps: Sequence[str], make) -> None:
+        """self.P[key] = make(), the layout derived from the weights of the modules `deps`.  Under a selective rebuild (self._only: the
+        modules whose weights changed, lora.LoraMixin._lora_apply) only the entries that derive from one of them are made again, by
+        the very derivation a full _prepare runs; every other entry stays the object it was."""
+        if self._only is None or any(d in self._only for d in deps):
+            self.P[key] = make()
+
+    def _rows(self, *ws: torch.Tensor) -> torch.Tensor:
+        """Row blocks of one fused matrix.  A merged adapter weight lives on the device, its untargeted neighbours on the host."""
+        if any(w.is_cuda for w in ws):
+            ws = [w.to(self.device) for w in ws]
+        return torch.cat(list(ws), 0)
+
     def _conv(self, sd, name, prec=None, cin_pad=None, fp8: bool = False) -> ConvWeight:
         if self.training:
             return self._conv_param(name, sd[name + ".weight"], sd.get(name + ".bias"), prec or self.prec, cin_pad)
@@ -507,14 +532,17 @@ class _UNetCore(HipModel):
     # ---- parameter preparation ------------------------------------------------------------------
     def _prepare_time(self, sd):
         f32 = Precision.get("fp32")
-        self.te1 = self._conv(sd, "time_embedding.linear_1", f32)
-        self.te2 = self._conv(sd, "time_embedding.linear_2", f32)
-        self.add1 = self.add2 = None
-        if self.config["addition_embed_type"] == "text_time":
-            self.add1 = self._conv(sd, "add_embedding.linear_1", f32)
-            self.add2 = self._conv(sd, "add_embedding.linear_2", f32)
+        only = self._only
+        if only is None:
+            self.add1 = self.add2 = None
+        for attr, name in (("te1", "time_embedding.linear_1"), ("te2", "time_embedding.linear_2"), ("add1", "add_embedding.linear_1"),
+                           ("add2", "add_embedding.linear_2")):
+            if (only is None or name in only) and (attr[0] == "t" or self.config["addition_embed_type"] == "text_time"):
+                setattr(self, attr, self._conv(sd, name, f32))
         # all time_emb_proj layers as ONE [sum(Cout), temb] GEMM; each resnet reads a column slice
         names = [k[: -len(".time_emb_proj.weight")] for k in self.param_shapes() if k.endswith(".time_emb_proj.weight")]
+        if only is not None and not any(n + ".time_emb_proj" in only for n in names):
+            return
         self.temb_slices = {}
         off = 0
         ws, bs = [], []
@@ -534,15 +562,15 @@ class _UNetCore(HipModel):
             if p_w.grad is not None:
                 self._fw_params.append(p_w)        # one Linear, one weight gradient over all its rows: write-first like _conv_param's
         else:
-            self.temb_proj = ConvWeight(torch.cat(ws, 0), torch.cat(bs, 0), f32, self.device)
+            self.temb_proj = ConvWeight(self._rows(*ws), torch.cat(bs, 0), f32, self.device)
 
     def _prepare_resnet(self, sd, p):
-        self.P[p + "norm1"] = self._norm(sd, p + "norm1")
-        self.P[p + "conv1"] = self._conv(sd, p + "conv1")
-        self.P[p + "norm2"] = self._norm(sd, p + "norm2")
-        self.P[p + "conv2"] = self._conv(sd, p + "conv2")
+        self._put(p + "norm1", (), lambda: self._norm(sd, p + "norm1"))
+        self._put(p + "conv1", (p + "conv1",), lambda: self._conv(sd, p + "conv1"))
+        self._put(p + "norm2", (), lambda: self._norm(sd, p + "norm2"))
+        self._put(p + "conv2", (p + "conv2",), lambda: self._conv(sd, p + "conv2"))
         if p + "conv_shortcut.weight" in sd:
-            self.P[p + "conv_shortcut"] = self._conv(sd, p + "conv_shortcut")
+            self._put(p + "conv_shortcut", (p + "conv_shortcut",), lambda: self._conv(sd, p + "conv_shortcut"))
 
     def _prepare_transformer(self, sd, p):
         # precision "fp8": every Linear of the transformer blocks whose input is a token row of the model width runs on fp8
@@ -550,27 +578,32 @@ class _UNetCore(HipModel):
         # tokens, computed once per prompt) and everything outside the transformer blocks stay bf16
         f8 = self.prec.fp8_linear and not self.training
         ok8 = lambda name: f8 and sd[name + ".weight"].shape[1] % 16 == 0
-        self.P[p + "norm"] = self._norm(sd, p + "norm")
-        self.P[p + "proj_in"] = self._conv(sd, p + "proj_in", fp8=ok8(p + "proj_in") and sd[p + "proj_in.weight"].dim() == 2)
-        self.P[p + "proj_out"] = self._conv(sd, p + "proj_out", fp8=ok8(p + "proj_out") and sd[p + "proj_out.weight"].dim() == 2)
+        put = self._put
+        W = lambda name: sd[name + ".weight"]
+        H = lambda name: sd[name + ".weight"].cpu()      # the LayerNorm folds are computed where the weight lives: always on the host
+        put(p + "norm", (), lambda: self._norm(sd, p + "norm"))
+        put(p + "proj_in", (p + "proj_in",), lambda: self._conv(sd, p + "proj_in", fp8=ok8(p + "proj_in") and W(p + "proj_in").dim() == 2))
+        put(p + "proj_out", (p + "proj_out",), lambda: self._conv(sd, p + "proj_out", fp8=ok8(p + "proj_out") and W(p + "proj_out").dim() == 2))
         i = 0
         while f"{p}transformer_blocks.{i}.norm1.weight" in sd:
             b = f"{p}transformer_blocks.{i}."
             for n in ("norm1", "norm2", "norm3"):
-                self.P[b + n] = self._norm(sd, b + n)
+                put(b + n, (), lambda: self._norm(sd, b + n))
             for a in ("attn1", "attn2"):
                 for l in ("to_q", "to_k", "to_v", "to_out.0"):
                     nm = b + a + "." + l
-                    self.P[nm] = self._conv(sd, nm, fp8=ok8(nm) and not (a == "attn2" and l in ("to_k", "to_v")))
+                    put(nm, (nm,), lambda: self._conv(sd, nm, fp8=ok8(nm) and not (a == "attn2" and l in ("to_k", "to_v"))))
             if self.training:      # no fused / interleaved copies: the arena holds each parameter once
                 self.P[b + "ff.net.0.proj"] = self._conv(sd, b + "ff.net.0.proj")
             else:
                 # self-attention: q and k read the same tokens -> one GEMM with N = 2C
-                self.P[b + "attn1.to_qk"] = ConvWeight(torch.cat([sd[b + "attn1.to_q.weight"], sd[b + "attn1.to_k.weight"]], 0),
-                                                       None, self.prec, self.device, fp8=ok8(b + "attn1.to_q"))
-                self.P[b + "ff.net.0.proj"] = ops.geglu_weight(sd[b + "ff.net.0.proj.weight"], sd[b + "ff.net.0.proj.bias"],
-                                                               self.prec, self.device, fp8=ok8(b + "ff.net.0.proj"))
-            self.P[b + "ff.net.2"] = self._conv(sd, b + "ff.net.2", fp8=ok8(b + "ff.net.2"))
+                put(b + "attn1.to_qk", (b + "attn1.to_q", b + "attn1.to_k"),
+                    lambda: ConvWeight(self._rows(W(b + "attn1.to_q"), W(b + "attn1.to_k")), None, self.prec, self.device,
+                                       fp8=ok8(b + "attn1.to_q")))
+                put(b + "ff.net.0.proj", (b + "ff.net.0.proj",),
+                    lambda: ops.geglu_weight(W(b + "ff.net.0.proj"), sd[b + "ff.net.0.proj.bias"], self.prec, self.device,
+                                             fp8=ok8(b + "ff.net.0.proj")))
+            put(b + "ff.net.2", (b + "ff.net.2",), lambda: self._conv(sd, b + "ff.net.2", fp8=ok8(b + "ff.net.2")))
             c = sd[b + "norm1.weight"].shape[0]
             if self.prec.name in ("bf16", "fp16") and not self.training and c % 320 == 0:
                 # bf16 inference: the three LayerNorms of the block are FOLDED into the Linears that consume them (W diag(gamma),
@@ -578,15 +611,16 @@ class _UNetCore(HipModel):
                 # self-attention are one GEMM whose V third is stored transposed: 3 LayerNorm launches and the V^T launch less
                 # per block, the normalised tensors are never written (attention.py:203,233,261,291-412)
                 ln = lambda n: (sd[b + n + ".weight"], sd[b + n + ".bias"], 1e-5)
-                self.P[b + "attn1.to_qkv_ln"] = ConvWeight(torch.cat([sd[b + "attn1.to_q.weight"], sd[b + "attn1.to_k.weight"],
-                                                                      sd[b + "attn1.to_v.weight"]], 0), None, self.prec, self.device,
-                                                           ln=ln("norm1"))
-                self.P[b + "attn2.to_q_ln"] = ConvWeight(sd[b + "attn2.to_q.weight"], None, self.prec, self.device, ln=ln("norm2"))
+                put(b + "attn1.to_qkv_ln", (b + "attn1.to_q", b + "attn1.to_k", b + "attn1.to_v"),
+                    lambda: ConvWeight(torch.cat([H(b + "attn1.to_q"), H(b + "attn1.to_k"), H(b + "attn1.to_v")], 0), None, self.prec,
+                                       self.device, ln=ln("norm1")))
+                put(b + "attn2.to_q_ln", (b + "attn2.to_q",),
+                    lambda: ConvWeight(H(b + "attn2.to_q"), None, self.prec, self.device, ln=ln("norm2")))
                 # norm3 -> GEGLU projection (round 6): on the ring tiles the fold lost at every level (sixteen column tiles repeat the row
                 # statistics, and the GEGLU epilogue wants small tiles); the persistent tile 70 gathers them once per block from the A
                 # tiles it stages anyway (tools/bench_ff1.py: 32768 x 320 -> 2560 +4 us against a 12 us LayerNorm launch)
-                self.P[b + "ff.net.0.proj_ln"] = ops.geglu_weight(sd[b + "ff.net.0.proj.weight"], sd[b + "ff.net.0.proj.bias"],
-                                                                  self.prec, self.device, ln=ln("norm3"))
+                put(b + "ff.net.0.proj_ln", (b + "ff.net.0.proj",),
+                    lambda: ops.geglu_weight(H(b + "ff.net.0.proj"), sd[b + "ff.net.0.proj.bias"], self.prec, self.device, ln=ln("norm3")))
             i += 1
         self.tdepth[p] = i
 
@@ -969,7 +1003,7 @@ class _UNetCore(HipModel):
         cw = None
         if (self._src is not None and bn._src is not None and not self.P[p + "proj_out"].fp8 and not self.training
                 and self._src[p + "proj_out.weight"].dim() == 4 and bn.prec.name == self.prec.name):
-            w = torch.cat([self._src[p + "proj_out.weight"].float(), lz.scale * bn._src[lz.name + ".weight"].float()], 1)
+            w = torch.cat([self._current_weight(p + "proj_out.weight").float(), lz.scale * bn._src[lz.name + ".weight"].float()], 1)
             b = self._src[p + "proj_out.bias"].float() + lz.scale * bn._src[lz.name + ".bias"].float()
             cw = ConvWeight(w, b, self.prec, self.device)
         for k in [k for k in cache if k[0] == p and k != key]:     # weights or scale changed: drop the stale entry
@@ -1143,6 +1177,7 @@ class BrushNetModel(_UNetCore):
     """models/brushnet.py — attention-free UNet clone emitting 12 down + 1 mid + 15 up residuals."""
 
     _class_name = "BrushNetModel"
+    _lora_refusal = "BrushNetModel takes no LoRA adapter: the reference never loads one into it (pipeline_brushnet.py LoraLoaderMixin targets the UNet and the text encoder)"
 
     def __init__(self, config=None, precision="bf16", device="cuda", **kwargs):
         cfg = dict(config or {})
@@ -1379,6 +1414,7 @@ class UNet2DConditionModel(_UNetCore):
     """models/unets/unet_2d_condition.py with the BrushNet injection kwargs."""
 
     _class_name = "UNet2DConditionModel"
+    _lora_refusal = None
 
     def __init__(self, config=None, precision="bf16", device="cuda", **kwargs):
         cfg = dict(config or {})
@@ -1471,20 +1507,21 @@ class UNet2DConditionModel(_UNetCore):
 
     def _prepare(self, sd):
         c = self.config
-        self.P = {}
-        self.tdepth = {}
+        if self._only is None:
+            self.P = {}
+            self.tdepth = {}
         self.cin_pad = (c["in_channels"] + 7) // 8 * 8
-        self.P["conv_in"] = self._conv(sd, "conv_in", cin_pad=self.cin_pad)
+        self._put("conv_in", ("conv_in",), lambda: self._conv(sd, "conv_in", cin_pad=self.cin_pad))
         self._prepare_time(sd)
         for k in self.param_shapes():
             if k.endswith(".norm1.weight") and ".resnets." in k:
                 self._prepare_resnet(sd, k[: -len("norm1.weight")])
             elif k.endswith("samplers.0.conv.weight"):
-                self.P[k[: -len(".weight")]] = self._conv(sd, k[: -len(".weight")])
+                self._put(k[: -len(".weight")], (k[: -len(".weight")],), lambda: self._conv(sd, k[: -len(".weight")]))
             elif k.endswith(".proj_in.weight"):
                 self._prepare_transformer(sd, k[: -len("proj_in.weight")])
-        self.P["conv_norm_out"] = self._norm(sd, "conv_norm_out")
-        self.P["conv_out"] = self._conv(sd, "conv_out")
+        self._put("conv_norm_out", (), lambda: self._norm(sd, "conv_norm_out"))
+        self._put("conv_out", ("conv_out",), lambda: self._conv(sd, "conv_out"))
         self._cross_kv, self._ehs_key, self._ehs_gen, self._ehs_val, self._ehs_ref = {}, None, 0, None, None
 
     @_scoped_tune_ctx
@@ -1502,8 +1539,10 @@ class UNet2DConditionModel(_UNetCore):
         if any(v is not None for v in (class_labels, timestep_cond, attention_mask,
                                        down_block_additional_residuals, mid_block_additional_residual,
                                        down_intrablock_additional_residuals, encoder_attention_mask)) \
-                or (cross_attention_kwargs not in (None, {})):
+                or (cross_attention_kwargs not in (None, {}) and self._lora_state() is None):
             raise NotImplementedError("ControlNet / T2I-adapter / mask / LoRA-scale inputs are outside the MirrorFusion hot path")
+        if self._lora_state() is not None:          # adapters are always merged: {"scale": s} re-merges when s is not what is on the device
+            self._lora_sync(_lora_scale_of(cross_attention_kwargs))
         c = self.config
         n = len(c["block_out_channels"])
         lpb = c["layers_per_block"]

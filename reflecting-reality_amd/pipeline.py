@@ -21,6 +21,7 @@ import json
 import os
 import time
 
+from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Optional, Union
 
@@ -28,6 +29,7 @@ import numpy as np
 import torch
 
 from . import hip
+from . import lora as _lora
 from .models import AutoencoderKL, BrushNetModel, UNet2DConditionModel
 from .rng import PhiloxGenerator, is_philox, randn_tensor
 from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, PNDMScheduler,
@@ -719,8 +721,14 @@ class StableDiffusionBrushNetPipeline:
         if ip_mode and not getattr(self.unet, "_ip_procs", None):
             raise ValueError("normals_conditioning_mode='ip_adapter' needs IP-Adapter processors on the UNet: unet.load_ip_adapter(...) or "
                              "unet.set_attn_processor({...attn2.processor: MfhipIPAttnProcessor(...)})")
-        if cross_attention_kwargs:
+        lora_models = self._lora_models()
+        if cross_attention_kwargs and not lora_models:
             raise NotImplementedError("cross_attention_kwargs (LoRA scale) are not built")
+        if lora_models:                      # adapters are always merged: this call's scale is merged here, before anything is captured
+            lora_scale = _lora.scale_of(cross_attention_kwargs)
+            for m in lora_models:
+                m.set_lora_scale(1.0 if lora_scale is None else lora_scale)
+                m._lora_sync()
         if timesteps is not None:
             # retrieve_timesteps (pipeline_brushnet.py:113-119): the reference's DDIM / PNDM / UniPC `set_timesteps` take no custom
             # schedule either and the reference raises exactly this
@@ -1179,6 +1187,81 @@ class StableDiffusionBrushNetPipeline:
         info["meta"] = meta
         return info
 
+    # -- LoRA adapters (pipeline_brushnet.py:128-145 LoraLoaderMixin; lora.py) ---------------------------------------------------------
+    def _lora_models(self) -> list:
+        """The UNet / HIP text encoder that hold adapters."""
+        return [m for m in (self.unet, self.text_encoder) if hasattr(m, "_lora_state") and m._lora_state() is not None]
+
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None, weight_name: Optional[str] = None,
+                          **kwargs) -> None:
+        """LoraLoaderMixin.load_lora_weights: a diffusers, legacy attention-processor or kohya LoRA (dict, .safetensors file or a directory
+        holding pytorch_lora_weights.safetensors).  `unet.` / `lora_unet_` keys (and keys without a prefix) bind to the UNet,
+        `text_encoder.` / `lora_te_` keys to the HIP text encoder.  Both models are checked before either is changed."""
+        if kwargs:
+            raise NotImplementedError(f"load_lora_weights: {sorted(kwargs)} are not built")
+        self._lora_refuse_xl("load_lora_weights")
+        groups = _lora.group_keys(_lora.read_state_dict(pretrained_model_name_or_path_or_dict, weight_name))
+        unet_entries = OrderedDict(list(groups["unet"].items()) + list(groups[""].items()))
+        te_entries = groups["text_encoder"]
+        if not unet_entries and not te_entries:
+            raise ValueError("load_lora_weights: the state dict holds no LoRA weights")
+        if te_entries:
+            from .text_encoder import CLIPTextModel
+            if not isinstance(self.text_encoder, CLIPTextModel):
+                raise NotImplementedError("the file holds text-encoder LoRA keys: they load into the HIP text encoder (text_encoder.CLIPTextModel), "
+                                          "which this pipeline was not built with")
+        name = adapter_name or f"default_{max([len(m._lora_state().adapters) for m in self._lora_models()] or [0])}"
+        for model, entries in ((self.unet, unet_entries), (self.text_encoder, te_entries)):      # check everything before anything is changed
+            if entries:
+                model._lora_guard()
+                _lora.resolve(entries, model.param_shapes(), model.lora_modules())
+                if model._lora_state() is not None and name in model._lora_state().adapters:
+                    raise ValueError(f"adapter_name {name!r} is already loaded: unload_lora_weights() or pick another name")
+        for model, entries in ((self.unet, unet_entries), (self.text_encoder, te_entries)):
+            if entries:
+                model.load_lora(None, adapter_name=name, _entries=entries)
+
+    def set_adapters(self, adapter_names, adapter_weights=None) -> None:
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        models = self._lora_models()
+        known = {n for m in models for n in m._lora_state().adapters}
+        for n in names:
+            if n not in known:
+                raise ValueError(f"set_adapters: adapter {n!r} is not loaded (have {sorted(known)})")
+        if adapter_weights is None or isinstance(adapter_weights, (int, float)):
+            adapter_weights = [1.0 if adapter_weights is None else float(adapter_weights)] * len(names)
+        if len(adapter_weights) != len(names):
+            raise ValueError(f"set_adapters: {len(names)} names and {len(adapter_weights)} weights")
+        for m in models:                      # an adapter may touch one of the two models only
+            have = [(n, w) for n, w in zip(names, adapter_weights) if n in m._lora_state().adapters]
+            m.set_adapters([n for n, _ in have], [w for _, w in have])
+
+    def get_active_adapters(self) -> List[str]:
+        out: List[str] = []
+        for m in self._lora_models():
+            out += [n for n in m.active_adapters() if n not in out]
+        return out
+
+    def fuse_lora(self, fuse_unet: bool = True, fuse_text_encoder: bool = True, lora_scale: float = 1.0, safe_fusing: bool = False) -> None:
+        self._lora_refuse_xl("fuse_lora")
+        for m, on in ((self.unet, fuse_unet), (self.text_encoder, fuse_text_encoder)):
+            if on and m in self._lora_models():
+                m.fuse_lora(lora_scale=lora_scale, safe_fusing=safe_fusing)
+
+    def unfuse_lora(self, unfuse_unet: bool = True, unfuse_text_encoder: bool = True) -> None:
+        for m, on in ((self.unet, unfuse_unet), (self.text_encoder, unfuse_text_encoder)):
+            if on and m in self._lora_models():
+                m.unfuse_lora()
+
+    def unload_lora_weights(self) -> None:
+        for m in self._lora_models():
+            m.unload_lora()
+
+    def _lora_refuse_xl(self, what: str) -> None:
+        if type(self) is not StableDiffusionBrushNetPipeline:
+            raise NotImplementedError(f"{type(self).__name__}.{what}: LoRA loading is built for the SD1.5 pipeline (SDXL's two text encoders and "
+                                      "SGM key maps are not); at the model level a diffusers-format adapter loads into the SDXL UNet")
+
     def export_call(self, directory: str, **call_kwargs) -> dict:
         """Run the pipeline once and write the whole call as five programs plus manifest.json / manifest.txt into `directory`:
         encode_prompt.mfprog (mf_encode_prompt), bind_prompt.mfprog, conditioning.mfprog (mf_build_conditioning), step.mfprog
@@ -1192,6 +1275,10 @@ class StableDiffusionBrushNetPipeline:
             raise NotImplementedError(f"export_call under {type(self.scheduler).__name__}: the exported call's host loop feeds the sample "
                                       "to the step, the Euler family's step reads the scaled model input (export_denoise_step carries it)")
         program.refuse_ip_processors(self.unet)
+        for m in self._lora_models():
+            if m._lora_state().pinned is None:
+                raise NotImplementedError("export_call with LoRA adapters loaded but not fused: the exported programs hold one set of weights; "
+                                          "call fuse_lora(lora_scale=...) first")
         if type(self) is not StableDiffusionBrushNetPipeline:
             raise NotImplementedError("export_call is built for the SD1.5 pipeline (SDXL's pooled text embedding feeds export-time tables)")
         if self.normals_conditioning_mode is not None or call_kwargs.get("guess_mode"):

@@ -112,3 +112,23 @@ class HashTokenizer:
 
     def batch_decode(self, ids):
         return [" ".join(f"<{int(i)}>" for i in row) for row in ids]
+
+
+def lora_plan(modules: Iterable[str]):
+    """The fixture adapters' (module, rank, alpha) per LoRA-capable module (tools/make_golden_lora.py and the LoRA tests): ranks 4 and 3
+    alternate, every third target has no alpha."""
+    return [(m, 4 if i % 2 == 0 else 3, (None, 2.0, 6.0)[i % 3]) for i, m in enumerate(modules)]
+
+
+def lora_adapter(plan, shapes: Dict[str, Tuple[int, ...]], seed: int, gain: float, prefix: str = "unet."):
+    """A diffusers-format LoRA state dict and its network_alphas for plan = [(module, rank, alpha or None)]: every tensor is
+    gain * fill(its key without the prefix, its shape, seed).  down is [r, Cin(, kh, kw)], up [N, r(, 1, 1)]."""
+    sd, alphas = {}, {}
+    for module, rank, alpha in plan:
+        shp = tuple(shapes[module + ".weight"])
+        kd, ku = f"{module}.lora.down.weight", f"{module}.lora.up.weight"          # (the values do not depend on the prefix)
+        sd[prefix + kd] = gain * fill(kd, (rank,) + shp[1:], seed)
+        sd[prefix + ku] = gain * fill(ku, (shp[0], rank) + ((1, 1) if len(shp) == 4 else ()), seed)
+        if alpha is not None:
+            alphas[f"{prefix}{module}.alpha"] = float(alpha)
+    return sd, alphas

@@ -46,20 +46,29 @@ def norm_pair(sd, name: str, device):
     return (sd[name + ".weight"].to(device, F32).contiguous(), sd[name + ".bias"].to(device, F32).contiguous())
 
 
-def prepare_layers(P: Dict[str, Any], sd, prefix: str, layers: int, prec, dev) -> None:
-    """The device weights of the layers under `prefix`, as encoder_layer() reads them from P."""
+def prepare_layers(P: Dict[str, Any], sd, prefix: str, layers: int, prec, dev, only=None) -> None:
+    """The device weights of the layers under `prefix`, as encoder_layer() reads them from P.  `only`: the module names whose weights
+    changed (a selective rebuild, lora.py) — the entries that derive from none of them stay the objects they are."""
+    def put(key, deps, make):
+        if only is None or any(d in only for d in deps):
+            P[key] = make()
+
+    def rows(*ws):                                   # a merged adapter weight lives on the device, its untargeted neighbour on the host
+        return torch.cat([w.to(dev) for w in ws] if any(w.is_cuda for w in ws) else list(ws))
+
     for i in range(layers):
         p = f"{prefix}{i}."
         a = p + "self_attn."
-        P[f"{i}.ln1"] = norm_pair(sd, p + "layer_norm1", dev)
-        P[f"{i}.ln2"] = norm_pair(sd, p + "layer_norm2", dev)
-        P[f"{i}.to_qk"] = ConvWeight(torch.cat([sd[a + "q_proj.weight"], sd[a + "k_proj.weight"]]),
-                                     torch.cat([sd[a + "q_proj.bias"], sd[a + "k_proj.bias"]]), prec, dev)
+        put(f"{i}.ln1", (), lambda: norm_pair(sd, p + "layer_norm1", dev))
+        put(f"{i}.ln2", (), lambda: norm_pair(sd, p + "layer_norm2", dev))
+        put(f"{i}.to_qk", (a + "q_proj", a + "k_proj"),
+            lambda: ConvWeight(rows(sd[a + "q_proj.weight"], sd[a + "k_proj.weight"]),
+                               torch.cat([sd[a + "q_proj.bias"], sd[a + "k_proj.bias"]]), prec, dev))
         # V^T leaves ops.linear_t with the weight as the A operand: never pre-split
-        P[f"{i}.to_v"] = ConvWeight(sd[a + "v_proj.weight"], sd[a + "v_proj.bias"], prec, dev, raw=True)
-        P[f"{i}.out"] = ConvWeight(sd[a + "out_proj.weight"], sd[a + "out_proj.bias"], prec, dev)
-        P[f"{i}.fc1"] = ConvWeight(sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"], prec, dev)
-        P[f"{i}.fc2"] = ConvWeight(sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"], prec, dev)
+        put(f"{i}.to_v", (a + "v_proj",), lambda: ConvWeight(sd[a + "v_proj.weight"], sd[a + "v_proj.bias"], prec, dev, raw=True))
+        put(f"{i}.out", (a + "out_proj",), lambda: ConvWeight(sd[a + "out_proj.weight"], sd[a + "out_proj.bias"], prec, dev))
+        put(f"{i}.fc1", (p + "mlp.fc1",), lambda: ConvWeight(sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"], prec, dev))
+        put(f"{i}.fc2", (p + "mlp.fc2",), lambda: ConvWeight(sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"], prec, dev))
 
 
 def encoder_layer(P: Dict[str, Any], i: int, x: torch.Tensor, cfg, prec, eps: float, causal: bool) -> torch.Tensor:
@@ -120,6 +129,9 @@ class CLIPTextModel(HipModel):
     weights_name = "model.safetensors"
     _class_name = "CLIPTextModel"
     _projection = False
+    _lora_model = "text_encoder"
+    _lora_refusal = None
+    _lora_layers_prefix = "text_model.encoder.layers."      # the layers' Linears (the embeddings and the projection are no adapter targets)
 
     def __init__(self, config=None, precision="bf16", device="cuda", **kwargs):
         cfg = dict(_DEFAULTS)
@@ -175,6 +187,9 @@ class CLIPTextModel(HipModel):
     def _prepare(self, sd: Dict[str, torch.Tensor]) -> None:
         prec, dev = self.prec, self.device
         tdt = prec.compute if prec.half else F32
+        if self._only is not None:         # a selective rebuild (lora.py): only the layers' Linears are adapter targets
+            prepare_layers(self.P, sd, "text_model.encoder.layers.", self.config["num_hidden_layers"], prec, dev, only=self._only)
+            return
         P: Dict[str, Any] = {}
         P["token_embedding"] = sd["text_model.embeddings.token_embedding.weight"].to(dev, tdt).contiguous()
         P["position_embedding"] = sd["text_model.embeddings.position_embedding.weight"].to(dev, tdt).contiguous()
@@ -224,6 +239,7 @@ class CLIPTextModel(HipModel):
             raise hip.MfhipError("the text encoders are inference only: run them outside the training tape")
         if input_ids.dim() != 2:
             raise ValueError("input_ids is a [batch, seq] tensor of token ids")
+        self._lora_sync()
         if input_ids.shape[1] > self.config["max_position_embeddings"]:
             raise ValueError(f"sequence length {input_ids.shape[1]} exceeds max_position_embeddings "
                              f"{self.config['max_position_embeddings']}")

@@ -523,6 +523,8 @@ typedef struct mf_sched_row {
     mf_sched_op ops[MF_SCHED_MAX_OPS];
 } mf_sched_row;
 int mf_sizeof_sched_row(void);
+/* g < 0 means no classifier-free guidance, the convention of mf_cfg_ddim_step_dev: register 0 is eps_u as loaded, eps_c is never read
+ * and may be NULL.  With g >= 0 a NULL eps_c is MF_EINVAL (the message says so); nothing is launched. */
 int mf_sched_step_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row, int64_t n,
                       void* stream);
 /* mf_sched_step_dev with one more source of values, for samplers that add fresh noise at every step (DPM-Solver++ SDE): before the ops
@@ -535,7 +537,8 @@ int mf_sched_step_dev(const float* eps_u, const float* eps_c, float g, float* la
  * pairing stated there.  One thread is one block: per_sample % 4 == 0 is required (MF_EINVAL otherwise).  seed / offset / rng_state
  * follow mf_philox_normal: a non-null rng_state (device uint64 {seed, offset}) overrides the host pair, and the kernel never writes
  * it; the caller follows the launch with mf_philox_advance(rng_state, mf_philox_normal_blocks(global_batch, per_sample)) on the same
- * stream, which therefore runs after the kernel has read the state. */
+ * stream, which therefore runs after the kernel has read the state.  g < 0 as for mf_sched_step_dev: no guidance, register 0 is eps_u,
+ * eps_c may be NULL (and is MF_EINVAL when NULL with g >= 0). */
 /* (appended; MF_ABI_VERSION stays 23: no existing entry or struct changed) */
 int mf_sched_step_noise_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row,
                             int64_t n, int32_t noise_reg, int64_t per_sample, int64_t first_sample, int64_t global_batch, int64_t seed,

@@ -7,7 +7,7 @@ Sub-modules:
   ops        layer-level operators (conv2d / linear / attention / norms) over NHWC tensors
   models     BrushNetModel, UNet2DConditionModel, AutoencoderKL with the reference call surface
   schedulers DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler,
-             EulerAncestralDiscreteScheduler, DDPMScheduler (forward process only)
+             EulerAncestralDiscreteScheduler, LCMScheduler, DDPMScheduler (forward process only)
   autograd   the tape of hand-written vector-Jacobian products behind the training step
   training   MirrorFusionModel, training_loss, train_step (backward + clip + AdamW), checkpoint save / load hooks
   distributed  batch sharding for inference, bucketed gradient all-reduce (RCCL) for training
@@ -23,7 +23,7 @@ __version__ = "0.1.0"
 
 _LAZY = {
     "BrushNetModel": "models", "UNet2DConditionModel": "models", "AutoencoderKL": "models",
-    "BrushNetOutput": "models", "DDIMScheduler": "schedulers", "PNDMScheduler": "schedulers", "UniPCMultistepScheduler": "schedulers", "DPMSolverMultistepScheduler": "schedulers", "EulerDiscreteScheduler": "schedulers", "EulerAncestralDiscreteScheduler": "schedulers", "DDPMScheduler": "schedulers",
+    "BrushNetOutput": "models", "DDIMScheduler": "schedulers", "PNDMScheduler": "schedulers", "UniPCMultistepScheduler": "schedulers", "DPMSolverMultistepScheduler": "schedulers", "EulerDiscreteScheduler": "schedulers", "EulerAncestralDiscreteScheduler": "schedulers", "LCMScheduler": "schedulers", "DDPMScheduler": "schedulers",
     "MirrorFusionModel": "training", "compute_snr": "training", "training_loss": "training", "train_step": "training",
     "AdamW": "training", "save_state": "training", "load_state": "training", "run_sharded": "inference",
     "BatchFrontEnd": "training", "PreparedBatch": "training", "train_step_prepared": "training", "GraphedTrainStep": "training",

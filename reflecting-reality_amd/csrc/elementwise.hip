@@ -282,6 +282,8 @@ __global__ void axpby_kernel(AxpbyArgs a, float* y, int64_t n) {
 // mf_sched_step_noise_dev is the same body with NOISE: thread i holds elements [4i, 4i + 4), which are exactly Philox block `base + i` of
 // the draw (per_sample % 4 == 0, so the samples' streams are contiguous in blocks); its four normals go to register `reg` before the ops
 // run, through the same literal-index compare chain.  The generator's pair is read through scalar loads and never written.
+// GUIDED is compiled in: the unguided instantiations (g < 0 at the entry: no classifier-free guidance) take register 0 from eps_u as
+// loaded and issue no load for eps_c, which may be NULL; the guided ones are the code they were before the parameter existed.
 constexpr int kSchedRegs = MF_SCHED_MAX_REGS;
 
 struct SchedNoise {
@@ -297,7 +299,7 @@ __device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__bu
 // The register file is a local array of this one function and every index into it is a literal (fold expressions over Rs): SROA
 // keeps it in VGPRs.  (A helper taking the array by reference, or a loop over it, lets the optimizer turn the compare chain into a
 // load at a run-time offset first, and the array then lives in scratch.)
-template <bool NOISE, int... Rs>
+template <bool NOISE, bool GUIDED, int... Rs>
 __device__ __forceinline__ void sched_step_body(const f32x4_t* __restrict__ eu, const f32x4_t* __restrict__ ec, float g,
                                                 f32x4_t* __restrict__ lat, f32x4_t* __restrict__ state,
                                                 const mf_sched_row* __restrict__ row, int64_t n4, const SchedNoise& nz,
@@ -314,9 +316,13 @@ __device__ __forceinline__ void sched_step_body(const f32x4_t* __restrict__ eu, 
     const f32x4_t zero = {0.f, 0.f, 0.f, 0.f};
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         f32x4_t R[kSchedRegs];
-        const f32x4_t u = eu[i], c = ec[i];
+        if constexpr (GUIDED) {
+            const f32x4_t u = eu[i], c = ec[i];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) R[0][j] = __builtin_fmaf(g, c[j] - u[j], u[j]);
+            for (int j = 0; j < 4; ++j) R[0][j] = __builtin_fmaf(g, c[j] - u[j], u[j]);
+        } else {
+            R[0] = eu[i];
+        }
         R[1] = (ldm & 2u) ? lat[i] : zero;
         ((Rs >= 2 ? (R[Rs] = (Rs - 2 < nslots && ((ldm >> Rs) & 1u)) ? state[(int64_t)(Rs - 2) * n4 + i] : zero) : R[0]), ...);
         if constexpr (NOISE) {
@@ -353,16 +359,18 @@ __device__ __forceinline__ void sched_step_body(const f32x4_t* __restrict__ eu, 
     }
 }
 
+template <bool GUIDED>
 __global__ __launch_bounds__(256) void sched_step_kernel(const f32x4_t* __restrict__ eu, const f32x4_t* __restrict__ ec, float g,
                                                          f32x4_t* __restrict__ lat, f32x4_t* __restrict__ state,
                                                          const mf_sched_row* __restrict__ row, int64_t n4) {
-    sched_step_body<false>(eu, ec, g, lat, state, row, n4, SchedNoise{}, std::make_integer_sequence<int, kSchedRegs>{});
+    sched_step_body<false, GUIDED>(eu, ec, g, lat, state, row, n4, SchedNoise{}, std::make_integer_sequence<int, kSchedRegs>{});
 }
 
+template <bool GUIDED>
 __global__ __launch_bounds__(256) void sched_step_noise_kernel(const f32x4_t* __restrict__ eu, const f32x4_t* __restrict__ ec, float g,
                                                                f32x4_t* __restrict__ lat, f32x4_t* __restrict__ state,
                                                                const mf_sched_row* __restrict__ row, int64_t n4, const SchedNoise nz) {
-    sched_step_body<true>(eu, ec, g, lat, state, row, n4, nz, std::make_integer_sequence<int, kSchedRegs>{});
+    sched_step_body<true, GUIDED>(eu, ec, g, lat, state, row, n4, nz, std::make_integer_sequence<int, kSchedRegs>{});
 }
 
 // Training loss (train_brushnet_mirror.py:1433-1449): per-sample mean((pred - target)^2) * weight, then the
@@ -616,14 +624,19 @@ static int sched_step_grid(int64_t n4, const char* name, int* grid) {
 
 extern "C" int mf_sched_step_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row,
                                  int64_t n, void* stream) {
-    MF_CHECK_ARG(eps_u && eps_c && latents && row && n > 0 && n % 4 == 0, "mf_sched_step_dev: bad arguments (n %% 4 == 0 needed)");
-    MF_CHECK_ARG(mf_aligned16(eps_u) && mf_aligned16(eps_c) && mf_aligned16(latents) && (!state || mf_aligned16(state)),
+    MF_CHECK_ARG(eps_u && latents && row && n > 0 && n % 4 == 0, "mf_sched_step_dev: bad arguments (n %% 4 == 0 needed)");
+    MF_CHECK_ARG(g < 0.0f || eps_c, "mf_sched_step_dev: eps_c is NULL but g = %g asks for guidance (g < 0 means none: register 0 is eps_u)", (double)g);
+    MF_CHECK_ARG(mf_aligned16(eps_u) && (g < 0.0f || mf_aligned16(eps_c)) && mf_aligned16(latents) && (!state || mf_aligned16(state)),
                  "mf_sched_step_dev: tensors must be 16-byte aligned");
     const int64_t n4 = n / 4;
     int grid = 0;
     if (int rc = sched_step_grid(n4, "mf_sched_step_dev", &grid)) return rc;
-    hipLaunchKernelGGL(sched_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
-                       (const f32x4_t*)eps_c, g, (f32x4_t*)latents, (f32x4_t*)state, row, n4);
+    if (g < 0.0f)
+        hipLaunchKernelGGL(sched_step_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
+                           (const f32x4_t*)nullptr, g, (f32x4_t*)latents, (f32x4_t*)state, row, n4);
+    else
+        hipLaunchKernelGGL(sched_step_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
+                           (const f32x4_t*)eps_c, g, (f32x4_t*)latents, (f32x4_t*)state, row, n4);
     MF_CHECK_LAUNCH("mf_sched_step_dev");
     return MF_OK;
 }
@@ -631,8 +644,9 @@ extern "C" int mf_sched_step_dev(const float* eps_u, const float* eps_c, float g
 extern "C" int mf_sched_step_noise_dev(const float* eps_u, const float* eps_c, float g, float* latents, float* state, const mf_sched_row* row,
                                        int64_t n, int32_t noise_reg, int64_t per_sample, int64_t first_sample, int64_t global_batch,
                                        int64_t seed, int64_t offset, const uint64_t* rng_state, void* stream) {
-    MF_CHECK_ARG(eps_u && eps_c && latents && row && n > 0 && n % 4 == 0, "mf_sched_step_noise_dev: bad arguments (n %% 4 == 0 needed)");
-    MF_CHECK_ARG(mf_aligned16(eps_u) && mf_aligned16(eps_c) && mf_aligned16(latents) && (!state || mf_aligned16(state)),
+    MF_CHECK_ARG(eps_u && latents && row && n > 0 && n % 4 == 0, "mf_sched_step_noise_dev: bad arguments (n %% 4 == 0 needed)");
+    MF_CHECK_ARG(g < 0.0f || eps_c, "mf_sched_step_noise_dev: eps_c is NULL but g = %g asks for guidance (g < 0 means none: register 0 is eps_u)", (double)g);
+    MF_CHECK_ARG(mf_aligned16(eps_u) && (g < 0.0f || mf_aligned16(eps_c)) && mf_aligned16(latents) && (!state || mf_aligned16(state)),
                  "mf_sched_step_noise_dev: tensors must be 16-byte aligned");
     MF_CHECK_ARG(noise_reg >= 2 && noise_reg < MF_SCHED_MAX_REGS, "mf_sched_step_noise_dev: noise_reg %d outside [2, %d)", noise_reg,
                  MF_SCHED_MAX_REGS);
@@ -650,8 +664,12 @@ extern "C" int mf_sched_step_noise_dev(const float* eps_u, const float* eps_c, f
     nz.reg = noise_reg;
     nz.first_block = (uint64_t)first_sample * (uint64_t)(per_sample / 4);
     nz.seed = (uint64_t)seed; nz.offset = (uint64_t)offset; nz.state = rng_state;
-    hipLaunchKernelGGL(sched_step_noise_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
-                       (const f32x4_t*)eps_c, g, (f32x4_t*)latents, (f32x4_t*)state, row, n4, nz);
+    if (g < 0.0f)
+        hipLaunchKernelGGL(sched_step_noise_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
+                           (const f32x4_t*)nullptr, g, (f32x4_t*)latents, (f32x4_t*)state, row, n4, nz);
+    else
+        hipLaunchKernelGGL(sched_step_noise_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4_t*)eps_u,
+                           (const f32x4_t*)eps_c, g, (f32x4_t*)latents, (f32x4_t*)state, row, n4, nz);
     MF_CHECK_LAUNCH("mf_sched_step_noise_dev");
     return MF_OK;
 }

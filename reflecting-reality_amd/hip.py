@@ -1305,14 +1305,15 @@ def axpby_n(xs, coefs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     return out
 
 
-def sched_step_dev(eps_u: torch.Tensor, eps_c: torch.Tensor, g: float, latents: torch.Tensor, state: Optional[torch.Tensor],
+def sched_step_dev(eps_u: torch.Tensor, eps_c: Optional[torch.Tensor], g: float, latents: torch.Tensor, state: Optional[torch.Tensor],
                    row: torch.Tensor) -> torch.Tensor:
     """One multistep-scheduler step on the device (mf_sched_step_dev): the guided noise prediction, then the ops of `row` (the
     step's mf_sched_row in device memory, schedulers.device_plan) on `latents` (updated in place) and `state` ([nslots, *latents.shape]
-    fp32, the history kept between steps)."""
+    fp32, the history kept between steps).  `g < 0`: no guidance, register 0 is `eps_u` as loaded and `eps_c` may be None (the
+    convention of cfg_ddim_step_dev); `eps_c=None` with `g >= 0` is the library's argument error."""
     _req_cuda(eps_u, eps_c, latents, state, row)
     n = latents.numel()
-    if eps_u.numel() != n or eps_c.numel() != n or (state is not None and state.numel() % n) or row.numel() * row.element_size() < C.sizeof(SchedRow):
+    if eps_u.numel() != n or (eps_c is not None and eps_c.numel() != n) or (state is not None and state.numel() % n) or row.numel() * row.element_size() < C.sizeof(SchedRow):
         raise MfhipError("sched_step_dev: mismatched sizes")
     for t in (eps_u, eps_c, latents, state, row):
         if t is not None and (not t.is_contiguous() or (t.dtype != torch.float32 and t is not row)):
@@ -1321,16 +1322,16 @@ def sched_step_dev(eps_u: torch.Tensor, eps_c: torch.Tensor, g: float, latents: 
     return latents
 
 
-def sched_step_noise_dev(eps_u: torch.Tensor, eps_c: torch.Tensor, g: float, latents: torch.Tensor, state: Optional[torch.Tensor],
+def sched_step_noise_dev(eps_u: torch.Tensor, eps_c: Optional[torch.Tensor], g: float, latents: torch.Tensor, state: Optional[torch.Tensor],
                          row: torch.Tensor, noise_reg: int, seed: int = 0, offset: int = 0, first_sample: int = 0,
                          global_batch: Optional[int] = None, rng_state: Optional[torch.Tensor] = None) -> torch.Tensor:
     """sched_step_dev for a row that reads a step's noise (mf_sched_step_noise_dev): register `noise_reg` (plan.noise_reg of
     schedulers.device_plan) holds standard normals drawn in the kernel, bit for bit philox_normal(latents.shape, seed, offset, ...,
     first_sample, global_batch); `rng_state` (PhiloxGenerator.device_state()) overrides (seed, offset) and is not written: follow the
-    launch with philox_advance(rng_state, philox_normal_blocks(global_batch, per_sample))."""
+    launch with philox_advance(rng_state, philox_normal_blocks(global_batch, per_sample)).  `g < 0` / `eps_c=None`: as sched_step_dev."""
     _req_cuda(eps_u, eps_c, latents, state, row, rng_state)
     n = latents.numel()
-    if latents.dim() < 1 or eps_u.numel() != n or eps_c.numel() != n or (state is not None and state.numel() % n) \
+    if latents.dim() < 1 or eps_u.numel() != n or (eps_c is not None and eps_c.numel() != n) or (state is not None and state.numel() % n) \
             or row.numel() * row.element_size() < C.sizeof(SchedRow):
         raise MfhipError("sched_step_noise_dev: mismatched sizes")
     for t in (eps_u, eps_c, latents, state, row):

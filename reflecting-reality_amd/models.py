@@ -177,6 +177,8 @@ class HipModel(LoraMixin):
         optimizer updates them in place every step, so nothing is pre-split or fused) plus, when the model trains, a
         gradient arena of the same layout.  Precision must keep fp32 storage ('fp32', 'f16x3', or 'bf16x1': the arithmetic
         of the reference's --mixed_precision=bf16)."""
+        if self.config.get("time_cond_proj_dim") is not None:
+            raise NotImplementedError("time_cond_proj_dim (the guidance-scale embedding of a distilled UNet) has no training layout")
         if self._lora_state() is not None:
             raise NotImplementedError("prepare_training() with LoRA adapters loaded: they are merged into the inference layouts, and "
                                       "training LoRA layers is not built; unload_lora() first")
@@ -539,6 +541,14 @@ class _UNetCore(HipModel):
                            ("add2", "add_embedding.linear_2")):
             if (only is None or name in only) and (attr[0] == "t" or self.config["addition_embed_type"] == "text_time"):
                 setattr(self, attr, self._conv(sd, name, f32))
+        # a guidance-distilled UNet (LCM): TimestepEmbedding.cond_proj (embeddings.py:225-254), a bias-free Linear on the w-embedding
+        if self.config.get("time_cond_proj_dim") is not None:
+            if self.training:
+                raise NotImplementedError("time_cond_proj_dim (the guidance-scale embedding of a distilled UNet) has no training layout")
+            if only is None or "time_embedding.cond_proj" in only:
+                self.te_cond = self._conv(sd, "time_embedding.cond_proj", f32)
+        elif only is None:
+            self.te_cond = None
         # all time_emb_proj layers as ONE [sum(Cout), temb] GEMM; each resnet reads a column slice
         names = [k[: -len(".time_emb_proj.weight")] for k in self.param_shapes() if k.endswith(".time_emb_proj.weight")]
         if only is not None and not any(n + ".time_emb_proj" in only for n in names):
@@ -625,10 +635,12 @@ class _UNetCore(HipModel):
         self.tdepth[p] = i
 
     # ---- forward pieces ---------------------------------------------------------------------------
-    def _time_embedding(self, timestep, batch: int, added_cond_kwargs=None) -> torch.Tensor:
+    def _time_embedding(self, timestep, batch: int, added_cond_kwargs=None, timestep_cond=None) -> torch.Tensor:
         """Timesteps + TimestepEmbedding (+ SDXL's text_time add_embedding, unet_2d_condition.py:971-987) + every
         resnet's time_emb_proj(SiLU(emb)) -> [batch, sum(Cout)] fp32.
-        (embeddings.py:27-67,225-254; resnet.py:369-376).  Always fp32, like the reference."""
+        (embeddings.py:27-67,225-254; resnet.py:369-376).  Always fp32, like the reference.  `timestep_cond` ([1 | batch,
+        time_cond_proj_dim]): cond_proj(timestep_cond) is added to the sinusoid before linear_1 (embeddings.py:245-246), as the residual
+        of that one GEMM."""
         if not torch.is_tensor(timestep):
             t = torch.full((batch,), float(timestep), dtype=F32, device=self.device)
         else:
@@ -638,6 +650,20 @@ class _UNetCore(HipModel):
             t = t.contiguous()
         c0 = self.config["block_out_channels"][0]
         e = hip.timestep_embedding(t, c0, self.config["flip_sin_to_cos"], float(self.config["freq_shift"]))
+        if timestep_cond is not None:
+            te_cond = getattr(self, "te_cond", None)
+            if te_cond is None:
+                raise ValueError(f"{type(self).__name__}: `timestep_cond` needs the config key `time_cond_proj_dim` (and its weight "
+                                 "time_embedding.cond_proj.weight)")
+            if ops.TAPE is not None:
+                raise NotImplementedError("training with timestep_cond is not built")
+            cond = timestep_cond.to(self.device, F32).reshape(-1, timestep_cond.shape[-1])
+            if cond.shape[0] not in (1, batch) or cond.shape[1] != self.config["time_cond_proj_dim"]:
+                raise ValueError(f"timestep_cond is {tuple(timestep_cond.shape)}: [{batch}, {self.config['time_cond_proj_dim']}] expected")
+            cond = cond.expand(batch, -1)
+            if te_cond.cin_pad != cond.shape[1]:
+                cond = torch.nn.functional.pad(cond, (0, te_cond.cin_pad - cond.shape[1]))
+            e = ops.linear(cond.contiguous(), te_cond, res0=e, out_dtype=F32)
         if ops.TAPE is not None:           # training: every activation is its own differentiated operator
             if self.add1 is not None:
                 raise NotImplementedError("training the SDXL text_time embedding is not built")
@@ -666,23 +692,29 @@ class _UNetCore(HipModel):
         e = ops.linear(a, self.add2, res0=e, act=hip.ACT_SILU, out_dtype=F32)
         return ops.linear(e, self.temb_proj, out_dtype=F32)
 
-    def time_embedding_table(self, timesteps: torch.Tensor, batch: int, added_cond_kwargs=None) -> torch.Tensor:
+    def time_embedding_table(self, timesteps: torch.Tensor, batch: int, added_cond_kwargs=None, timestep_cond=None) -> torch.Tensor:
         """Every resnet's time_emb_proj(SiLU(time_embedding(t))) for ALL timesteps of a schedule in one batched pass
         (the timesteps are known after set_timesteps; resnet.py:369-376) -> [steps, rows, sum(Cout)] fp32.
         rows = 1 when the embedding depends on the timestep alone (SD1.5: every image of the batch reads the same row,
-        `forward(..., _temb=table[i])`), rows = batch with SDXL's per-image text_time embedding."""
+        `forward(..., _temb=table[i])`), rows = batch with SDXL's per-image text_time embedding or a per-image `timestep_cond`
+        (the guidance-scale embedding of a distilled UNet, [1 | batch, time_cond_proj_dim]): the table carries it, forward(_temb=) needs it no more."""
         t = timesteps.to(self.device, F32).reshape(-1)
         steps = t.numel()
-        if self.add1 is None:
+        if self.add1 is None and timestep_cond is None:
             return self._time_embedding(t, steps, None).view(steps, 1, -1)
-        added = {k: v.to(self.device, F32).repeat(steps, *([1] * (v.dim() - 1))) for k, v in added_cond_kwargs.items()}
-        return self._time_embedding(t.repeat_interleave(batch), steps * batch, added).view(steps, batch, -1)
+        added = cond = None
+        if self.add1 is not None:
+            added = {k: v.to(self.device, F32).repeat(steps, *([1] * (v.dim() - 1))) for k, v in added_cond_kwargs.items()}
+        if timestep_cond is not None:
+            cond = timestep_cond.to(self.device, F32).reshape(-1, timestep_cond.shape[-1])
+            cond = (cond.expand(batch, -1) if cond.shape[0] == 1 else cond).repeat(steps, 1)
+        return self._time_embedding(t.repeat_interleave(batch), steps * batch, added, cond).view(steps, batch, -1)
 
-    def _temb_rows(self, temb: Optional[torch.Tensor], timestep, bsz: int, added_cond_kwargs) -> torch.Tensor:
+    def _temb_rows(self, temb: Optional[torch.Tensor], timestep, bsz: int, added_cond_kwargs, timestep_cond=None) -> torch.Tensor:
         """The [bsz, sum(Cout)] time-embedding rows of one forward pass: computed here, or a precomputed row block of
         time_embedding_table (one shared row is broadcast with a zero row stride: mf_gemm_desc.ld_temb = 0)."""
         if temb is None:
-            return self._time_embedding(timestep, bsz, added_cond_kwargs)
+            return self._time_embedding(timestep, bsz, added_cond_kwargs, timestep_cond)
         if ops.TAPE is not None:
             raise hip.MfhipError("training differentiates its own time embedding: _temb is an inference input")
         if temb.shape[0] not in (1, bsz):
@@ -1442,6 +1474,8 @@ class UNet2DConditionModel(_UNetCore):
         depth = _as_tuple(c["transformer_layers_per_block"], len(boc))
         out["conv_in.weight"] = (boc[0], c["in_channels"], 3, 3); out["conv_in.bias"] = (boc[0],)
         out["time_embedding.linear_1.weight"] = (temb, boc[0]); out["time_embedding.linear_1.bias"] = (temb,)
+        if c.get("time_cond_proj_dim") is not None:                  # TimestepEmbedding.cond_proj: Linear(time_cond_proj_dim, in), no bias
+            out["time_embedding.cond_proj.weight"] = (boc[0], int(c["time_cond_proj_dim"]))
         out["time_embedding.linear_2.weight"] = (temb, temb); out["time_embedding.linear_2.bias"] = (temb,)
         _add_embedding_shapes(out, c, temb)
         lpb = c["layers_per_block"]
@@ -1533,10 +1567,11 @@ class UNet2DConditionModel(_UNetCore):
                 mid_block_add_sample: Optional[torch.Tensor] = None,
                 up_block_add_samples: Optional[List[torch.Tensor]] = None, *, _temb: Optional[torch.Tensor] = None):
         """unet_2d_condition.py:1039-1348.  `down_block_add_samples` / `up_block_add_samples` are consumed with
-        pop(0) exactly like the reference does (the caller's lists are emptied)."""
+        pop(0) exactly like the reference does (the caller's lists are emptied).  `timestep_cond` (config `time_cond_proj_dim`): the
+        guidance-scale embedding of a distilled UNet, added inside the time embedding (:1083-1091)."""
         if not self._ready:
             raise RuntimeError("UNet2DConditionModel has no parameters loaded")
-        if any(v is not None for v in (class_labels, timestep_cond, attention_mask,
+        if any(v is not None for v in (class_labels, attention_mask,
                                        down_block_additional_residuals, mid_block_additional_residual,
                                        down_intrablock_additional_residuals, encoder_attention_mask)) \
                 or (cross_attention_kwargs not in (None, {}) and self._lora_state() is None):
@@ -1549,7 +1584,7 @@ class UNet2DConditionModel(_UNetCore):
         is_brushnet = down_block_add_samples is not None and mid_block_add_sample is not None \
             and up_block_add_samples is not None                                                    # :1202
         bsz = sample.shape[0]
-        temb = self._temb_rows(_temb, timestep, bsz, added_cond_kwargs)
+        temb = self._temb_rows(_temb, timestep, bsz, added_cond_kwargs, timestep_cond)       # (a `_temb` row block carries timestep_cond already)
         ehs = self._bind_prompt(encoder_hidden_states)
         x = from_nchw(sample.to(self.device), self.prec, self.cin_pad)
         if ops.TAPE is not None:

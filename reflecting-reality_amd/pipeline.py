@@ -32,7 +32,7 @@ from . import hip
 from . import lora as _lora
 from .models import AutoencoderKL, BrushNetModel, UNet2DConditionModel
 from .rng import PhiloxGenerator, is_philox, randn_tensor
-from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, PNDMScheduler,
+from .schedulers import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, LCMScheduler, PNDMScheduler,
                          UniPCMultistepScheduler, device_plan)
 
 try:
@@ -162,7 +162,10 @@ class _DevicePlan:
     reads a step's noise (DPM-Solver++ SDE) takes a rng.PhiloxGenerator: mf_sched_step_noise_dev draws the noise in the kernel from the
     generator's device state and mf_philox_advance moves that state, both inside the graph; the host pair follows per replayed step.
     Euler / Euler-ancestral: the plan keeps the sample in slot `plan.x_slot` and every row ends by writing the next step's model input
-    into the latents; attach() starts the run (x0 into the slot, x0 * plan.first_scale into the latents: one launch)."""
+    into the latents; attach() starts the run (x0 into the slot, x0 * plan.first_scale into the latents: one launch).
+    LCM: a noisy plan whose last row reads no noise (plan.draws); the one captured step still draws and advances there, so the host pair
+    stays where the host's step() leaves it and the generator's device state is brought level again on its next use.  Without
+    classifier-free guidance launch() gets ec=None and hands the kernels g < 0: register 0 is the noise prediction as the UNet wrote it."""
 
     def __init__(self, pipe, g, nsteps, generator=None):
         self.sched, self.g = pipe.scheduler, float(g)
@@ -203,18 +206,24 @@ class _DevicePlan:
             hip.axpby_n([self.x], [self.plan.first_scale], out=lat)
             self.sched.model_input_prescaled = True          # (scale_model_input inside the step body: the identity; finish() clears it)
 
-    def load(self, i): self.row_cur.copy_(self.rows[i])
+    def load(self, i):
+        self.i = i
+        self.row_cur.copy_(self.rows[i])
 
     def launch(self, eu, ec, lat):
+        g = self.g if ec is not None else -1.0    # (no classifier-free guidance: the kernels' g < 0 form, eps_c is not read)
         if self.gen is None:
-            hip.sched_step_dev(eu, ec, self.g, lat, self.state, self.row_cur)
+            hip.sched_step_dev(eu, ec, g, lat, self.state, self.row_cur)
         else:                                     # (same stream: the advance runs after the kernel has read the state)
-            hip.sched_step_noise_dev(eu, ec, self.g, lat, self.state, self.row_cur, self.plan.noise_reg, rng_state=self.rng_state)
+            hip.sched_step_noise_dev(eu, ec, g, lat, self.state, self.row_cur, self.plan.noise_reg, rng_state=self.rng_state)
             hip.philox_advance(self.rng_state, self.blocks)
 
     def after_replay(self, t, lat):
         if self.gen is not None:
-            self.gen.note_advanced(self.blocks, on_device=True)
+            if self.plan.draws[self.i]:
+                self.gen.note_advanced(self.blocks, on_device=True)
+            else:                                 # the row read no noise: the host pair stays, the device state has moved past it
+                self.gen.device_moved()
 
     def sample(self, lat): return lat if self.x is None else self.x
 
@@ -267,7 +276,7 @@ class _HostStep:
             sched.model_input_prescaled = True    # (scale_model_input inside the step body: the identity; finish() clears it)
 
     def load(self, i): pass
-    def launch(self, eu, ec, lat): self.eps.copy_(hip.cfg_combine(eu, ec, self.g))                  # :1310-1312
+    def launch(self, eu, ec, lat): self.eps.copy_(eu if ec is None else hip.cfg_combine(eu, ec, self.g))    # :1310-1312
 
     # (multistep schedulers keep references to their inputs (ets, last_sample): hand them copies, not the graph's static buffers)
     def after_replay(self, t, lat):
@@ -348,7 +357,7 @@ class StableDiffusionBrushNetPipeline:
 
     # ---- loading / saving (pipelines/pipeline_utils.py:148-296 save_pretrained, :465-919 from_pretrained) ---------
     _scheduler_classes = ("DDIMScheduler", "PNDMScheduler", "UniPCMultistepScheduler", "DPMSolverMultistepScheduler",
-                          "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler")
+                          "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler", "LCMScheduler")
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, torch_dtype=None, device="cuda", **kwargs):
@@ -504,7 +513,25 @@ class StableDiffusionBrushNetPipeline:
 
     @property
     def do_classifier_free_guidance(self):
-        return self._guidance_scale > 1
+        """pipeline_brushnet.py:~835: a UNet with `time_cond_proj_dim` (guidance-distilled, LCM) takes the guidance scale as an embedding
+        and never runs the doubled batch."""
+        return self._guidance_scale > 1 and self.unet.config.get("time_cond_proj_dim") is None
+
+    def get_guidance_scale_embedding(self, w: torch.Tensor, embedding_dim: int = 512, dtype=torch.float32) -> torch.Tensor:
+        """pipeline_brushnet.py:795-822 (https://github.com/google-research/vdm model_vdm.py#L298): the sinusoidal embedding
+        [len(w), embedding_dim] of the guidance scales `w` (1-D), zero-padded by one column when embedding_dim is odd.  Host arithmetic,
+        once per call."""
+        assert len(w.shape) == 1
+        w = w * 1000.0
+        half_dim = embedding_dim // 2
+        emb = torch.log(torch.tensor(10000.0)) / (half_dim - 1)
+        emb = torch.exp(torch.arange(half_dim, dtype=dtype) * -emb)
+        emb = w.to(dtype)[:, None] * emb[None, :]
+        emb = torch.cat([torch.sin(emb), torch.cos(emb)], dim=1)
+        if embedding_dim % 2 == 1:
+            emb = torch.nn.functional.pad(emb, (0, 1))
+        assert emb.shape == (w.shape[0], embedding_dim)
+        return emb
 
     @property
     def num_timesteps(self):
@@ -729,9 +756,9 @@ class StableDiffusionBrushNetPipeline:
             for m in lora_models:
                 m.set_lora_scale(1.0 if lora_scale is None else lora_scale)
                 m._lora_sync()
-        if timesteps is not None:
+        if timesteps is not None and "timesteps" not in inspect.signature(self.scheduler.set_timesteps).parameters:
             # retrieve_timesteps (pipeline_brushnet.py:113-119): the reference's DDIM / PNDM / UniPC `set_timesteps` take no custom
-            # schedule either and the reference raises exactly this
+            # schedule either and the reference raises exactly this (LCMScheduler's takes one: below)
             raise ValueError(f"The current scheduler class {self.scheduler.__class__}'s `set_timesteps` does not support custom"
                              f" timestep schedules. Please check whether you are using the correct scheduler.")
         if guess_mode and type(self) is not StableDiffusionBrushNetPipeline:
@@ -776,7 +803,11 @@ class StableDiffusionBrushNetPipeline:
                                              conditioning_noise, normals, generator)
         once = self._brushnet_once = (not guess_mode) and self._brushnet_shareable(cond, nb, do_cfg, identical)
 
-        self.scheduler.set_timesteps(num_inference_steps, device=self.device)                       # :1171
+        if timesteps is not None:                                                                   # retrieve_timesteps :113-125
+            self.scheduler.set_timesteps(timesteps=timesteps, device=self.device)
+            num_inference_steps = len(self.scheduler.timesteps)
+        else:
+            self.scheduler.set_timesteps(num_inference_steps, device=self.device)                   # :1171
         ts = self.scheduler.timesteps
         if _end is not None and isinstance(_end, float) and 0.0 < _end < 1.0:                        # pipeline_brushnet_sd_xl.py:1376-1391
             ntrain = int(self.scheduler.config["num_train_timesteps"])
@@ -785,6 +816,10 @@ class StableDiffusionBrushNetPipeline:
             ts = ts[:num_inference_steps]
         self._num_timesteps = len(ts)
         latents, _ = self.prepare_latents(nb, self.unet.config["in_channels"], height, width, generator, latents)
+        timestep_cond = None                 # :1218-1223: the guidance scale as an embedding, for the UNet only (BrushNet never sees it, :1277)
+        if self.unet.config.get("time_cond_proj_dim") is not None:
+            timestep_cond = self.get_guidance_scale_embedding(torch.tensor(self.guidance_scale - 1).repeat(nb),
+                                                              embedding_dim=self.unet.config["time_cond_proj_dim"]).to(self.device, torch.float32)
 
         keep = [1.0 - float(i / len(ts) < control_guidance_start or (i + 1) / len(ts) > control_guidance_end)
                 for i in range(len(ts))]                                                             # :1236-1242
@@ -796,19 +831,23 @@ class StableDiffusionBrushNetPipeline:
             _timing["denoise_end"] = torch.cuda.Event(enable_timing=True)
             _timing["denoise_start"].record()
         fused_ddim = do_cfg and isinstance(self.scheduler, DDIMScheduler) and eta == 0.0 and rescale == 0.0
-        use_graph = (self.use_hip_graph and do_cfg and callback is None and (fused_ddim or eta == 0.0) and rescale == 0.0
+        # (without classifier-free guidance the captured step serves LCMScheduler, whose calls run there by design; the other samplers'
+        # unguided calls keep the eager loop they have always had)
+        use_graph = (self.use_hip_graph and (do_cfg or isinstance(self.scheduler, LCMScheduler)) and callback is None
+                     and (fused_ddim or eta == 0.0) and rescale == 0.0
                      and all(k == 1.0 for k in keep) and len(ts) > 2 and not guess_mode)
         # THE place that decides how a step ends.  PNDM / UniPC / DPM-Solver++ / Euler update on the device (one plan row per step) unless
         # a callback may read the scheduler between steps, or an eps-form step program is being exported; the eager loop always steps them
         # on the host.  The SDE type of DPM-Solver++ and Euler-ancestral draw noise at every step: on the device only from ONE
         # rng.PhiloxGenerator (the library's stream, which the kernel can draw); a torch.Generator, none, or a list of generators steps on
-        # the host.
-        sde = isinstance(self.scheduler, EulerAncestralDiscreteScheduler) or (
+        # the host.  LCM draws too (every step but the last).
+        sde = isinstance(self.scheduler, (EulerAncestralDiscreteScheduler, LCMScheduler)) or (
             isinstance(self.scheduler, DPMSolverMultistepScheduler) and self.scheduler.config["algorithm_type"] == "sde-dpmsolver++")
         if fused_ddim:
             update = _FusedDDIM(self, guidance_scale)
         elif (use_graph and callback_on_step_end is None and not (_export is not None and _export["scheduler"] == "host")
-              and isinstance(self.scheduler, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler))
+              and isinstance(self.scheduler, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler,
+                                              LCMScheduler))
               and (not sde or isinstance(generator, PhiloxGenerator))):
             update = _DevicePlan(self, guidance_scale, len(ts), generator if sde else None)
         else:
@@ -824,14 +863,14 @@ class StableDiffusionBrushNetPipeline:
         with self.progress_bar(total=num_inference_steps) as bar:
             if use_graph:
                 latents = self._denoise_graph(latents, ts, pe, pe_u, cond, nb, guidance_scale, float(brushnet_conditioning_scale), once,
-                                              _added, update, step_end, bar, _export)
+                                              _added, update, step_end, bar, _export, do_cfg, timestep_cond)
                 ts = []
             for i, t in enumerate(ts):                                                               # :1250 HOT LOOP
                 # step 0 autotunes GEMM tiles: keep its timings undisturbed; guess_mode re-packs the residuals on this
                 # stream (the per-residual events are keyed by the tensors BrushNet returned)
                 self._overlap(i > 0 and not guess_mode)
                 eu, ec = self._predict_noise(latents, t, pe, pe_u, cond, nb, float(brushnet_conditioning_scale) * keep[i], do_cfg, once,
-                                             guess_mode, _added)
+                                             guess_mode, _added, timestep_cond=timestep_cond)
                 latents = step_end(i, t, update.eager(eu, ec, t, latents))
                 if i == len(ts) - 1 or ((i + 1) > num_warmup and (i + 1) % self.scheduler.order == 0):
                     bar.update()
@@ -888,12 +927,14 @@ class StableDiffusionBrushNetPipeline:
                              + (f" or the two guidance halves stacked ({2 * batch})" if do_cfg else ""))
         return torch.cat([pe, torch.cat([t.repeat_interleave(per_prompt, dim=0) for t in parts])], 1).contiguous()
 
-    def _predict_noise(self, latents, t, pe, pe_u, cond, nb, cond_scale, do_cfg, once, guess_mode, added, temb=(None, None), lazy=None):
+    def _predict_noise(self, latents, t, pe, pe_u, cond, nb, cond_scale, do_cfg, once, guess_mode, added, temb=(None, None), lazy=None,
+                       timestep_cond=None):
         """The body of a denoise step up to the scheduler update (pipeline_brushnet.py:1256-1296), for the eager loop and for the
         captured step alike: BrushNet, the UNet with its residuals, and the noise prediction's (unconditional, conditional) halves —
         (eps, None) without classifier-free guidance.  `once` / `guess_mode`: BrushNet sees one half of the batch (the halves are identical
         / the conditional one, :1260-1264); `pe_u`: the UNet's own prompt embeddings; `temb`: the step's rows of the (UNet's, BrushNet's)
-        time-embedding tables; `lazy`: unet.lazy_injection_names()."""
+        time-embedding tables; `lazy`: unet.lazy_injection_names(); `timestep_cond`: the UNet's guidance-scale embedding (a `temb` row block
+        holds it already)."""
         x_in = torch.cat([latents] * 2) if do_cfg else latents                                       # :1256
         x_in = self.scheduler.scale_model_input(x_in, t)          # (returns its input for DDIM / PNDM / UniPC: no launch)
         cond_only = guess_mode and do_cfg
@@ -906,7 +947,8 @@ class StableDiffusionBrushNetPipeline:
             mid = torch.cat([torch.zeros_like(mid), mid])
             up = [torch.cat([torch.zeros_like(u), u]) for u in up]
         eps = self.unet(x_in, t, encoder_hidden_states=pe_u, down_block_add_samples=down, mid_block_add_sample=mid,
-                        up_block_add_samples=up, added_cond_kwargs=added, return_dict=False, _temb=temb[0])[0]                       # :1296
+                        up_block_add_samples=up, added_cond_kwargs=added, return_dict=False, _temb=temb[0],
+                        timestep_cond=timestep_cond if temb[0] is None else None)[0]                                                 # :1296
         return (eps[:nb], eps[nb:]) if do_cfg else (eps, None)
 
     def _brushnet_shareable(self, cond: torch.Tensor, nb: int, do_cfg: bool, identical: Optional[bool] = None) -> bool:
@@ -952,14 +994,17 @@ class StableDiffusionBrushNetPipeline:
             self.brushnet.side_stream = None
             self.unet.aux_stream = self.brushnet.aux_stream = None
 
-    def _denoise_graph(self, latents, ts, pe, pe_u, cond, nb, guidance_scale, cond_scale, once, added, update, step_end, bar, export=None):
+    def _denoise_graph(self, latents, ts, pe, pe_u, cond, nb, guidance_scale, cond_scale, once, added, update, step_end, bar, export=None,
+                       do_cfg=True, timestep_cond=None):
         """The hot loop as ONE captured hipGraph replayed per timestep (BrushNet + UNet + CFG + what `update` launches, ~800
         kernels on two streams): launch overhead disappears and the host only refreshes two tiny device buffers
         (timestep, the update's row) between replays.  DDIM's update is inside the graph (_FusedDDIM); so is that of the multistep
         schedulers (_DevicePlan), unless a callback_on_step_end may read the scheduler between steps or an eps-form step program is
         exported: then they get the guided noise prediction from the graph and step eagerly (_HostStep).  `export`: the request of
         export_denoise_step, the capture of step 1 is recorded as a program too.  The first step runs eagerly: it autotunes GEMM tiles,
-        binds the prompt (cross-attention K/V cache) and sizes every scratch buffer before anything is captured."""
+        binds the prompt (cross-attention K/V cache) and sizes every scratch buffer before anything is captured.  `do_cfg`: False runs the
+        step on the undoubled batch (LCMScheduler's calls at guidance_scale <= 1 or on a guidance-distilled UNet, whose `timestep_cond`
+        enters the UNet's time-embedding table) and hands the update ec=None; part of the graph's key."""
         dev = latents.device
         tvals = ts.to(torch.float32).to(dev)
         ip = pe_u is not pe                                   # the 'ip_adapter' normals mode: the UNet reads its own embeddings
@@ -970,7 +1015,8 @@ class StableDiffusionBrushNetPipeline:
         key = (tuple(latents.shape), tuple(pe.shape), tuple(cond.shape), float(guidance_scale), cond_scale, update.key,
                str(dev), id(self.unet), self.unet._weights_gen, id(self.brushnet), self.brushnet._weights_gen, once,
                tuple((k, tuple(v.shape)) for k, v in sorted(added.items())) if added else None,
-               tuple(pe_u.shape) if ip else None, self.unet.ip_signature() if hasattr(self.unet, "ip_signature") else None)
+               tuple(pe_u.shape) if ip else None, self.unet.ip_signature() if hasattr(self.unet, "ip_signature") else None,
+               bool(do_cfg), timestep_cond is not None)
         st = self._graph_state if self._graph_state is not None and self._graph_state["key"] == key else None
         if st is None:
             st = dict(key=key, graph=None, lat=torch.empty_like(latents), pe=torch.empty_like(pe),
@@ -988,10 +1034,11 @@ class StableDiffusionBrushNetPipeline:
         # every timestep is known here: both nets' time embeddings and the fused time_emb_proj GEMM run ONCE for
         # the whole schedule (4 batched launches per net) instead of 8 dependent launches at the head of every step; the
         # graph reads one row block per step from a static buffer.  Kept across calls with the same schedule.
-        tkey = (tuple(float(t) for t in ts.tolist()), self.unet._weights_gen, self.brushnet._weights_gen)
+        tkey = (tuple(float(t) for t in ts.tolist()), self.unet._weights_gen, self.brushnet._weights_gen,
+                float(guidance_scale) if timestep_cond is not None else None)
         if self.precompute_time_embedding and (st.get("temb_key") != tkey or added):
             nrows_b = nb if once else pe.shape[0]
-            st["temb_tab"] = (self.unet.time_embedding_table(tvals, pe.shape[0], added),
+            st["temb_tab"] = (self.unet.time_embedding_table(tvals, pe.shape[0], added, timestep_cond),
                               self.brushnet.time_embedding_table(tvals, nrows_b, added))
             st["temb_key"] = tkey
             if "temb_cur" not in st or any(c.shape != t.shape[1:] for c, t in zip(st["temb_cur"], st["temb_tab"])):
@@ -1001,10 +1048,11 @@ class StableDiffusionBrushNetPipeline:
         temb_u, temb_b = st["temb_cur"] if self.precompute_time_embedding else (None, None)
 
         # residuals that land on a proj_out are never computed: their zero-conv becomes a second K segment of that GEMM
-        lazy = self.unet.lazy_injection_names() if (self.fold_zero_convs and not once) else None
+        lazy = self.unet.lazy_injection_names() if (self.fold_zero_convs and not once and do_cfg) else None
 
         def one_step():
-            eu, ec = self._predict_noise(lat, t_cur, pe, pe_u, cond, nb, cond_scale, True, once, False, added, (temb_u, temb_b), lazy)
+            eu, ec = self._predict_noise(lat, t_cur, pe, pe_u, cond, nb, cond_scale, do_cfg, once, False, added, (temb_u, temb_b), lazy,
+                                         timestep_cond)
             update.launch(eu, ec, lat)
 
         # A graph captured by an earlier call with this key serves every step, the first included: what depends on the
@@ -1100,13 +1148,14 @@ class StableDiffusionBrushNetPipeline:
         if scheduler not in ("host", "device"):
             raise ValueError(f"export_denoise_step: scheduler must be 'host' or 'device', not {scheduler!r}")
         if scheduler == "device" and not isinstance(self.scheduler, (DDIMScheduler, PNDMScheduler, UniPCMultistepScheduler,
-                                                                     DPMSolverMultistepScheduler, EulerDiscreteScheduler)):
+                                                                     DPMSolverMultistepScheduler, EulerDiscreteScheduler, LCMScheduler)):
             raise NotImplementedError(f"{type(self.scheduler).__name__} has no device update")
         if (scheduler == "device" and not isinstance(call_kwargs.get("generator"), PhiloxGenerator)
                 and (getattr(self.scheduler, "config", {}).get("algorithm_type") == "sde-dpmsolver++"
-                     or isinstance(self.scheduler, EulerAncestralDiscreteScheduler))):
-            raise NotImplementedError("a step program of the DPM-Solver++ SDE / Euler-ancestral update draws its noise in the kernel: pass "
+                     or isinstance(self.scheduler, (EulerAncestralDiscreteScheduler, LCMScheduler)))):
+            raise NotImplementedError("a step program of the DPM-Solver++ SDE / Euler-ancestral / LCM update draws its noise in the kernel: pass "
                                       "generator=rng.PhiloxGenerator(seed), or export with scheduler='host'")
+        self._refuse_unguided_export("export_denoise_step", call_kwargs)
         from . import program
         program.refuse_ip_processors(self.unet)      # before anything is captured (the recorder would refuse in the middle of a two-stream capture)
         request = dict(path=path, scheduler=scheduler, info=None)       # travels with the call; _denoise_graph leaves the result in it
@@ -1117,6 +1166,16 @@ class StableDiffusionBrushNetPipeline:
                                  "use_graph left on)")
         request["info"]["result"] = out
         return request["info"]
+
+    def _refuse_unguided_export(self, what: str, call_kwargs: dict) -> None:
+        """Before any file is written: the captured step without classifier-free guidance (LCMScheduler at guidance_scale <= 1, or a UNet
+        with time_cond_proj_dim) has no step-program form yet.  Other schedulers' unguided calls never reach the captured step."""
+        distilled = self.unet.config.get("time_cond_proj_dim") is not None
+        if (isinstance(self.scheduler, LCMScheduler) or distilled) and (distilled or float(call_kwargs.get("guidance_scale", 7.5)) <= 1):
+            raise NotImplementedError(f"{what} without classifier-free guidance ("
+                                      + ("the UNet has time_cond_proj_dim" if distilled else "guidance_scale <= 1 under LCMScheduler")
+                                      + "): a step program's hosts feed the doubled batch and both halves of the noise prediction; export "
+                                      "under guidance_scale > 1, or run the call through the pipeline")
 
     # ---- the two ends of a call as step programs (program.py; include/mfhip.h "step programs") --------------------------------
     def _refuse_vae_switches(self, what: str, batch: int, height: int, width: int, decode: bool = True) -> None:
@@ -1274,6 +1333,7 @@ class StableDiffusionBrushNetPipeline:
         if isinstance(self.scheduler, EulerDiscreteScheduler):       # before any file is written
             raise NotImplementedError(f"export_call under {type(self.scheduler).__name__}: the exported call's host loop feeds the sample "
                                       "to the step, the Euler family's step reads the scaled model input (export_denoise_step carries it)")
+        self._refuse_unguided_export("export_call", call_kwargs)
         program.refuse_ip_processors(self.unet)
         for m in self._lora_models():
             if m._lora_state().pinned is None:

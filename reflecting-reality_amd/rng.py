@@ -73,6 +73,11 @@ class PhiloxGenerator:
         if on_device and self._state is not None and self._synced == was:
             self._synced = (self._seed, self._offset)
 
+    def device_moved(self) -> None:
+        """Queued device work moved the device state and the host pair did NOT follow (a captured step that advances at a step whose
+        update reads no noise): the next device_state() uploads the host pair again."""
+        self._synced = None
+
     def randn(self, shape: Sequence[int], first_sample: int = 0, global_batch: Optional[int] = None, scale: float = 1.0,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """fp32 normals [B, ...] drawn per sample: this call owns the samples [first_sample, first_sample + B) of a draw of

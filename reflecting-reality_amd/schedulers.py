@@ -5,7 +5,7 @@ add_noise :473-497) and scheduling_pndm.py (set_timesteps :168-226, step_prk :26
 _get_prev_sample :407-448).  The scalar coefficients are computed on the host exactly like the reference
 does (fp32 0-dim tensor arithmetic on the alphas_cumprod table); the per-element update is one HIP kernel
 (mf_cfg_ddim_step / mf_axpby_n).  Latents stay fp32 whatever the model precision.  device_plan (end of the file) turns a PNDM /
-UniPC / DPM-Solver++ / Euler schedule into rows for mf_sched_step_dev, the whole update of a step in one launch with device-resident coefficients.
+UniPC / DPM-Solver++ / Euler / LCM schedule into rows for mf_sched_step_dev, the whole update of a step in one launch with device-resident coefficients.
 EulerDiscreteScheduler / EulerAncestralDiscreteScheduler (scheduling_euler_discrete.py, scheduling_euler_ancestral_discrete.py) are the two
 classes whose scale_model_input is not the identity: their plans keep the sample in a state slot and write the model input to the latents.
 """
@@ -28,6 +28,12 @@ from .models import FrozenConfig
 class SchedulerOutput:
     prev_sample: torch.Tensor
     pred_original_sample: Optional[torch.Tensor] = None
+
+
+@dataclass
+class LCMSchedulerOutput:
+    prev_sample: torch.Tensor
+    denoised: Optional[torch.Tensor] = None
 
 
 def _betas(cfg) -> torch.Tensor:
@@ -912,6 +918,152 @@ class EulerAncestralDiscreteScheduler(EulerDiscreteScheduler):
         return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
 
 
+class LCMScheduler(_SchedulerBase):
+    """schedulers/scheduling_lcm.py: latent-consistency multistep sampling (Luo et al. 2023), 1-8 steps on a distilled UNet or under an
+    LCM-LoRA.  set_timesteps (:351-490) picks its steps from the `original_inference_steps`-sized distillation schedule, or takes a custom
+    list.  A step (:500-594) is linear in {sample, model output, noise}: the data prediction, the boundary-condition scalings c_skip /
+    c_out (:492-498) and sqrt(alpha_prev) / sqrt(1 - alpha_prev) fold into float coefficients, so it is TWO mf_axpby_n launches:
+    `denoised` from {sample, model output}, then `prev_sample` from {denoised, noise}.  The last step draws nothing and returns `denoised`
+    (:580).  The scalars are numpy float32 arithmetic with np.sqrt on the fp32 alphas_cumprod table (what the reference's 0-dim fp32
+    tensors compute; see EulerDiscreteScheduler._sigma_table for why not torch's `** 0.5`), folded in double and rounded once."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", trained_betas=None,
+                     original_inference_steps=50, clip_sample=False, clip_sample_range=1.0, set_alpha_to_one=True, steps_offset=0,
+                     prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0,
+                     timestep_spacing="leading", timestep_scaling=10.0, rescale_betas_zero_snr=False)
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        c = self.config
+        if c["thresholding"]:
+            raise NotImplementedError("thresholding is not built: the quantile clamp is not linear in the sample")
+        if c["clip_sample"]:
+            raise NotImplementedError("clip_sample=True is not built: the clamp is not linear in the sample (LCM checkpoints ship it off)")
+        if c["rescale_betas_zero_snr"]:
+            raise NotImplementedError("rescale_betas_zero_snr is outside the MirrorFusion path")
+        if c["prediction_type"] not in ("epsilon", "sample", "v_prediction"):
+            raise ValueError(f"prediction_type given as {c['prediction_type']} must be one of `epsilon`, `sample` or `v_prediction` for "
+                             "`LCMScheduler`.")
+        self.custom_timesteps = False
+        self._step_index = None
+        self._begin_index = None
+
+    step_index = EulerDiscreteScheduler.step_index
+    begin_index = EulerDiscreteScheduler.begin_index
+    set_begin_index = EulerDiscreteScheduler.set_begin_index
+
+    def index_for_timestep(self, timestep, schedule_timesteps=None):
+        ts = self.timesteps if schedule_timesteps is None else schedule_timesteps
+        cand = (ts == int(timestep)).nonzero()
+        return int(cand[1 if len(cand) > 1 else 0])
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, original_inference_steps: Optional[int] = None,
+                      timesteps: Optional[List[int]] = None, strength: float = 1.0):
+        """:351-490.  The integer schedule and the ValueErrors are the reference's; what it only warns about (a custom schedule off the
+        distillation grid, or not starting at the last training step) is accepted silently."""
+        c = self.config
+        nt = c["num_train_timesteps"]
+        if num_inference_steps is None and timesteps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `custom_timesteps`.")
+        if num_inference_steps is not None and timesteps is not None:
+            raise ValueError("Can only pass one of `num_inference_steps` or `custom_timesteps`.")
+        original_steps = original_inference_steps if original_inference_steps is not None else c["original_inference_steps"]
+        if original_steps > nt:
+            raise ValueError(f"`original_steps`: {original_steps} cannot be larger than `self.config.train_timesteps`: {nt} as the unet "
+                             f"model trained with this scheduler can only handle maximal {nt} timesteps.")
+        k = nt // original_steps                                     # the skipping step of the distillation schedule
+        origin = np.asarray(list(range(1, int(original_steps * strength) + 1))) * k - 1
+        if timesteps is not None:
+            timesteps = [int(t) for t in timesteps]
+            for i in range(1, len(timesteps)):
+                if timesteps[i] >= timesteps[i - 1]:
+                    raise ValueError("`custom_timesteps` must be in descending order.")
+            if timesteps[0] >= nt:
+                raise ValueError(f"`timesteps` must start before `self.config.train_timesteps`: {nt}.")
+            ts = np.array(timesteps, dtype=np.int64)
+            self.num_inference_steps = len(ts)
+            self.custom_timesteps = True
+            init_timestep = min(int(self.num_inference_steps * strength), self.num_inference_steps)      # (strength: the img2img cut)
+            ts = ts[max(self.num_inference_steps - init_timestep, 0) * self.order:]
+        else:
+            if num_inference_steps > nt:
+                raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `self.config.train_timesteps`: {nt} "
+                                 f"as the unet model trained with this scheduler can only handle maximal {nt} timesteps.")
+            if len(origin) // num_inference_steps < 1:
+                raise ValueError(f"The combination of `original_steps x strength`: {original_steps} x {strength} is smaller than "
+                                 f"`num_inference_steps`: {num_inference_steps}. Make sure to either reduce `num_inference_steps` to a "
+                                 f"value smaller than {int(original_steps * strength)} or increase `strength` to a value higher than "
+                                 f"{float(num_inference_steps / original_steps)}.")
+            self.num_inference_steps = num_inference_steps
+            if num_inference_steps > original_steps:
+                raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `original_inference_steps`: "
+                                 f"{original_steps} because the final timestep schedule will be a subset of the "
+                                 "`original_inference_steps`-sized initial timestep schedule.")
+            origin = origin[::-1].copy()
+            idx = np.floor(np.linspace(0, len(origin), num=num_inference_steps, endpoint=False)).astype(np.int64)
+            ts = origin[idx]
+        self.timesteps = torch.from_numpy(ts).to(torch.int64)        # kept on the host: the loop indexes coefficient tables
+        self._coef_cache = {}
+        self._step_index = None
+        self._begin_index = None
+
+    def get_scalings_for_boundary_condition_discrete(self, timestep):
+        """:492-498 in fp32, what the reference computes for a timestep taken from `timesteps` (an int64 tensor times a float)."""
+        sd = np.float32(0.5)
+        st = np.float32(int(timestep)) * np.float32(self.config["timestep_scaling"])
+        return float(sd * sd / (st * st + sd * sd)), float(st / np.sqrt(st * st + sd * sd))
+
+    def _step_coefs(self, timestep: int, index: int):
+        """((of sample, of model output) for `denoised`, (of denoised, of noise) for `prev_sample` | None on the last step)."""
+        n = len(self.timesteps)
+        prev_t = int(self.timesteps[index + 1]) if index + 1 < n else timestep
+        f32 = np.float32
+        a_t, a_p = f32(float(self._alpha(timestep))), f32(float(self._alpha(prev_t)))
+        sa, sb = float(np.sqrt(a_t)), float(np.sqrt(f32(1) - a_t))
+        c_skip, c_out = self.get_scalings_for_boundary_condition_discrete(timestep)
+        p = self.config["prediction_type"]
+        if p == "epsilon":                   # x0 = (x - sqrt(b_t) e) / sqrt(a_t)
+            den = [c_skip + c_out / sa, -c_out * sb / sa]
+        elif p == "sample":
+            den = [c_skip, c_out]
+        else:                                # x0 = sqrt(a_t) x - sqrt(b_t) v
+            den = [c_skip + c_out * sa, -c_out * sb]
+        if index == self.num_inference_steps - 1:
+            return den, None
+        return den, [float(np.sqrt(a_p)), float(np.sqrt(f32(1) - a_p))]
+
+    _noise = DPMSolverMultistepScheduler._noise
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
+             variance_noise: Optional[torch.Tensor] = None, return_dict: bool = True):
+        """:500-594.  Returns (prev_sample, denoised).  `variance_noise`: the step's noise (drawn from `generator` when None; the last
+        step of the schedule neither draws nor reads one)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._step_index = self.index_for_timestep(timestep) if self._begin_index is None else self._begin_index
+        key = (int(timestep), self._step_index)
+        coefs = self._coef_cache.get(key)
+        if coefs is None:
+            coefs = self._coef_cache[key] = self._step_coefs(*key)
+        den, nxt = coefs
+        x = sample.float().contiguous()
+        denoised = hip.axpby_n([x, model_output.float().contiguous()], den)
+        if nxt is not None:
+            if variance_noise is None:
+                variance_noise = self._noise(tuple(x.shape), generator, x.device)
+            if not isinstance(variance_noise, _Sym):
+                variance_noise = variance_noise.to(x.device).float().contiguous()
+            prev = hip.axpby_n([denoised, variance_noise], nxt)
+        else:
+            prev = denoised
+        self._step_index += 1
+        return (prev, denoised) if not return_dict else LCMSchedulerOutput(prev_sample=prev, denoised=denoised)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        raise NotImplementedError("LCMScheduler.add_noise is only used by training / image-to-image (SURVEY.md §8 f-2)")
+
+
 # ---- the multistep schedulers' update on the device (mf_sched_step_dev) ------------------------------------------------------------
 # A step of PNDM / UniPC is a short list of mf_axpby_n calls over the guided noise prediction, the latents and the history the
 # scheduler keeps.  device_plan() runs the scheduler's OWN step() on stand-in tensors that record those calls (terms, order, float
@@ -1026,8 +1178,11 @@ class SchedPlan:
     """device_plan()'s result: `rows` (int32 [steps, sizeof(mf_sched_row) / 4], one mf_sched_row per step, host memory), `nslots` (S: the
     state buffer is [S, *latents.shape] fp32) and the traced scheduler, whose end state finish() hands to the real one."""
 
-    def __init__(self, rows: torch.Tensor, nslots: int, traced, steps: int, noise_reg: int = -1, x_slot: int = -1, first_scale: float = 1.0):
+    def __init__(self, rows: torch.Tensor, nslots: int, traced, steps: int, noise_reg: int = -1, x_slot: int = -1, first_scale: float = 1.0,
+                 draws: Optional[List[bool]] = None):
         self.rows, self.nslots, self._traced, self.steps = rows, nslots, traced, steps
+        # per step: does the row read the step's noise?  (LCM's last step does not: the host's step() draws nothing there)
+        self.draws = [noise_reg >= 0] * steps if draws is None else draws
         # the register mf_sched_step_noise_dev fills with the step's standard normals (SDE and ancestral samplers); -1: the plan reads no noise
         self.noise_reg = noise_reg
         # Euler family: the slot that holds the sample x, while the latents (register 1) hold the model input, x / sqrt(sigma^2 + 1) of
@@ -1051,10 +1206,10 @@ class SchedPlan:
 
 def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
     """The rows of mf_sched_step_dev for the first `steps` (default: all) entries of `sched.timesteps`, for a PNDMScheduler,
-    UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler or EulerAncestralDiscreteScheduler right after set_timesteps.  `sched` itself is not changed (a copy is traced).
-    The SDE type of DPM-Solver++ and the ancestral Euler class read a noise value per step: its register is `noise_reg` of the plan (mf_sched_step_noise_dev)."""
+    UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler or LCMScheduler right after set_timesteps.  `sched` itself is not changed (a copy is traced).
+    The SDE type of DPM-Solver++, the ancestral Euler class and LCM read a noise value per step (`plan.draws`: which steps do): its register is `noise_reg` of the plan (mf_sched_step_noise_dev)."""
     global hip
-    if not isinstance(sched, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler)):
+    if not isinstance(sched, (PNDMScheduler, UniPCMultistepScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, LCMScheduler)):
         raise NotImplementedError(f"{type(sched).__name__} has no device plan (DDIM updates through mf_cfg_ddim_step_dev)")
     if sched.num_inference_steps is None:
         raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
@@ -1068,9 +1223,9 @@ def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
             setattr(traced, k, list(v))
     ts = sched.timesteps
     steps = len(ts) if steps is None else int(steps)
-    slots, per_step, ntemps = [], [], 0
+    slots, per_step, ntemps, draws = [], [], 0, []
     real, tracer = hip, _TraceHip()
-    noisy = isinstance(sched, EulerAncestralDiscreteScheduler) or (
+    noisy = isinstance(sched, (EulerAncestralDiscreteScheduler, LCMScheduler)) or (
         isinstance(sched, DPMSolverMultistepScheduler) and sched.config["algorithm_type"] == "sde-dpmsolver++")
     # Euler family: the sample keeps slot 0 from step to step (the host puts x0 there), and every row ends with one more op, the next
     # step's model input into register 1
@@ -1090,6 +1245,7 @@ def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
             prev = traced.step(e, ts[k], x, **(dict(variance_noise=noise) if noisy else {}), return_dict=False)[0]
         finally:
             hip = real
+        draws.append(noisy and any(v is noise for _, xs, _ in tracer.calls for v in xs))
         held = _held(traced)
         if euler:
             sample = prev
@@ -1128,4 +1284,4 @@ def device_plan(sched, steps: Optional[int] = None) -> SchedPlan:
         rows.append(bytes(row))
     table = torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.int32).view(steps, -1).clone() if rows else \
         torch.zeros(0, C.sizeof(_Row) // 4, dtype=torch.int32)
-    return SchedPlan(table, nslots, traced, steps, base["t"] if noisy else -1, 0 if euler else -1, first_scale)
+    return SchedPlan(table, nslots, traced, steps, base["t"] if noisy else -1, 0 if euler else -1, first_scale, draws)

@@ -221,6 +221,27 @@ typedef struct mf_gemm_plan {
 } mf_gemm_plan;
 int mf_gemm_conv_plan(const mf_gemm_desc* d, mf_gemm_plan* out);
 int mf_sizeof_gemm_plan(void);
+/* The 3x3 / padding 1 convolution over a nearest-2x upsampled image (the UNet / BrushNet upsamplers: mf_gemm_desc.upsample = 1) as
+ * FOUR 2x2 convolutions over the low-resolution image, one per output phase (py, px), in one launch: output pixel (2y + py, 2x + px)
+ * reads only the 2x2 low-resolution window that starts at (y - 1 + py, x - 1 + px), with the 3x3 taps that land on the same pixel
+ * summed (rows: py = 0 -> {ky0}, {ky1 + ky2}; py = 1 -> {ky0 + ky1}, {ky2}; columns alike) — 4/9 of the multiply-adds, and the zero
+ * padding of the upsampled image is the zero padding of the low-resolution one, so the borders are exact.  The descriptor struct is
+ * mf_gemm_desc, unchanged, read as follows:
+ *   h_in, w_in: the LOW-resolution geometry; h_out = 2 h_in, w_out = 2 w_in; kh = kw = 2, stride = 1, upsample = 1; one A segment
+ *   (a1 NULL, c1 0), dtype MF_BF16 / MF_F16 with a_dtype = dtype.
+ *   w: four weight matrices [n][ldw >= 4 c0] with k = (ty * 2 + tx) * c0 + c over the window's taps; phase p = 2 py + px starts at
+ *   w + p * w_zs_o elements.
+ *   out / ldc / out_dtype, res0, res1 (res1_rows counted in OUTPUT rows), bias, alpha, act (none / SiLU), gn_part (+ gn_groups and the
+ *   host out-fields) mean what they mean to mf_gemm_conv, over the full-resolution output of 4 * batch * h_in * w_in rows.  The partial
+ *   sums of gn_part cover R output rows each and an output image's partial rows are contiguous, which is all mf_groupnorm's part0
+ *   asks: (image, phase, block of R low-resolution rows) with R = the tile's rows when the epilogue makes them (no split-K,
+ *   h_in * w_in a multiple of the tile's rows), blocks of R consecutive output rows otherwise.
+ *   tile: 0 or one of 42 / 43 / 48; splitk: 0 / 1 or a forced count (ws holds splitk full-resolution slabs, summed by a reduce launch).
+ *   nz > 1, temb, ln_colsum, vt_out, MF_ACT_GEGLU4, a second segment, scales, bias_mode 1 and defer_reduce: MF_EINVAL, nothing written.
+ * mf_conv_up2x_plan: the same checks and choices on the host, nothing launched (as mf_gemm_conv_plan is to mf_gemm_conv).
+ * (appended; MF_ABI_VERSION stays 23: no existing entry or struct changed) */
+int mf_conv_up2x(const mf_gemm_desc* d, void* stream);
+int mf_conv_up2x_plan(const mf_gemm_desc* d, mf_gemm_plan* out);
 /* number of instantiated tile configurations and their (BM, BN) */
 int mf_gemm_num_tiles(void);
 int mf_gemm_tile_shape(int tile, int* bm, int* bn);

@@ -138,4 +138,15 @@ static bool launch16_ws_ring(int tile, const GemmArgs& a, dim3 grid, hipStream_t
     }
 }
 
+// mf_conv_up2x: the phase form (MF_FX_UP) of the plain warp-specialised ring tiles the step's upsampled convs were tuned to whose phase forms keep their registers (42, 43, 48; 50 spills 24 bytes in this form)
+template <int DT>
+static bool launch16_up2x(int tile, const GemmArgs& a, dim3 grid, hipStream_t s) {
+    switch (tile) {
+        case 43: launch_one<DT, 128, 160, 4, 1, false, 3, false, false, true, true, false, false, MF_FX_UP>(a, grid, s); return true;
+        case 48: launch_one<DT, 128, 160, 4, 2, false, 3, false, false, false, true, true, false, MF_FX_UP>(a, grid, s); return true;
+        case 42: launch_one<DT, 256, 160, 8, 1, false, 3, false, false, true, true, false, false, MF_FX_UP>(a, grid, s); return true;
+        default: return false;
+    }
+}
+
 }  // namespace mfgemm

@@ -255,7 +255,7 @@ int pick_tile(int M, int N, int nz, int splitk, int max_tile = kNumTiles, bool s
 // ---- plan, then launch: gemm_plan makes every check and every decision of a call on the host (no HIP runtime call; no device pointer
 // and no host out-pointer of the descriptor is dereferenced), gemm_launch issues what the plan says.  mf_gemm_conv is one after the
 // other, mf_gemm_conv_plan reports the first.
-enum GemmFamily { kTiled, kHalo, kNloop, kPers };        // the implicit-GEMM template, resident-patch tiles 16-19, tile 69, tile 70
+enum GemmFamily { kTiled, kHalo, kNloop, kPers, kUp2x };  // the implicit-GEMM template, resident-patch tiles 16-19, tile 69, tile 70, phase form (mf_conv_up2x)
 enum GnStats { kGnNone, kGnFused, kGnColsum };           // mf_gemm_desc.gn_part: off, in the epilogue, by gn_colsum*_kernel afterwards
 struct GemmPlan {
     GemmArgs a;                                 // everything but ovf / stamps (runtime addresses: gemm_launch)
@@ -263,6 +263,7 @@ struct GemmPlan {
     bool a_f32;                                 // fp32 activations converted on load (bf16 compute)
     bool reduce_launch; int deferred_splits;    // a split-K reduce launch follows / (> 0) is left to the consumer (mf_gemm_desc.defer_reduce)
     GnStats gn; int gn_rows; bool gn_grouped;   // rows per block of the statistics (*gn_part_rows), per-group sums too (*gn_grouped)
+    int m_out;                                  // rows of the stored output the reduce / column-sum launches walk (kUp2x: 4 * a.M; else 0 = a.M)
 };
 
 // column ranges per row tile of the persistent tiles: enough blocks for the chip (one block per CU), as many output tiles per block
@@ -568,6 +569,136 @@ int gemm_plan(const mf_gemm_desc* d, GemmPlan* plan) {
     return MF_OK;
 }
 
+// mf_conv_up2x: the 3x3 / pad 1 conv over a nearest-2x upsampled image as four 2x2 convs over the low-resolution image, one per output
+// phase (py, px), in ONE launch of the phase form (MF_FX_UP, gemm_conv_kernel.h) — 4/9 of the multiply-adds.  The same descriptor struct,
+// read as the header says: h_in / w_in the low-resolution geometry, kh = kw = 2, w = four [n][4 c0] matrices w_zs_o elements apart;
+// everything of the epilogue (out / ldc, res0 / res1 / res1_rows, bias, alpha, act, gn_part, the host out-fields) over the
+// full-resolution output.  Every check and decision on the host, like gemm_plan.
+bool tile_up2x(int tile) { return tile == 42 || tile == 43 || tile == 48; }
+
+int up2x_plan(const mf_gemm_desc* d, GemmPlan* plan) {
+    MF_CHECK_ARG(d != nullptr, "mf_conv_up2x: null descriptor");
+    MF_CHECK_ARG(mf_is16(d->dtype) && d->a_dtype == d->dtype && d->w_split == 0,
+                 "mf_conv_up2x: bf16 / fp16 compute on activations of the same type (dtype %d, a_dtype %d, w_split %d)", d->dtype, d->a_dtype, d->w_split);
+    MF_CHECK_ARG(d->a0 && d->w && d->out, "mf_conv_up2x: null a0/w/out");
+    MF_CHECK_ARG(d->a1 == nullptr && d->c1 == 0, "mf_conv_up2x: one A segment (no channel concat)");
+    MF_CHECK_ARG(d->c0 > 0 && d->c0 % 8 == 0 && d->lda0 % 8 == 0 && d->lda0 >= d->c0 && d->ldw % 8 == 0 && d->w_zs_o % 8 == 0 && d->w_zs_o >= 0,
+                 "mf_conv_up2x: c0 (%d), lda0, ldw and w_zs_o must be multiples of 8 elements", d->c0);
+    MF_CHECK_ARG(d->kh == 2 && d->kw == 2 && d->stride == 1 && d->upsample == 1 && d->batch >= 1 && d->h_in >= 1 && d->w_in >= 1 && d->n >= 1 &&
+                     d->h_out == 2 * d->h_in && d->w_out == 2 * d->w_in,
+                 "mf_conv_up2x: kh = kw = 2, stride 1, upsample 1 and h_out / w_out twice h_in / w_in (got %d x %d taps, stride %d, upsample %d, %d x %d -> %d x %d)",
+                 d->kh, d->kw, d->stride, d->upsample, d->h_in, d->w_in, d->h_out, d->w_out);
+    MF_CHECK_ARG(d->nz == 1, "mf_conv_up2x: no batched (nz > 1) form");
+    MF_CHECK_ARG(d->temb == nullptr, "mf_conv_up2x: no time-embedding epilogue");
+    MF_CHECK_ARG(d->ln_colsum == nullptr && d->vt_out == nullptr, "mf_conv_up2x: no folded LayerNorm / transposed columns (ln_colsum, vt_out)");
+    MF_CHECK_ARG(d->act != MF_ACT_GEGLU4, "mf_conv_up2x: no GEGLU epilogue");
+    MF_CHECK_ARG(d->a_scale == nullptr && d->w_scale == nullptr && d->bias_mode == 0 && d->defer_reduce == 0,
+                 "mf_conv_up2x: no scales, per-column bias only, no deferred reduce");
+    if (!mf_aligned16(d->a0) || !mf_aligned16(d->w)) {
+        mf_set_error("mf_conv_up2x: a0/w must be 16-byte aligned");
+        return MF_EALIGN;
+    }
+    const int64_t M64 = (int64_t)d->batch * d->h_in * d->w_in;
+    MF_CHECK_ARG(4 * M64 < (1ll << 31), "mf_conv_up2x: M too large");
+    MF_CHECK_ARG(d->lda0 * 2 < (1ll << 31), "mf_conv_up2x: pixel stride too large");
+    {
+        const int r0 = d->res0 ? d->res0_dtype : -1, r1 = d->res1 ? d->res1_dtype : -1;
+        MF_CHECK_ARG(d->dtype == MF_F16 ? !mf_any_bf16(d->out_dtype, r0, r1) : !mf_any_f16(d->out_dtype, r0, r1),
+                     "mf_conv_up2x: fp16 outputs / residuals go with dtype MF_F16 and bf16 ones with MF_BF16 (dtype %d, out %d, res %d %d)",
+                     d->dtype, d->out_dtype, r0, r1);
+    }
+    *plan = GemmPlan{};
+    GemmArgs& a = plan->a;
+    const int m_out = plan->m_out = (int)(4 * M64);
+    a.a0 = (const char*)d->a0; a.a1 = nullptr;
+    a.C0 = a.Ctot = d->c0;
+    a.ld0b = (int)(d->lda0 * 2); a.ld1b = 0;
+    // the GEMM's rows are the low-resolution pixels: "output" extents of the staging code = the input's
+    a.Hin = a.Ho = d->h_in; a.Win = a.Wo = d->w_in; a.HoWo = d->h_in * d->w_in;
+    a.KW = 2; a.stride = 1; a.pad_t = 1; a.pad_l = 1; a.ups = 0;          // (the kernel takes the window origin from the phase)
+    auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (v > 0 && (1 << s) == v) ? s : -1; };
+    a.howo_sh = lg(a.HoWo); a.wo_sh = lg(a.Wo); a.ho_sh = lg(a.Ho);
+    a.w = (const char*)d->w; a.ldw = d->ldw;
+    a.M = (int)M64; a.N = d->n; a.K = 4 * d->c0;
+    MF_CHECK_ARG(d->ldw >= a.K, "mf_conv_up2x: ldw %lld < K %d", (long long)d->ldw, a.K);
+    a.zdiv = 1; a.nz = 1;                                                   // blockIdx.z = phase: W moves by w_zs_o per phase, nothing else
+    a.w_zs_o = d->w_zs_o;
+    a.bias = d->bias; a.bias_mode = 0;
+    a.res0 = (const char*)d->res0; a.res0_dt = d->res0_dtype; a.ld_res0 = d->ld_res0;
+    a.res1 = (const char*)d->res1; a.res1_dt = d->res1_dtype; a.ld_res1 = d->ld_res1;
+    a.res1_rows = (d->res1 && d->res1_rows > 0 && d->res1_rows < m_out) ? d->res1_rows : 0;      // counted in OUTPUT rows
+    MF_CHECK_ARG(a.res1_rows == 0 || m_out % a.res1_rows == 0, "mf_conv_up2x: res1_rows=%d must divide the output's %d rows", d->res1_rows, m_out);
+    a.alpha = d->alpha; a.act = d->act;
+    a.out = (char*)d->out; a.out_dt = d->out_dtype; a.ldc = d->ldc;
+    MF_CHECK_ARG(d->ldc >= d->n, "mf_conv_up2x: ldc %lld < n %d", (long long)d->ldc, d->n);
+    const int gn_hw = d->h_out * d->w_out;
+    if (d->gn_part) {
+        MF_CHECK_ARG(d->gn_part_rows != nullptr && d->n % 8 == 0 && gn_hw % 32 == 0 && mf_aligned16(d->gn_part) &&
+                         d->gn_part_floats >= 2ll * d->n * (m_out / 32),
+                     "mf_conv_up2x: gn_part needs gn_part_rows, n %% 8 == 0, h_out * w_out %% 32 == 0 and 2 * n * (M / 32) = %lld floats (got %lld)",
+                     (long long)(2ll * d->n * (m_out / 32)), (long long)d->gn_part_floats);
+        plan->gn = kGnColsum;
+        plan->gn_rows = gn_hw % 128 == 0 ? 128 : (gn_hw % 64 == 0 ? 64 : 32);
+    }
+    a.vec_ok = (d->n % 8 == 0) && (d->ldc % 8 == 0) && mf_aligned16(d->out) && (!d->bias || mf_aligned16(d->bias)) &&
+               (!d->res0 || (mf_aligned16(d->res0) && d->ld_res0 % 8 == 0)) && (!d->res1 || (mf_aligned16(d->res1) && d->ld_res1 % 8 == 0));
+    int tile = d->tile;
+    MF_CHECK_ARG(tile == 0 || tile_up2x(tile), "mf_conv_up2x: tile %d has no phase form (42, 43 and 48 do)", tile);
+    // one block per CU: 256 rows per block once that still gives every CU a block, else 128
+    if (tile == 0) tile = (int64_t)cdiv(a.M, 256) * cdiv(a.N, 160) * 4 >= 256 ? 42 : 48;
+    plan->tile = tile;
+    const TileCfg& tc = kTiles[tile - 1];
+    a.nkt = cdiv(a.K, 64);
+    const int64_t tiles_mn = (int64_t)cdiv(a.M, tc.bm) * cdiv(a.N, tc.bn) * 4;
+    a.ws = d->ws;
+    int splitk = d->splitk;
+    if (splitk == 0) {      // as gemm_plan: fill the chip when the output grid alone cannot, >= 4 K tiles per slice
+        // (the four phases already multiply the grid: at 128 blocks — the 8 x 8 level at batch 8 — one slice measured fastest)
+        splitk = 1;
+        if (tiles_mn < 128 && a.nkt >= 8 && d->ws != nullptr) {
+            splitk = (int)((384 + tiles_mn - 1) / tiles_mn);
+            if (splitk > a.nkt / 4) splitk = a.nkt / 4;
+            if ((int64_t)splitk * m_out * a.N > d->ws_floats) splitk = (int)(d->ws_floats / ((int64_t)m_out * a.N));
+        }
+    }
+    a.splitk = splitk > 1 ? splitk : 1;
+    if (a.splitk > a.nkt) a.splitk = a.nkt;
+    a.kt_per_split = cdiv(a.nkt, a.splitk);
+    a.splitk = cdiv(a.nkt, a.kt_per_split);   // no empty splits
+    MF_CHECK_ARG(a.splitk == 1 || (a.ws != nullptr && (int64_t)a.splitk * m_out * a.N <= d->ws_floats),
+                 "mf_conv_up2x: split-K=%d needs a workspace of %lld floats", a.splitk, (long long)a.splitk * m_out * a.N);
+    a.sk_tickets = nullptr;                     // (no in-launch combine: the reduce launch walks the full-resolution slabs)
+    {
+        const int64_t ext_a = (M64 - 1) * a.ld0b + (int64_t)a.C0 * 2, ext_w = ((int64_t)(a.N - 1) * a.ldw + a.K) * 2;
+        a.fast = (a.C0 % 64 == 0) && ext_a < (1ll << 31) - (1 << 20) && ext_w < (1ll << 31) - (1 << 20);
+    }
+    a.pointwise = 0;
+    a.tiles_n = cdiv(a.N, tc.bn);
+    a.tiles_m = cdiv(a.M, tc.bm);
+    a.wfr_magic = 0; a.epb = 0; a.epb_sh = 31;
+    const int64_t nblk = (int64_t)a.tiles_m * a.tiles_n * a.splitk;
+    MF_CHECK_ARG(nblk < (1ll << 31), "mf_conv_up2x: grid too large");
+    a.nblk = (int)nblk;
+    a.ord_pw = a.tiles_n;
+    a.up_bpi = 1;
+    // statistics in the epilogue: a block's rows inside one low-resolution image (its four phases' blocks are four of the output image's)
+    if (d->gn_part != nullptr && a.splitk == 1 && a.vec_ok && a.HoWo % tc.bm == 0) {
+        plan->gn = kGnFused;
+        plan->gn_rows = tc.bm;
+        a.gn_part = (float2*)d->gn_part;
+        a.up_bpi = a.HoWo / tc.bm;
+        if (d->gn_groups > 0 && a.N % d->gn_groups == 0) {
+            const int cpg = a.N / d->gn_groups;
+            plan->gn_grouped = tc.bn % cpg == 0 && (int64_t)2 * (a.N + d->gn_groups) * (m_out / tc.bm) <= d->gn_part_floats;
+            if (plan->gn_grouped) { a.gn_grp = a.gn_part + (int64_t)a.N * (m_out / tc.bm); a.gn_cpg = cpg; }
+        }
+    }
+    plan->family = kUp2x;
+    plan->grid = dim3((unsigned)nblk, 1, 4u);
+    plan->reduce_launch = a.splitk > 1;
+    return MF_OK;
+}
+
 // the implicit-GEMM template's instantiations, by precision and tile group (false: this tile is not instantiated for this precision)
 bool launch_tiled(const mf_gemm_desc* d, const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
     const int tile = p.tile, dxr = kTiles[tile - 1].dxr;
@@ -604,9 +735,12 @@ int gemm_launch(const GemmPlan& p, const mf_gemm_desc* d, hipStream_t s) {
     case kNloop: launched = launch_nloop(d->dtype, a, s); what = "mf_gemm_conv(nloop)"; break;
     case kPers: launched = launch_pers(d->dtype, a, s); what = "mf_gemm_conv(pers)"; break;
     case kTiled: launched = launch_tiled(d, p, a, s); break;
+    case kUp2x: launched = d->dtype == MF_F16 ? launch_f16_up2x(p.tile, a, p.grid, s) : launch_bf16_up2x(p.tile, a, p.grid, s); what = "mf_conv_up2x"; break;
     }
-    MF_CHECK_ARG(launched, "mf_gemm_conv: tile %d is not instantiated for dtype %d (w_split=%d)", p.tile, d->dtype, d->w_split);
+    MF_CHECK_ARG(launched, "%s: tile %d is not instantiated for dtype %d (w_split=%d)", p.family == kUp2x ? "mf_conv_up2x" : "mf_gemm_conv", p.tile, d->dtype,
+                 d->w_split);
     MF_CHECK_LAUNCH(what);
+    if (p.m_out) { a.M = p.m_out; a.HoWo = d->h_out * d->w_out; a.howo_sh = -1; }      // the tail walks the stored (full-resolution) output
     if (p.reduce_launch) {
         const int64_t total = (int64_t)a.M * a.N * a.nz / (a.vec_ok ? 8 : 1);
         const int blocks = total > 4096 * 256 ? 4096 : (int)((total + 255) / 256);        // (total >= 1)
@@ -657,6 +791,21 @@ extern "C" int mf_gemm_conv(const mf_gemm_desc* d, void* stream) {
     GemmPlan plan;
     const int rc = gemm_plan(d, &plan);
     return rc != MF_OK ? rc : gemm_launch(plan, d, (hipStream_t)stream);
+}
+
+extern "C" int mf_conv_up2x(const mf_gemm_desc* d, void* stream) {
+    GemmPlan plan;
+    const int rc = up2x_plan(d, &plan);
+    return rc != MF_OK ? rc : gemm_launch(plan, d, (hipStream_t)stream);
+}
+
+extern "C" int mf_conv_up2x_plan(const mf_gemm_desc* d, mf_gemm_plan* out) {
+    MF_CHECK_ARG(out != nullptr, "mf_conv_up2x_plan: null plan");
+    GemmPlan p;
+    const int rc = up2x_plan(d, &p);
+    if (rc == MF_OK)
+        *out = mf_gemm_plan{p.tile, p.a.splitk, 1, (int32_t)(p.grid.x * p.grid.y * p.grid.z), p.reduce_launch, 0, p.gn_rows, p.gn_grouped};
+    return rc;
 }
 
 extern "C" int mf_sizeof_gemm_plan(void) { return (int)sizeof(mf_gemm_plan); }

@@ -117,6 +117,9 @@ struct GemmArgs {
     // ... and per-GROUP sums gn_grp[tile_m * (N / gn_cpg) + group] when the consumer's groups are whole inside a tile's columns
     // (BN % gn_cpg == 0; the host checks): the consumer GroupNorm then needs no finalize launch
     float2* gn_grp; int gn_cpg;
+    // phase form (MF_FX_UP, mf_conv_up2x): row blocks of BM rows per LOW-resolution image (Ho * Wo / BM) when the epilogue leaves
+    // GroupNorm sums — they are stored image by image, (image, phase, block), so that an output image's partial rows stay contiguous
+    int up_bpi;
 };
 
 __device__ __forceinline__ int div_sh(int x, int d, int sh) { return sh >= 0 ? x >> sh : x / d; }
@@ -302,6 +305,11 @@ __device__ __forceinline__ f32x16_t mfma32x16(bf16x8_t a, bf16x8_t b, f32x16_t c
 #define MF_FX_AE 4     // dx-reuse convs: the A window of group g + 1 issued one tap early
 #define MF_FX_ALL 7
 #define MF_FX_XQ 8     // the cross-tile pipeline at k16 granularity (32x32x16 forms with 64-row wave tiles: two sets of MT + NT fragments)
+// MF_FX_UP (mf_conv_up2x, gemm_up2x.hip): the phase form of a 3x3 conv over a nearest-2x upsampled image.  The GEMM's rows are the
+// LOW-resolution pixels (Ho = Hin, Wo = Win), its taps a 2x2 window; blockIdx.z is the phase p = 2 py + px (zdiv = 1: the weight base
+// moves by p * w_zs_o), the window starts at (y - 1 + py, x - 1 + px), and row m = (b H + y) W + x of the phase is row
+// 4 m - 2 (m mod W) + 2 W py + px of the full-resolution output, residuals and split-K slabs.  Warp-specialised ring tiles only.
+#define MF_FX_UP 16
 
 // LDS layout of the staged epilogue rows of a warp-specialised tile: [bias][ln_colsum][temb of image 0 .. nimg-1], fp32, each row
 // padded to whole 64-float DMA pieces; placed behind the ring (and the LayerNorm statistics).  nimg = 0: the tile has no room.
@@ -407,6 +415,9 @@ void gemm_conv_kernel(const GemmArgs p) {
     constexpr bool SPLIT = (DT == MF_F16X3 || DT == MF_BF16X3 || X1);
     static_assert(!WPK || (SPLIT && !X1), "a pre-split W operand only exists for the three-MFMA split codes");
     constexpr bool FP8 = (DT == MF_FP8);
+    constexpr bool UP = (FX & MF_FX_UP) != 0;     // phase form of the upsampled 3x3 conv
+    static_assert(!UP || (WS && !DXR && H16 && !SKF), "the phase form is instantiated on the warp-specialised 16-bit ring tiles");
+    static_assert(!UP || !(FX & MF_FX_EPB), "the staged-epilogue-rows branch stores to row m: it has no phase form");
     constexpr int ES = H16 ? 2 : (FP8 ? 1 : 4);   // element size of the operands in memory / LDS
     constexpr int AES = A_F32 ? 4 : ES;          // element size of the A storage dtype
     constexpr int VEC = 16 / ES;                 // elements per 16-byte LDS chunk
@@ -521,8 +532,8 @@ void gemm_conv_kernel(const GemmArgs p) {
                 const int oy = div_sh(r, p.Wo, p.wo_sh);
                 const int ox = r - oy * p.Wo;
                 a_pix[i] = b * p.Hin * p.Win;
-                a_iy0[i] = oy * p.stride - p.pad_t;
-                a_ix0[i] = ox * p.stride - p.pad_l;
+                a_iy0[i] = UP ? oy - 1 + (z >> 1) : oy * p.stride - p.pad_t;
+                a_ix0[i] = UP ? ox - 1 + (z & 1) : ox * p.stride - p.pad_l;
             }
         } else {
             a_pix[i] = 0;
@@ -1507,7 +1518,14 @@ void gemm_conv_kernel(const GemmArgs p) {
     char* slab = smem + wave * (SR * EP_RS);        // private to this wave: [SR rows][WN + 4] fp32
     constexpr int CPR = WN / 8;                      // 8-channel groups per output row
     constexpr int ITEMS = SR * CPR;                  // (row, group) items per slab
-    float* ws = p.splitk > 1 ? p.ws + ((int64_t)ksplit * p.nz + z) * (int64_t)p.M * p.N : nullptr;
+    // (phase form: the slabs hold the full-resolution output, 4 M rows, addressed by output row like `out`)
+    float* ws = p.splitk > 1 ? p.ws + (UP ? (int64_t)ksplit * 4 : (int64_t)ksplit * p.nz + z) * (int64_t)p.M * p.N : nullptr;
+    // phase form: output row of GEMM row m (a division only where W is not a power of two)
+    const int up_off = UP ? 2 * p.Wo * (z >> 1) + (z & 1) : 0;
+    auto orow = [&](int m) -> int {
+        if constexpr (!UP) return m;
+        else return 4 * m - 2 * (m - div_sh(m, p.Wo, p.wo_sh) * p.Wo) + up_off;
+    };
     const int64_t zo = zq * p.o_zs_o + zr * p.o_zs_i;
     // bf16 residuals of a slab's items are fetched BEFORE its LDS transposition: loads and stores share vmcnt and
     // return in order, so a load issued after the previous item's store waits for that store's round trip
@@ -1547,8 +1565,9 @@ void gemm_conv_kernel(const GemmArgs p) {
                     const bool on = coords(u, sw, row, ec, m, n);
                     q0[u] = uint4{0, 0, 0, 0}; q1[u] = uint4{0, 0, 0, 0};
                     if (on && m < p.M && n + 8 <= p.N) {
-                        if (p.res0) q0[u] = *reinterpret_cast<const uint4*>(p.res0 + ((int64_t)m * p.ld_res0 + n) * 2);
-                        if (p.res1) q1[u] = *reinterpret_cast<const uint4*>(p.res1 + ((int64_t)res1_row(p, m) * p.ld_res1 + n) * 2);
+                        const int mo = orow(m);
+                        if (p.res0) q0[u] = *reinterpret_cast<const uint4*>(p.res0 + ((int64_t)mo * p.ld_res0 + n) * 2);
+                        if (p.res1) q1[u] = *reinterpret_cast<const uint4*>(p.res1 + ((int64_t)res1_row(p, mo) * p.ld_res1 + n) * 2);
                     }
                 }
             }
@@ -1645,19 +1664,20 @@ void gemm_conv_kernel(const GemmArgs p) {
                 }
                 v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
                 if (m < p.M && n < p.N) {
+                    const int mo = orow(m);
                     if (ws) {
                         if (n + 8 <= p.N && (p.N & 3) == 0) {
-                            *reinterpret_cast<float4*>(ws + (int64_t)m * p.N + n) = lo;
-                            *reinterpret_cast<float4*>(ws + (int64_t)m * p.N + n + 4) = hi;
+                            *reinterpret_cast<float4*>(ws + (int64_t)mo * p.N + n) = lo;
+                            *reinterpret_cast<float4*>(ws + (int64_t)mo * p.N + n + 4) = hi;
                         } else {
-                            for (int jj = 0; jj < 8 && n + jj < p.N; ++jj) ws[(int64_t)m * p.N + n + jj] = v[jj];
+                            for (int jj = 0; jj < 8 && n + jj < p.N; ++jj) ws[(int64_t)mo * p.N + n + jj] = v[jj];
                         }
                     } else if (p.vec_ok && n + 8 <= p.N) {
                         if (epb) {
                             const char* eb = smem + EPB_OFF + (n - n0) * 4;
                             epilogue_store8<DT == MF_F16>(p, zo, m, n, v, res_pre, q0[u], q1[u], zq, eb, eb + (2 + (m >> p.epb_sh) - (m0 >> p.epb_sh)) * (EPB_PITCH * 4));
                         } else {
-                            epilogue_store8<DT == MF_F16>(p, zo, m, n, v, res_pre, q0[u], q1[u], zq);
+                            epilogue_store8<DT == MF_F16>(p, zo, mo, n, v, res_pre, q0[u], q1[u], UP ? 0 : zq);
                         }
                         if (gn) {      // the final values go back into the slab for the column pass below
                             char* slw = smem + sw * (SR * EP_RS) + row * EP_RS + ec * 4;
@@ -1665,7 +1685,7 @@ void gemm_conv_kernel(const GemmArgs p) {
                             *reinterpret_cast<float4*>(slw + 16) = make_float4(v[4], v[5], v[6], v[7]);
                         }
                     } else {
-                        for (int jj = 0; jj < 8 && n + jj < p.N; ++jj) epilogue_store(p, zo, m, n + jj, v[jj], zq);
+                        for (int jj = 0; jj < 8 && n + jj < p.N; ++jj) epilogue_store(p, zo, mo, n + jj, v[jj], UP ? 0 : zq);
                     }
                 }
             }
@@ -1711,11 +1731,14 @@ void gemm_conv_kernel(const GemmArgs p) {
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_s_barrier();
             const int tcol = (int)threadIdx.x;
+            // phase form: the block's rows lie in ONE low-resolution image (the host checked); partial rows in (image, phase, block) order
+            int gn_row = tile_m;
+            if constexpr (UP) { const int img = tile_m / p.up_bpi; gn_row = (img * 4 + z) * p.up_bpi + (tile_m - img * p.up_bpi); }
             float a = 0.0f, b = 0.0f;
             if (tcol < BN && n0 + tcol < p.N) {
 #pragma unroll
                 for (int w2 = 0; w2 < WAVES_M; ++w2) { const float2 x = red[w2 * BN + tcol]; a += x.x; b += x.y; }
-                p.gn_part[(int64_t)tile_m * p.N + n0 + tcol] = make_float2(a, b);
+                p.gn_part[(int64_t)gn_row * p.N + n0 + tcol] = make_float2(a, b);
             }
             if (p.gn_grp) {       // whole groups of gn_cpg columns inside this tile: their sums, columns in order
                 float2* tot = red + WAVES_M * BN;
@@ -1726,7 +1749,7 @@ void gemm_conv_kernel(const GemmArgs p) {
                 if (c0g < BN && n0 + c0g < p.N) {
                     float ga = 0.0f, gb = 0.0f;
                     for (int j = 0; j < cpg; ++j) { const float2 x = tot[c0g + j]; ga += x.x; gb += x.y; }
-                    p.gn_grp[(int64_t)tile_m * (p.N / cpg) + (n0 + c0g) / cpg] = make_float2(ga, gb);
+                    p.gn_grp[(int64_t)gn_row * (p.N / cpg) + (n0 + c0g) / cpg] = make_float2(ga, gb);
                 }
             }
         }
@@ -1918,6 +1941,8 @@ bool launch_f16_b(int tile, const GemmArgs& a, dim3 grid, hipStream_t s);
 bool launch_f16_c(int tile, const GemmArgs& a, dim3 grid, hipStream_t s);
 bool launch_f16_ws_dx(int tile, const GemmArgs& a, dim3 grid, hipStream_t s);
 bool launch_f16_ws_ring(int tile, const GemmArgs& a, dim3 grid, hipStream_t s);
+bool launch_bf16_up2x(int tile, const GemmArgs& a, dim3 grid, hipStream_t s);            // phase forms (MF_FX_UP) of 42, 43, 48: mf_conv_up2x
+bool launch_f16_up2x(int tile, const GemmArgs& a, dim3 grid, hipStream_t s);
 bool launch_f32_a(int tile, const GemmArgs& a, dim3 grid, hipStream_t s);                // fp32 MFMA, tiles 1-12
 bool launch_f32_b(int tile, const GemmArgs& a, dim3 grid, hipStream_t s);                // fp32 MFMA, tiles 13-15, 20-24, 31-36
 bool launch_f16x3(int tile, const GemmArgs& a, dim3 grid, hipStream_t s, bool wpk);

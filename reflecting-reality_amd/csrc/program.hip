@@ -65,7 +65,15 @@ enum NoiseFn { H_SCHED_STEP_NOISE_DEV = G_END, H_PHILOX_ADVANCE, H_END };
 const struct { int fn; const char* name; const char* sig; } kNoiseFns[H_END - G_END] = {
     {H_SCHED_STEP_NOISE_DEV, "mf_sched_step_noise_dev", "ppfppplilllllp"}, {H_PHILOX_ADVANCE, "mf_philox_advance", "pl"},
 };
-inline const char* sig_of(int fn) { return fn < F_COUNT ? kFns[fn].sig : fn < G_END ? kCallFns[fn - F_COUNT].sig : kNoiseFns[fn - G_END].sig; }
+// The upsampler convs of a denoise step in their phase form (mf_conv_up2x: the mf_gemm_desc read as four 2x2 convs).
+// program._REPLAYABLE_UP holds the same table; a fourth table, as the first two are pinned as they stand; ids go on from H_END.
+enum UpFn { U_CONV_UP2X = H_END, U_END };
+const struct { int fn; const char* name; const char* sig; } kUpFns[U_END - H_END] = {
+    {U_CONV_UP2X, "mf_conv_up2x", "d"},
+};
+inline const char* sig_of(int fn) {
+    return fn < F_COUNT ? kFns[fn].sig : fn < G_END ? kCallFns[fn - F_COUNT].sig : fn < H_END ? kNoiseFns[fn - G_END].sig : kUpFns[fn - H_END].sig;
+}
 
 struct Reader {
     const uint8_t* p; const uint8_t* end; bool ok = true;
@@ -163,6 +171,8 @@ extern "C" int mf_program_load(const void* blob, int64_t bytes, mf_program** out
             if (call.name == g.name) call.fn = g.fn;
         for (const auto& h : kNoiseFns)
             if (call.name == h.name) call.fn = h.fn;
+        for (const auto& u : kUpFns)
+            if (call.name == u.name) call.fn = u.fn;
         if (call.stream >= nstreams) {
             mf_set_error("mf_program_load: call %u (%s) on stream %u of %u", c, call.name.c_str(), call.stream, nstreams);
             delete p;
@@ -208,7 +218,7 @@ extern "C" int mf_program_load(const void* blob, int64_t bytes, mf_program** out
         }
         for (auto& pd : pending) {
             Desc d;
-            const size_t want = call.fn == F_GEMM_CONV ? sizeof(mf_gemm_desc) : sizeof(mf_groupnorm_desc);
+            const size_t want = (call.fn == F_GEMM_CONV || call.fn == U_CONV_UP2X) ? sizeof(mf_gemm_desc) : sizeof(mf_groupnorm_desc);
             const uint8_t* raw = r.take((size_t)pd.second);
             if (!raw || (size_t)pd.second != want) {
                 mf_set_error("mf_program_load: call %u (%s): descriptor of %lld bytes, this library's is %zu", c, call.name.c_str(), (long long)pd.second, want);
@@ -293,7 +303,7 @@ int run_call(const mf_program* prog, const Call& c, void* s) {
 #define L(k) (a[k].i)
 #define F(k) (a[k].f)
     switch (c.fn) {
-    case F_GEMM_CONV: case F_GROUPNORM: {
+    case F_GEMM_CONV: case F_GROUPNORM: case U_CONV_UP2X: {
         const Desc& d = c.descs[a[0].buf];
         alignas(16) uint8_t raw[sizeof(mf_gemm_desc) > sizeof(mf_groupnorm_desc) ? sizeof(mf_gemm_desc) : sizeof(mf_groupnorm_desc)];
         memcpy(raw, d.bytes.data(), d.bytes.size());
@@ -308,7 +318,7 @@ int run_call(const mf_program* prog, const Call& c, void* s) {
         int32_t rows_unused = 0, grouped_unused = 0;
         if (g->gn_part) { g->gn_part_rows = &rows_unused; g->gn_grouped = &grouped_unused; }
         if (g->defer_reduce) g->deferred_splits = &grouped_unused;      // (the recorded consumer already expects the slabs)
-        return mf_gemm_conv(g, s);
+        return c.fn == U_CONV_UP2X ? mf_conv_up2x(g, s) : mf_gemm_conv(g, s);
     }
     case F_LAYERNORM: return mf_layernorm(P(0), I(1), P(2), I(3), FP(4), FP(5), L(6), I(7), F(8), s);
     case F_SOFTMAX_ROWS: return mf_softmax_rows(FP(0), P(1), I(2), L(3), I(4), I(5), s);

@@ -250,6 +250,8 @@ SIGNATURES = {
     "mf_sched_step_noise_dev": "i:ppfppplilllllpp",
     # LoRA adapters merged on the device (csrc/lora.hip)
     "mf_sizeof_lora_target": "i:", "mf_sizeof_lora_term": "i:", "mf_lora_tiles": "l:ii", "mf_lora_merge": "i:pppppiip",
+    # the upsampled 3x3 conv as four 2x2 phase convs in one launch (csrc/gemm_conv.hip)
+    "mf_conv_up2x": "i:Gp", "mf_conv_up2x_plan": "i:GP",
 }
 EXPORTS = list(SIGNATURES)
 # (struct, the entry that reports its sizeof in the library) — load() refuses a binding whose layout differs
@@ -788,6 +790,77 @@ def gemm_conv(a0: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, dtype, w_
         # (buffer, rows per block, G): G > 0 = per-group sums of G groups follow the per-channel ones at float 2 * n * (M / rows)
         out._gn_part = (part, int(part_rows.value), int(d.gn_groups) if grouped.value else 0)
     return out
+
+
+UP2X_TILES = (42, 43, 48)       # tiles with a phase form (csrc/gemm_conv.hip: tile_up2x)
+
+
+def _up2x_desc(a0: torch.Tensor, w4: torch.Tensor, out: torch.Tensor, *, c0: int, batch: int, h_in: int, w_in: int, n: int,
+               lda0: Optional[int] = None, ldw: Optional[int] = None, w_zs: Optional[int] = None, ldc: Optional[int] = None,
+               bias: Optional[torch.Tensor] = None, res0: Optional[torch.Tensor] = None, ld_res0: Optional[int] = None,
+               res1: Optional[torch.Tensor] = None, ld_res1: Optional[int] = None, res1_rows: int = 0, alpha: float = 1.0,
+               act: int = ACT_NONE, splitk: int = 0, tile: int = 0) -> GemmDesc:
+    """The mf_gemm_desc of one mf_conv_up2x call (include/mfhip.h): the low-resolution geometry, four [n][4 c0] phase weights."""
+    _req_cuda(a0, w4, out, bias, res0, res1)
+    if a0.dtype not in (torch.bfloat16, torch.float16) or w4.dtype != a0.dtype:
+        raise MfhipError(f"conv_up2x: bf16 / fp16 activations and phase weights of one dtype (got {a0.dtype}, {w4.dtype})")
+    if bias is not None and bias.dtype != torch.float32:
+        raise MfhipError("bias must be fp32")
+    d = GemmDesc()
+    d.dtype = d.a_dtype = dt_code(a0.dtype)
+    d.a0, d.c0, d.lda0 = _ptr(a0), c0, (lda0 if lda0 is not None else c0)
+    d.batch, d.h_in, d.w_in, d.h_out, d.w_out = batch, h_in, w_in, 2 * h_in, 2 * w_in
+    d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.upsample = 2, 2, 1, 1, 1, 1
+    d.w, d.ldw = _ptr(w4), (ldw if ldw is not None else 4 * c0)
+    d.w_zs_o = w_zs if w_zs is not None else n * d.ldw
+    d.n, d.nz, d.zdiv = n, 1, 1
+    d.bias = _ptr(bias)
+    d.res0, d.res0_dtype, d.ld_res0 = _ptr(res0), (dt_code(res0.dtype) if res0 is not None else 0), (ld_res0 if ld_res0 is not None else n)
+    d.res1, d.res1_dtype, d.ld_res1 = _ptr(res1), (dt_code(res1.dtype) if res1 is not None else 0), (ld_res1 if ld_res1 is not None else n)
+    d.res1_rows = int(res1_rows)
+    d.alpha, d.act = alpha, act
+    d.out, d.out_dtype, d.ldc = _ptr(out), dt_code(out.dtype), (ldc if ldc is not None else n)
+    ws = scratch("splitk", SPLITK_WS_FLOATS, out.device)
+    d.splitk, d.ws, d.ws_floats, d.tile = splitk, ws.data_ptr(), ws.numel(), tile
+    return d
+
+
+def conv_up2x(a0: torch.Tensor, w4: torch.Tensor, out: torch.Tensor, *, gn_part: Union[bool, int] = False, **kw) -> torch.Tensor:
+    """Raw descriptor-level call of mf_conv_up2x: the 3x3 conv over the nearest-2x upsampled a0 [batch, h_in, w_in, c0] as four 2x2 phase
+    convs in one launch, with the phase weights w4 [4][n][4 c0] of ops.phase_weights.  (tile, split-K): the caller's, else the tune
+    cache's entry "up2x,<code>,<M>,<n>,<K>" (M = batch * h_in * w_in rows per phase, K = 4 c0), else the library's own choice.
+    gn_part as in gemm_conv: the partial sums are attached to `out` for groupnorm()."""
+    d = _up2x_desc(a0, w4, out, **kw)
+    n, m_out = d.n, 4 * d.batch * d.h_in * d.w_in
+    if d.tile == 0 and d.splitk in (0, 1) and AUTOTUNE:
+        cfg = _tune_load().get(_tune_key(("up2x", d.dtype, m_out // 4, n, 4 * d.c0)))
+        if cfg is not None:
+            d.tile, d.splitk = cfg[0], cfg[1]
+    part = part_rows = None
+    if gn_part:
+        part = torch.empty(2 * n * (m_out // 32), dtype=torch.float32, device=out.device)
+        part_rows, grouped = C.c_int32(0), C.c_int32(0)
+        d.gn_part, d.gn_part_floats, d.gn_part_rows = part.data_ptr(), part.numel(), C.addressof(part_rows)
+        d.gn_groups, d.gn_grouped = (int(gn_part) if (gn_part is not True and int(gn_part) > 1) else 0), C.addressof(grouped)
+    if PROFILE is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    _check(load().mf_conv_up2x(C.byref(d), _stream()), "mf_conv_up2x")
+    if PROFILE is not None:
+        e1.record()
+        # as four batched 2x2 convs of M = m_out / 4 rows (nz = 4): bench.py's byte model then counts every phase's weight matrix and
+        # output once (and the low-resolution input once per phase, which is what the launch reads)
+        PROFILE.append((e0, e1, 2.0 * m_out * n * 4 * d.c0, (m_out // 4, n, 4 * d.c0, 2, 1, 0, 4, d.tile, d.splitk, int(d.dtype))))
+    if part is not None:
+        out._gn_part = (part, int(part_rows.value), int(d.gn_groups) if grouped.value else 0)
+    return out
+
+
+def conv_up2x_plan(a0: torch.Tensor, w4: torch.Tensor, out: torch.Tensor, **kw) -> GemmPlan:
+    """What the library would do with the call conv_up2x(a0, w4, out, **kw) makes (mf_conv_up2x_plan: nothing is launched)."""
+    plan = GemmPlan()
+    _check(load().mf_conv_up2x_plan(C.byref(_up2x_desc(a0, w4, out, **kw)), C.byref(plan)), "mf_conv_up2x_plan")
+    return plan
 
 
 def _groupnorm_desc(x0: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, pend, *, groups: int, eps: float, silu: bool,

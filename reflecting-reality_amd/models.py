@@ -574,6 +574,27 @@ class _UNetCore(HipModel):
         else:
             self.temb_proj = ConvWeight(self._rows(*ws), torch.cat(bs, 0), f32, self.device)
 
+    # The upsamplers' 3x3 conv over the nearest-2x upsampled tensor (Upsample2D, upsampling.py) as four 2x2 phase convs in one launch
+    # (ops.conv_up2x: 4/9 of the multiply-adds).  bf16 / fp16 inference only; everything else — f16x3, fp32, bf16x1, fp8, training, a
+    # forward under an autograd tape — keeps conv2d(upsample=True).  `upsample_phases = False` on a model turns the routing off (A/B).
+    upsample_phases = True
+    # per level, by measurement (profiles/upsample_phases_ab.txt, batch 8): the phase form won at 32 x 32 x 640 (8192 rows per phase),
+    # 16 x 16 x 1280 (2048) and 8 x 8 x 1280 (512); nothing smaller was measured, so nothing smaller is routed.  The key is the
+    # launch's grid fill — rows per phase, batch included — so that SDXL's levels and other resolutions fall on the measured side by
+    # size, not by name: at batch 1 or 2 the 8 x 8 level drops back to the 3x3 form, and the 16 x 16 / 32 x 32 levels route with 512 to
+    # 2048 rows, the span the batch-8 table covers but at other (H W, C) than were timed.
+    UP2X_MIN_ROWS = 512
+
+    def _put_phase_weights(self, sd, name: str) -> None:
+        if ".upsamplers." in name and self.prec.name in ("bf16", "fp16") and not self.training:
+            self._put(name + ".up2x", (name,), lambda: ops.PhaseWeight(sd[name + ".weight"], sd.get(name + ".bias"), self.prec, self.device))
+
+    def _upsample_conv(self, name: str, x: torch.Tensor, res1: Optional[torch.Tensor] = None) -> torch.Tensor:
+        pw = self.P.get(name + ".up2x") if (self.upsample_phases and ops.TAPE is None and not self.training) else None
+        if pw is not None and x.shape[0] * x.shape[1] * x.shape[2] >= self.UP2X_MIN_ROWS:
+            return ops.conv_up2x(x, pw, res1=res1, gn_part=self.config["norm_num_groups"])
+        return ops.conv2d(x, self.P[name], upsample=True, res1=res1, gn_part=self.config["norm_num_groups"])
+
     def _prepare_resnet(self, sd, p):
         self._put(p + "norm1", (), lambda: self._norm(sd, p + "norm1"))
         self._put(p + "conv1", (p + "conv1",), lambda: self._conv(sd, p + "conv1"))
@@ -1327,6 +1348,7 @@ class BrushNetModel(_UNetCore):
                 self._prepare_resnet(sd, k[: -len("norm1.weight")])
             elif k.endswith("samplers.0.conv.weight"):
                 self.P[k[: -len(".weight")]] = self._conv(sd, k[: -len(".weight")])
+                self._put_phase_weights(sd, k[: -len(".weight")])
             elif k.startswith("brushnet_") and k.endswith(".weight"):
                 self.P[k[: -len(".weight")]] = self._conv(sd, k[: -len(".weight")])
 
@@ -1434,7 +1456,7 @@ class BrushNetModel(_UNetCore):
                 x = self._resnet(f"up_blocks.{i}.resnets.{j}.", x, temb, x1=skips.pop())
                 u.append(zero_conv(f"brushnet_up_blocks.{len(u)}", x))
             if i != n - 1:
-                x = ops.conv2d(x, self.P[f"up_blocks.{i}.upsamplers.0.conv"], upsample=True, gn_part=self.config["norm_num_groups"])
+                x = self._upsample_conv(f"up_blocks.{i}.upsamplers.0.conv", x)
                 u.append(zero_conv(f"brushnet_up_blocks.{len(u)}", x))
         return d, m, u
 
@@ -1552,6 +1574,7 @@ class UNet2DConditionModel(_UNetCore):
                 self._prepare_resnet(sd, k[: -len("norm1.weight")])
             elif k.endswith("samplers.0.conv.weight"):
                 self._put(k[: -len(".weight")], (k[: -len(".weight")],), lambda: self._conv(sd, k[: -len(".weight")]))
+                self._put_phase_weights(sd, k[: -len(".weight")])
             elif k.endswith(".proj_in.weight"):
                 self._prepare_transformer(sd, k[: -len("proj_in.weight")])
         self._put("conv_norm_out", (), lambda: self._norm(sd, "conv_norm_out"))
@@ -1630,7 +1653,7 @@ class UNet2DConditionModel(_UNetCore):
                     x = self._resnet(f"up_blocks.{i}.resnets.{j}.", x, temb, x1=sk, inj=inj)
             if i != n - 1:
                 inj = take(up_block_add_samples) if is_brushnet else None
-                x = ops.conv2d(x, self.P[f"up_blocks.{i}.upsamplers.0.conv"], upsample=True, res1=inj, gn_part=self.config["norm_num_groups"])
+                x = self._upsample_conv(f"up_blocks.{i}.upsamplers.0.conv", x, res1=inj)
         x = ops.groupnorm(x, self.P["conv_norm_out"], groups=c["norm_num_groups"], eps=c["norm_eps"], silu=True,
                           out_dtype=self.prec.act)
         y = ops.conv2d(x, self.P["conv_out"], out_dtype=F32)

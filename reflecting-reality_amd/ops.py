@@ -294,6 +294,60 @@ def conv2d(x: torch.Tensor, cw: ConvWeight, *, stride: int = 1,
     return out
 
 
+_PHASE_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))      # [py][ty]: the 3x3 rows that land on window row ty of output phase py (columns alike)
+
+
+def fold_phase_weights(weight: torch.Tensor) -> torch.Tensor:
+    """[N, Cin, 3, 3] -> [4, N, 2, 2, Cin] in the weight's own dtype: the four 2x2 kernels of a 3x3 / padding 1 conv over a nearest-2x
+    upsampled image.  Output pixel (2y + py, 2x + px) reads the low-resolution window starting at (y - 1 + py, x - 1 + px); taps of the
+    3x3 kernel that land on the same low-resolution pixel are summed: py = 0 -> {ky0}, {ky1 + ky2}; py = 1 -> {ky0 + ky1}, {ky2}."""
+    n, cin, kh, kw = weight.shape
+    if (kh, kw) != (3, 3):
+        raise hip.MfhipError(f"fold_phase_weights: a 3x3 kernel (got {kh}x{kw})")
+    w = weight.permute(0, 2, 3, 1)                  # [N, ky, kx, Cin]
+    out = weight.new_zeros(4, n, 2, 2, cin)
+    for py in range(2):
+        for px in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    for ky in _PHASE_TAPS[py][ty]:
+                        for kx in _PHASE_TAPS[px][tx]:
+                            out[2 * py + px, :, ty, tx] += w[:, ky, kx]
+    return out
+
+
+class PhaseWeight:
+    """The phase weights of an upsampler conv for mf_conv_up2x: [4][N][2*2*Cin_pad], summed in fp32 from the master weight and rounded
+    ONCE to the storage dtype.  Derived from the conv's weight like every other layout (models.HipModel._put)."""
+
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor], prec: Precision, device):
+        if not prec.half:
+            raise hip.MfhipError("phase weights exist for the bf16 / fp16 modes")
+        n, cin = weight.shape[:2]
+        cp = _round_up(cin, prec.vec)
+        w = fold_phase_weights(weight.detach().to(device=device, dtype=torch.float32))
+        if cp != cin:
+            w = torch.nn.functional.pad(w, (0, cp - cin))
+        self.w = w.reshape(4, n, 4 * cp).to(prec.compute).contiguous()
+        self.bias = None if bias is None else bias.detach().to(device=device, dtype=torch.float32).contiguous()
+        self.n, self.cin, self.cin_pad, self.prec = n, cin, cp, prec
+
+
+def conv_up2x(x: torch.Tensor, pw: PhaseWeight, *, res0: Optional[torch.Tensor] = None, res1: Optional[torch.Tensor] = None,
+              alpha: float = 1.0, act: int = hip.ACT_NONE, splitk: int = 0, tile: int = 0, gn_part: Union[bool, int] = False) -> torch.Tensor:
+    """conv2d(x, cw, upsample=True) of a 3x3 / padding 1 conv as four 2x2 phase convs in one launch (mf_conv_up2x): 4/9 of the
+    multiply-adds, the same fused epilogue alpha * (conv + bias) + res0 + res1 and the same gn_part hand-over.  Inference only."""
+    if TAPE is not None:
+        raise hip.MfhipError("conv_up2x is inference only: training keeps conv2d(upsample=True)")
+    b, h, w, c0 = x.shape
+    if c0 != pw.cin_pad or not x.is_contiguous():
+        raise hip.MfhipError(f"conv_up2x: a contiguous NHWC input of {pw.cin_pad} channels (got {tuple(x.shape)})")
+    out = torch.empty(b, 2 * h, 2 * w, pw.n, dtype=pw.prec.act, device=x.device)
+    return hip.conv_up2x(x, pw.w, out, c0=c0, batch=b, h_in=h, w_in=w, n=pw.n, bias=pw.bias, res0=res0, res1=res1,
+                         res1_rows=_shared_rows(res1, b * 4 * h * w, pw.n), alpha=alpha, act=act, splitk=splitk, tile=tile,
+                         gn_part=(gn_part if _want_gn_part(gn_part, 4 * h * w, pw.n) else False))
+
+
 def linear(x: torch.Tensor, lw: ConvWeight, *, res0: Optional[torch.Tensor] = None,
            res1: Optional[torch.Tensor] = None, alpha: float = 1.0, act: int = hip.ACT_NONE,
            out_dtype: Optional[torch.dtype] = None, splitk: int = 0, tile: int = 0,

@@ -56,11 +56,15 @@ SIGNATURES_CALL["mf_axpby_n"] = "p" * _AXPBY_MAX + "f" * _AXPBY_MAX + "ipl"
 # table, as the two above are pinned as they stand.
 _REPLAYABLE_NOISE = ("mf_sched_step_noise_dev", "mf_philox_advance")
 SIGNATURES_NOISE = {name: hip.SIGNATURES[name][2:-1] for name in _REPLAYABLE_NOISE}
-_ALL_SIGNATURES = {**SIGNATURES, **SIGNATURES_CALL, **SIGNATURES_NOISE}
+# The upsampler convs of a denoise step in their phase form (models._UNetCore._upsample_conv): mf_conv_up2x takes the mf_gemm_desc struct
+# like mf_gemm_conv.  csrc/program.hip's kUpFns; a fourth table, as the first two are pinned as they stand.
+_REPLAYABLE_UP = ("mf_conv_up2x",)
+SIGNATURES_UP = {name: hip.SIGNATURES[name][2:-1].replace("G", "d") for name in _REPLAYABLE_UP}
+_ALL_SIGNATURES = {**SIGNATURES, **SIGNATURES_CALL, **SIGNATURES_NOISE, **SIGNATURES_UP}
 # queries / developer switches: forwarded, never recorded
 _PASS_THROUGH = ("mf_last_error", "mf_abi_version", "mf_gemm_num_tiles", "mf_gemm_tile_shape", "mf_gemm_tile_table_version",
                  "mf_groupnorm_ws_floats", "mf_sizeof_gemm_desc", "mf_sizeof_groupnorm_desc", "mf_sizeof_sched_row", "mf_minmax_ws_floats",
-                 "mf_gemm_conv_plan", "mf_sizeof_gemm_plan", "mf_groupnorm_slab_applies")
+                 "mf_gemm_conv_plan", "mf_sizeof_gemm_plan", "mf_groupnorm_slab_applies", "mf_conv_up2x_plan")
 # descriptor fields that are HOST out-pointers (the library reports a choice through them): null in a program
 _HOST_FIELDS = {"gn_part_rows", "gn_grouped", "deferred_splits"}
 

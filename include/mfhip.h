@@ -453,7 +453,11 @@ int mf_split_overflow(int32_t reset, int32_t* raised, void* stream);
 
 /* Per-row dynamic fp8 (e4m3) quantisation of [rows][c] (c % 8 == 0, c <= 8192), optionally fused behind a LayerNorm
  * (gamma / beta non-NULL: y = LN(x) first, attention.py:203,233,261): out_q[r][j] = fp8(y[r][j] / scale[r]),
- * scale[r] = max_j |y[r][j]| / 448.  The pair (out_q, scale) is an fp8 GEMM's A operand + a_scale. */
+ * scale[r] = max_j |y[r][j]| / 448.  The pair (out_q, scale) is an fp8 GEMM's A operand + a_scale.
+ * In fp32: scale = amax * fl(1 / 448) (1 for an all-zero row), out_q = RNE_e4m3(clamp(y * (1 / scale), -448, 448)); a row with
+ * amax < 2^-64 is multiplied by 2^64 first, so that 1 / scale stays finite.  A row of y that holds a NaN or an Inf (with the
+ * LayerNorm: a row of x that does) gets scale[r] = NaN and every code NaN (0x7F), so that the GEMM's output row is NaN as in
+ * every other precision; the other rows are not affected. */
 int mf_quantize_rows_fp8(const void* x, int32_t in_dtype, void* out_q, float* scale, int64_t rows, int32_t c,
                          const float* gamma, const float* beta, float eps, void* stream);
 

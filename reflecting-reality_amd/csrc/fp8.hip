@@ -3,6 +3,16 @@
 // MI355X-side precision choice for the layers whose arithmetic is attention.py:203-412 (LayerNorm -> Linear).
 // One half-wave per row, 8-channel (16-byte) vectors, the row stays in registers between the passes: one read of x,
 // one 1-byte-per-element write.  scale[r] = max|y| / 448 (448 = largest e4m3 value), q = fp8(y / scale).
+//
+// The arithmetic, which tests/fp8_ref.py quantize_contract repeats step by step in fp32: amax = max|y| over the row,
+// sc = amax * fl(1 / 448) (1 for an all-zero row), inv = 1 / sc, q = RNE_e4m3(clamp(y * inv, -448, 448)).  A row whose amax
+// lies below 2^-64 is multiplied by 2^64 first (exact), so that 1 / sc stays finite down to the smallest denormal.
+// The fused LayerNorm is two-pass in fp32 with the mean refined once (mean + mean(x - mean)), so that rows whose mean dwarfs their
+// spread come out as accurately as well-centred ones (tests/test_fp8_audit_gpu.py, the conditioning ladder).
+// Non-finite rows: a row of y that holds a NaN or an Inf (with the LayerNorm, one in x makes the whole row of y so) comes out
+// with scale[r] = NaN and every code NaN (0x7F): the GEMM's dequantisation carries the NaN into every output of that row, as
+// every other precision does.  The maximum is taken on the bit patterns of |y| as unsigned integers, which order like the
+// values and put Inf and every NaN above all finite values: a NaN cannot drop out of it as it does out of fmaxf.
 #include "mf_common.h"
 
 namespace {
@@ -47,12 +57,25 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const char* x, int 
 #pragma unroll
         for (int off = LPR / 2; off >= 1; off >>= 1) s += __shfl_xor(s, off, LPR);
         const float mean = s / (float)C;
+        // the mean once more, of x - mean: one fp32 number holds the mean to 2^-25 |mean|, which rstd magnifies by |mean| / std in
+        // every output of a row whose mean dwarfs its spread (4 % of gamma on a constant row of 77.7); x - mean is exact or nearly so
+        // there, and its own mean recovers the bits that were lost
+        float r = 0.0f;
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j)
+            if (l32 + LPR * j < c8n) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { v[j][e] -= mean; r += v[j][e]; }
+            }
+#pragma unroll
+        for (int off = LPR / 2; off >= 1; off >>= 1) r += __shfl_xor(r, off, LPR);
+        const float mlo = r / (float)C;
         float q = 0.0f;
 #pragma unroll
         for (int j = 0; j < MAXV; ++j)
             if (l32 + LPR * j < c8n) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { const float d = v[j][e] - mean; q += d * d; }
+                for (int e = 0; e < 8; ++e) { v[j][e] -= mlo; q += v[j][e] * v[j][e]; }
             }
 #pragma unroll
         for (int off = LPR / 2; off >= 1; off >>= 1) q += __shfl_xor(q, off, LPR);
@@ -65,20 +88,24 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const char* x, int 
                 load8f(reinterpret_cast<const char*>(gamma), MF_F32, c8 * 8, g);
                 load8f(reinterpret_cast<const char*>(beta), MF_F32, c8 * 8, bb);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[j][e] = (v[j][e] - mean) * rstd * g[e] + bb[e];
+                for (int e = 0; e < 8; ++e) v[j][e] = v[j][e] * rstd * g[e] + bb[e];
             }
         }
     }
-    float amax = 0.0f;
+    unsigned abits = 0u;                                // max |y| as bits: NaN > Inf > every finite value
 #pragma unroll
     for (int j = 0; j < MAXV; ++j)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[j][e]));
+        for (int e = 0; e < 8; ++e) abits = max(abits, __float_as_uint(v[j][e]) & 0x7fffffffu);
 #pragma unroll
-    for (int off = LPR / 2; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, LPR));
+    for (int off = LPR / 2; off >= 1; off >>= 1) abits = max(abits, (unsigned)__shfl_xor((int)abits, off, LPR));
     if (!live) return;
-    const float sc = amax > 0.0f ? amax * (1.0f / 448.0f) : 1.0f;
-    const float inv = 1.0f / sc;
+    const bool bad = abits >= 0x7f800000u;              // the row holds an Inf or a NaN
+    const float amax = __uint_as_float(abits);
+    const float up = amax < 0x1p-64f ? 0x1p64f : 1.0f;  // rows of denormal-sized values: 1 / sc would overflow
+    const float scu = (amax * up) * (1.0f / 448.0f);
+    const float sc = bad ? __uint_as_float(0x7fc00000u) : (amax > 0.0f ? scu * (1.0f / up) : 1.0f);
+    const float inv = 1.0f / (amax > 0.0f ? scu : 1.0f);
     if (l32 == 0) scale[row] = sc;
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {
@@ -86,12 +113,13 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const char* x, int 
         if (c8 < c8n) {
             float y[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) y[e] = fminf(fmaxf(v[j][e] * inv, -448.0f), 448.0f);
+            for (int e = 0; e < 8; ++e) y[e] = fminf(fmaxf((v[j][e] * up) * inv, -448.0f), 448.0f);
             int lo = 0, hi = 0;
             lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
             lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
             hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
             hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+            if (bad) lo = hi = 0x7f7f7f7f;
             *reinterpret_cast<uint2*>(out + row * C + c8 * 8) = uint2{(unsigned)lo, (unsigned)hi};
         }
     }

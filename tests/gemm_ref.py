@@ -7,6 +7,9 @@ calls a project kernel: plain torch float64, on whatever device the operands liv
 
 `ops` maps a descriptor pointer field ("a0", "a1", "w", "bias", "temb", "res0", "res1", "ln_colsum") to a flat tensor whose element
 0 sits at that pointer, in the pointer's storage dtype.  A descriptor that uses a field the model does not cover raises NotModelled.
+
+fp8 (dtype == a_dtype == MF_FP8): "a0" / "w" are torch.float8_e4m3fn tensors, "a_scale" / "w_scale" fp32 ones read at
+(z / zdiv) * a_scale_zs + m and (z / zdiv) * w_scale_zs + n; v = acc * rs[m] * cs[n] before the bias, the order of epilogue_store.
 """
 from __future__ import annotations
 
@@ -20,6 +23,7 @@ import torch
 MF_F32, MF_BF16, MF_F16X3, MF_BF16X3, MF_FP8, MF_BF16X1, MF_F16 = 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_SILU, ACT_GEGLU4 = 0, 1, 2
 TORCH_DT = {MF_F32: torch.float32, MF_BF16: torch.bfloat16, MF_F16: torch.float16}
+FP8_DT = torch.float8_e4m3fn
 SPLIT_CODES = (MF_F16X3, MF_BF16X3)
 
 # Error bounds, in units of S (the sum of |a_k w_k| after the epilogue's first-order propagation, see reference()).
@@ -51,6 +55,12 @@ LN_A = 2.0 ** -20
 # single rounding of gemm_conv_kernel.  The model follows the tile it is given.  Where the exact intermediate lies within
 # 2^-18 S of a rounding boundary the kernel may round it the other way: two intermediate ulps (one ulp of the larger binade at a
 # binade edge), times the gain of what follows, are then allowed in `a`.
+# fp8: the block-scaled MFMA (v_mfma_scale_f32_32x32x64_f8f6f4) sums its 64 products per step with fewer bits than a chain of fp32
+# FMAs.  No derivation is at hand; the figure is the project's own (tests/test_fp8_gpu.py: measured 4e-5 ... 7e-5 of the result's
+# rms, asserted at 2e-4), made scale-aware: a[m, n] = 2e-4 R rs[m] cs[n] |alpha| with R the float64 rms of the unscaled code product
+# q_a q_w^T over the case.  Rows out of the quantiser all have amax 448, so the code product is homogeneous across rows and columns
+# and a small rs[m] or cs[n] shrinks the allowance with the output.  It goes into Ref.a and through the epilogue gains like LN_A.
+FP8_A = 2e-4
 PERS_TILE = 70
 SENTINEL = 0x7B          # byte pattern of untouched output memory: bf16 / fp32 1.3e36, fp16 61280 (finite, never a result here)
 
@@ -69,12 +79,14 @@ class Ref:
 
 def check_supported(d) -> None:
     why = []
-    if d.dtype not in (MF_F32, MF_BF16, MF_F16) + SPLIT_CODES:
+    if d.dtype not in (MF_F32, MF_BF16, MF_F16, MF_FP8) + SPLIT_CODES:
         why.append(f"compute code {d.dtype}")
     if d.a_dtype != d.dtype and not (d.a_dtype == MF_F32 and d.dtype in (MF_BF16,) + SPLIT_CODES):
         why.append(f"a_dtype {d.a_dtype} with dtype {d.dtype}")
-    if d.a_scale or d.w_scale:
-        why.append("a_scale / w_scale (fp8 dequantisation)")
+    if (d.a_scale or d.w_scale) and d.dtype != MF_FP8:
+        why.append("a_scale / w_scale without the fp8 code")
+    if d.dtype == MF_FP8 and (d.ln_colsum or d.vt_out):
+        why.append("fp8 with ln_colsum / vt_out (the entry refuses it)")
     if d.w_split and d.dtype not in SPLIT_CODES:
         why.append("w_split with a non-split code")
     if d.nz < 1 or d.zdiv < 1:
@@ -120,6 +132,13 @@ def zoff(z: int, zdiv: int, o: int, i: int) -> int:
     return (z // zdiv) * o + (z % zdiv) * i
 
 
+def _take(buf: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """buf[idx]; fp8 storage is indexed through its bytes."""
+    if buf.dtype == FP8_DT:
+        return buf.view(torch.uint8)[idx].view(FP8_DT).float()
+    return buf[idx]
+
+
 def _a_values(d, t: torch.Tensor) -> torch.Tensor:
     """Operand A as the kernel multiplies it: 16-bit storage as is, fp32 storage under a bf16 code rounded to bf16 (RNE), fp32
     under the split and fp32 codes as is."""
@@ -149,7 +168,7 @@ def gather_a(d, ops, rows: torch.Tensor, z: int = 0) -> torch.Tensor:
             pix = (b * d.h_in + sy) * d.w_in + sx
             for buf, c, lda in segs:
                 idx = za + pix[:, None] * lda + torch.arange(c, device=pix.device)[None, :]
-                v = _a_values(d, buf[idx])
+                v = _a_values(d, _take(buf, idx))
                 cols.append(torch.where(ok[:, None], v, torch.zeros((), dtype=v.dtype, device=v.device)))
     return torch.cat(cols, 1)
 
@@ -169,7 +188,7 @@ def w_matrix(d, ops, z: int = 0) -> torch.Tensor:
         w = buf[base + hi_off[None, :]].double() + buf[base + hi_off[None, :] + 32].double()
         return w[:, :k]
     wz = zoff(z, d.zdiv, d.w_zs_o, d.w_zs_i)
-    return buf[wz + nn[:, None] * d.ldw + torch.arange(k, device=dev)[None, :]].double()
+    return _take(buf, wz + nn[:, None] * d.ldw + torch.arange(k, device=dev)[None, :]).double()
 
 
 def _gelu(x):
@@ -180,8 +199,9 @@ def _gelu_d(x):
     return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
 
 
-def reference(d, ops, rows: torch.Tensor, zs: Optional[List[int]] = None) -> Ref:
-    """Exact output and S for output rows `rows` (int64) of every z in `zs` (default all)."""
+def reference(d, ops, rows: torch.Tensor, zs: Optional[List[int]] = None, fp8_allow: float = FP8_A) -> Ref:
+    """Exact output and S for output rows `rows` (int64) of every z in `zs` (default all).  fp8_allow: FP8_A above; 0 for cases
+    whose products and sums are exact in fp32 (small integer codes, power-of-two scales)."""
     check_supported(d)
     dev = ops["a0"].device
     rows = rows.to(dev)
@@ -192,12 +212,19 @@ def reference(d, ops, rows: torch.Tensor, zs: Optional[List[int]] = None) -> Ref
     if pers and d.out_dtype == MF_F32:
         raise NotModelled("tile 70 with an fp32 output")
     vs, ss, al = [], [], []
-    for z in zs:
-        a = gather_a(d, ops, rows, z)
-        w = w_matrix(d, ops, z)
+    fp8 = d.dtype == MF_FP8
+    prods = [(gather_a(d, ops, rows, z), w_matrix(d, ops, z)) for z in zs]
+    if fp8:         # R: the rms of the unscaled code product over the case (FP8_A)
+        code_rms = math.sqrt(sum(float(((a @ w.T) ** 2).sum()) for a, w in prods) / max(1, len(zs) * len(rows) * n))
+    for z, (a, w) in zip(zs, prods):
         acc = a @ w.T
         s = a.abs() @ w.abs().T
         allow = torch.zeros_like(acc)
+        if fp8:
+            rs = ops["a_scale"][(z // d.zdiv) * d.a_scale_zs + rows].double()[:, None] if d.a_scale else torch.ones((), dtype=torch.float64, device=dev)
+            cs = ops["w_scale"][(z // d.zdiv) * d.w_scale_zs + ncol].double()[None, :] if d.w_scale else torch.ones((), dtype=torch.float64, device=dev)
+            g = (rs * cs).abs()
+            acc, s, allow = acc * rs * cs, s * g, allow + fp8_allow * code_rms * g
         if d.ln_colsum:
             # out = rstd[m] (acc - mean[m] colsum[n]): mean / var of the A row over K (population variance), in the kernel from fp32
             # sums: d(mean) ~ mean|a|, d(var) ~ mean(a^2) + |mean| mean|a| (cancellation of E[a^2] - mean^2), d(rstd)/rstd ~ d(var)/var

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import attention_ref as A
-from test_gemm_launches_gpu import Buf
+from gemm_audit import Buf
 
 pytestmark = pytest.mark.gpu
 

@@ -227,8 +227,87 @@ def test_model_vt_out_transpose():
     assert ob == [(0, m, n0, ldc)] and vb == [(0, imgs * (n - n0), tokens, vt_ld)]
 
 
+def _fp8_case(seed=15, m=5, n=7, k=48, nz=2):
+    """A small batched fp8 descriptor with strides of its own everywhere: (d, ops, codes A [nz, m, k], W [nz, n, k], rs, cs, bias)."""
+    g = torch.Generator().manual_seed(seed)
+    lda, ldw, a_zs, w_zs, rs_zs, cs_zs = k + 16, k + 32, m * (k + 16) + 16, n * (k + 32) + 48, m + 3, n + 2
+    qa = (torch.randn(nz, m, k, generator=g) * 100).clamp(-448, 448).to(G.FP8_DT)
+    qw = (torch.randn(nz, n, k, generator=g) * 100).clamp(-448, 448).to(G.FP8_DT)
+    a = torch.full((nz * a_zs,), 448.0).to(G.FP8_DT)                          # gaps hold 448: a model that reads one is far off
+    w = torch.full((nz * w_zs,), 448.0).to(G.FP8_DT)
+    rs = torch.full((nz * rs_zs,), GAP)
+    cs = torch.full((nz * cs_zs,), GAP)
+    for z in range(nz):
+        a.view(torch.uint8)[z * a_zs: z * a_zs + m * lda].view(m, lda)[:, :k] = qa[z].view(torch.uint8)
+        w.view(torch.uint8)[z * w_zs: z * w_zs + n * ldw].view(n, ldw)[:, :k] = qw[z].view(torch.uint8)
+        rs[z * rs_zs: z * rs_zs + m] = torch.exp2(torch.randint(-12, 12, (m,), generator=g).float()) * (1 + torch.rand(m, generator=g))
+        cs[z * cs_zs: z * cs_zs + n] = torch.exp2(torch.randint(-12, 12, (n,), generator=g).float()) * (1 + torch.rand(n, generator=g))
+    bias = torch.randn(m, generator=g)
+    d = desc(dtype=G.MF_FP8, a_dtype=G.MF_FP8, out_dtype=G.MF_F32, c0=k, lda0=lda, h_in=m, h_out=m, ldw=ldw, n=n, nz=nz,
+             a_zs_o=a_zs, w_zs_o=w_zs, o_zs_o=m * n, ldc=n, a_scale=1, w_scale=1, a_scale_zs=rs_zs, w_scale_zs=cs_zs,
+             bias=1, bias_mode=1, alpha=-0.75)
+    ops = {"a0": a, "w": w, "a_scale": rs, "w_scale": cs, "bias": bias}
+    return d, ops, qa, qw, rs.view(nz, rs_zs)[:, :m], cs.view(nz, cs_zs)[:, :n], bias
+
+
+def test_model_fp8_matches_a_brute_force_loop():
+    """5 x 7 x 48 with nz = 2: v = alpha (acc rs[m] cs[n] + bias[m]) by a plain float64 loop over every (z, m, n, k); S and the
+    fp8 allowance 2e-4 R rs cs |alpha| with R the rms of the unscaled code product."""
+    d, ops, qa, qw, rs, cs, bias = _fp8_case()
+    nz, m, k = qa.shape
+    n = qw.shape[1]
+    ref = G.reference(d, ops, all_rows(d))
+    fa, fw = qa.float().double().tolist(), qw.float().double().tolist()
+    want = torch.zeros(nz, m, n, dtype=torch.float64)
+    want_s = torch.zeros_like(want)
+    code = torch.zeros_like(want)
+    for z in range(nz):
+        for i in range(m):
+            for j in range(n):
+                acc = sabs = 0.0
+                for kk in range(k):
+                    acc += fa[z][i][kk] * fw[z][j][kk]
+                    sabs += abs(fa[z][i][kk] * fw[z][j][kk])
+                g = float(rs[z, i].double() * cs[z, j].double())
+                code[z, i, j] = acc
+                want[z, i, j] = -0.75 * (acc * g + float(bias[i]))
+                want_s[z, i, j] = 0.75 * (sabs * g + abs(float(bias[i])))
+    torch.testing.assert_close(ref.v, want, rtol=1e-13, atol=0)
+    torch.testing.assert_close(ref.s, want_s, rtol=1e-13, atol=0)
+    rms = float((code ** 2).mean().sqrt())
+    want_a = 2e-4 * rms * 0.75 * rs.double()[:, :, None] * cs.double()[:, None, :]
+    torch.testing.assert_close(ref.a, want_a, rtol=1e-12, atol=0)
+    assert float(ref.a.max() / ref.a.min()) > 1e3                 # the allowance follows the scales
+    exact = G.reference(d, ops, all_rows(d), fp8_allow=0.0)
+    assert float(exact.a.abs().max()) == 0.0 and torch.equal(exact.v, ref.v)
+    # one z alone, and a GEGLU epilogue: the allowance goes through the gains like LN_A
+    one = G.reference(d, ops, all_rows(d), zs=[1])
+    torch.testing.assert_close(one.v[0], want[1], rtol=1e-13, atol=0)
+
+
+def test_model_fp8_geglu_and_what_stays_refused():
+    g = torch.Generator().manual_seed(16)
+    m, k, n = 6, 32, 16
+    qa = (torch.randn(m, k, generator=g) * 60).clamp(-448, 448).to(G.FP8_DT)
+    qw = (torch.randn(n, k, generator=g) * 60).clamp(-448, 448).to(G.FP8_DT)
+    rs, cs = torch.rand(m, generator=g) * 1e-2, torch.rand(n, generator=g) * 1e-2
+    bias = torch.randn(n, generator=g)
+    ops = {"a0": qa.flatten(), "w": qw.flatten(), "a_scale": rs, "w_scale": cs, "bias": bias}
+    kw = dict(dtype=G.MF_FP8, a_dtype=G.MF_FP8, c0=k, lda0=k, h_in=m, h_out=m, ldw=k, n=n, a_scale=1, w_scale=1, bias=1)
+    ref = G.reference(desc(act=G.ACT_GEGLU4, ldc=n // 2, **kw), ops, torch.arange(m))
+    v = (qa.float().double() @ qw.float().double().T) * rs.double()[:, None] * cs.double()[None, :] + bias.double()
+    v = v.view(m, n // 8, 8)
+    torch.testing.assert_close(ref.v[0], (v[..., :4] * F.gelu(v[..., 4:])).reshape(m, n // 2), rtol=1e-12, atol=1e-14)
+    assert bool((ref.a > 0).all())
+    for bad in (dict(kw, ln_colsum=1), dict(kw, vt_out=1, vt_n0=8, vt_tokens=2),              # as the entry refuses them
+                dict(kw, dtype=G.MF_BF16, a_dtype=G.MF_BF16), dict(kw, dtype=G.MF_BF16, a_dtype=G.MF_BF16, a_scale=None),
+                dict(kw, a_dtype=G.MF_BF16), dict(kw, dtype=G.MF_BF16)):                    # a scale, or half of fp8, without the code
+        with pytest.raises(G.NotModelled):
+            G.reference(desc(**bad), ops, torch.arange(m))
+
+
 def test_model_refuses_what_it_does_not_cover():
-    for kw in ({"a_scale": 1}, {"dtype": G.MF_FP8}, {"dtype": G.MF_BF16X1}, {"defer_reduce": 1}, {"act": 7}):
+    for kw in ({"a_scale": 1}, {"w_scale": 1}, {"dtype": G.MF_BF16X1}, {"defer_reduce": 1}, {"act": 7}):
         d = desc(c0=8, lda0=8, ldw=8, n=8, **kw)
         with pytest.raises(G.NotModelled):
             G.reference(d, {"a0": torch.zeros(8, dtype=torch.bfloat16), "w": torch.zeros(64, dtype=torch.bfloat16)}, torch.arange(1))
